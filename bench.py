@@ -7,7 +7,7 @@ seeded synthetic generator (sparkglm_amd.synth; bit-identical host copy).  A "st
 one IRLS iteration: the fused pass over every resident row (eta, mu, w, z, deviance and
 the X'WX / X'Wz Gramian on fp64 MFMA) + the all-reduce over ranks + the p x p solve.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
                   [--workload logit256|poisson64|gamma2048|logit512|logit512r|logit1b|lm20]
                   [--rows R] [--p P]
 
@@ -17,10 +17,19 @@ torch.distributed.run, before anything touches the GPU) and exits with their sta
 holds its own 100M-row shard (weak scaling) and the per-iteration Gram all-reduce runs on RCCL
 over xGMI inside the engine.  Rank 0 prints ONE JSON line.
 
-The default run (N = 1) also measures, after the headline, the north-star 1B x 32 strong point
-(`strong_scaling_1b_logit`) and every other BASELINE config's per-GPU shard (`configs_n1`: configs[0]
-LM, the configs[2] Poisson, configs[3] gamma and configs[4] procedural shards), each with its own
-roofline object; `--no-strong` / `--no-configs` skip them.
+A plain run does only what the headline needs: it generates the shard, fits it once (the
+time-to-converge, and the coefficients the timed iterations start from), warms up, times the K
+steps and prints the line.  `--dump-outputs DIR` then writes what the last timed step returned to
+its caller as DIR/<name>.npy (float64): `coefs` and `deviance` of a GLM workload; `coefs`, `stderr`,
+`xtxi` and `scalars` (sse, r2, fstat, sigma) of lm20.  The shard comes from the seeded generator, so
+two runs with the same arguments see the same inputs.
+
+`--full` adds the measurements that take runs of their own: the CPU baseline (`cpu_baseline`), the
+host-to-HBM load probe (`load`) and, on the default workload, the north-star 1B x 32 strong point
+(`strong_scaling_1b_logit`) and at N = 1 every other BASELINE config's per-GPU shard (`configs_n1`:
+configs[0] LM, the configs[2] Poisson, configs[3] gamma and configs[4] procedural shards), each with
+its own roofline object; `--no-cpu-baseline` / `--no-load` / `--no-strong` / `--no-configs` skip
+single ones of them.
 """
 from __future__ import annotations
 
@@ -46,7 +55,7 @@ def log(*a):
 
 
 # BASELINE.json configs -> bench workloads.  The default (N=1 headline) is configs[1]; the others
-# are measured in the default run's configs_n1 and with --workload, recorded under profiles/ (rows per GPU = the config's global
+# are measured in a --full run's configs_n1 and with --workload, recorded under profiles/ (rows per GPU = the config's global
 # rows / 8 where the config is quoted on 8 GPUs, or the largest resident shard, as labelled).
 WORKLOADS = {
     "lm20": dict(cfg=0, kind=1, family="gaussian", link="identity", p=20, rows=1_000_000, seed=1, lm=True,
@@ -298,13 +307,18 @@ def main() -> int:
     ap.add_argument("--p", type=int, default=None)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--cpu-rows", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, the load probe and, on the default workload, the "
+                         "1B x 32 strong point and the other BASELINE configs' N = 1 points")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--comm", choices=["rccl", "torch"], default="rccl")
-    ap.add_argument("--no-load", action="store_true", help="skip the host-to-HBM load probe")
+    ap.add_argument("--no-load", action="store_true", help="--full: skip the host-to-HBM load probe")
     ap.add_argument("--no-strong", action="store_true",
-                    help="skip the 1B x 32 strong-scaling point measured after the default workload")
+                    help="--full: skip the 1B x 32 strong-scaling point measured after the default workload")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the other BASELINE configs' N = 1 points measured after the default workload")
+                    help="--full: skip the other BASELINE configs' N = 1 points measured after the default workload")
     args = ap.parse_args()
     wl = WORKLOADS[args.workload]
 
@@ -373,10 +387,12 @@ def main() -> int:
     eng.reset_stats()
     barrier()
     t0 = time.perf_counter()
-    beta, _ = eng.irls_iterations(beta, args.steps, fam, lnk)
+    beta, last_dev = eng.irls_iterations(beta, args.steps, fam, lnk)
     barrier()
     dt = time.perf_counter() - t0
     st = eng.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"coefs": beta, "deviance": [last_dev]})
     ranks_diag = rank_stats(st, args.steps, dist_on, shared)
     if dist_on:
         tt = torch.tensor([dt, ttc], dtype=torch.float64, device="cpu" if shared else "cuda")
@@ -423,19 +439,19 @@ def main() -> int:
             "ranks": ranks_diag,
             "solve_path": st["solve_path_name"],
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl, p, args.cpu_rows or wl["cpu_rows"])
         else:
             out["cpu_baseline"] = None
     eng.close()
-    if not args.no_load and rank == 0:
+    if args.full and not args.no_load and rank == 0:
         try:  # the H2D load of a host-resident design, reported apart from the fit;
             # rank 0 only (every rank would otherwise build ~4 GB of host arrays it throws away)
             out["load"] = load_probe(dev, p, wl, n)
         except Exception as exc:
             log(f"[rank {rank}] load probe failed: {exc}")
             out["load"] = None
-    if args.workload == "logit256" and not args.no_strong:
+    if args.full and args.workload == "logit256" and not args.no_strong:
         try:  # the north-star 1B-row strong-scaling point, beside the headline (own shard, freed after)
             strong_1b_res = strong_1b(args, dev, world, rank, dist_on, shared, barrier)
         except Exception as exc:  # never lose the headline line to the secondary measurement
@@ -443,7 +459,7 @@ def main() -> int:
             strong_1b_res = None
         if rank == 0:
             out["strong_scaling_1b_logit"] = strong_1b_res
-    if args.workload == "logit256" and world == 1 and not args.no_configs:
+    if args.full and args.workload == "logit256" and world == 1 and not args.no_configs:
         out["configs_n1"] = config_points(dev)
     if rank == 0:
         print(json.dumps(out), file=JSON_OUT, flush=True)
@@ -502,7 +518,7 @@ def pass_roofline(st: dict, wl: dict, n: int, p: int):
     return roof, pass_ms
 
 
-# The other BASELINE configs measured inside the default N = 1 run (after the headline and the strong
+# The other BASELINE configs measured inside the default workload's --full run at N = 1 (after the headline and the strong
 # point, each on its own engine, freed before the next), so the driver's run observes every config's
 # per-GPU shard, not only builder-side profiles/.  Compact: a fit to convergence, one warm-up
 # iteration, CONFIG_STEPS timed iterations (LM: CONFIG_LM_FITS timed fits).
@@ -579,6 +595,13 @@ def config_points(dev: int) -> dict:
             log(f"[rank 0] config point {name} failed: {exc}")
             out[name] = {"error": f"{type(exc).__name__}: {exc}"}
     return out
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array of the last timed step's result as <path>/<name>.npy, float64."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def load_probe(dev: int, p: int, wl: dict, n_shard: int, sample_bytes: float = 4e9) -> dict:
@@ -746,6 +769,9 @@ def run_lm(args, wl, eng, n, p, world, rank, dist_on, shared, barrier) -> int:
     barrier()
     dt = time.perf_counter() - t0
     st = eng.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"coefs": fit.coefs, "stderr": fit.stderr, "xtxi": fit.xtxi,
+                                         "scalars": [fit.sse, fit.r2, fit.fstat, fit.sigma]})
     if dist_on:
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if shared else "cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -773,7 +799,7 @@ def run_lm(args, wl, eng, n, p, world, rank, dist_on, shared, barrier) -> int:
             "breakdown_ms_per_step": {"gram_pass_kernel": kern_ms, "reduce": st["reduce_kernel_ms"] / args.steps,
                                       "solve": st["solve_ms"] / args.steps, "comm": st["comm_ms"] / args.steps},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl, p, args.cpu_rows or wl["cpu_rows"])
         else:
             out["cpu_baseline"] = None

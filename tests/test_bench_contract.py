@@ -1,6 +1,6 @@
 """bench.py's contract pieces: every workload maps to a BASELINE.json config with the family /
-shape it names, the traffic lookup, and the roofline bound choice (no GPU); the default run's
-config points on the device (gpu)."""
+shape it names, the traffic lookup, and the roofline bound choice (no GPU); the plain run, the
+--full run's extra measurements and its config points on the device (gpu)."""
 import importlib.util
 import json
 import os
@@ -72,7 +72,7 @@ def test_every_baseline_config_has_a_workload():
 
 
 def test_strong_scaling_point_and_p32_traffic():
-    # the default run appends the north-star 1B x 32 strong-scaling point (bench.strong_1b),
+    # the default workload's --full run appends the north-star 1B x 32 strong-scaling point (bench.strong_1b),
     # whose per-row PMC traffic the logit1b roofline uses
     assert callable(bench.strong_1b) and callable(bench.attach_comm)
     t = bench.pmc_traffic(32, 1000, "binomial")
@@ -247,7 +247,7 @@ def test_lm_line_traffic_comes_from_the_lm_pmc_entry():
 
 def test_default_run_covers_every_baseline_config():
     # the headline (configs[1]) + the strong 1B point + configs_n1: every config's per-GPU shard is
-    # measured by the driver's own default run, not only by builder-side --workload runs
+    # measured by one `bench.py --full` run of the default workload, not only by --workload runs
     cfgs = json.load(open(os.path.join(ROOT, "BASELINE.json")))["configs"]
     covered = {bench.WORKLOADS["logit256"]["cfg"]} | {bench.WORKLOADS[w]["cfg"] for w in bench.CONFIG_POINTS}
     assert covered == set(range(len(cfgs)))
@@ -272,11 +272,91 @@ def test_pass_roofline_from_stats():
     assert "kernel_frac_of_pipe_bound" in roof["fp64_pipe"]
 
 
+def test_dump_outputs_writes_float64_npy(tmp_path):
+    import numpy as np
+    d = tmp_path / "a" / "b"  # created on demand
+    bench.dump_outputs(str(d), {"coefs": np.arange(3, dtype=np.float32), "deviance": [1.5]})
+    assert sorted(os.listdir(d)) == ["coefs.npy", "deviance.npy"]
+    c, v = np.load(d / "coefs.npy"), np.load(d / "deviance.npy")
+    assert c.dtype == np.float64 and c.tolist() == [0.0, 1.0, 2.0]
+    assert v.dtype == np.float64 and v.shape == (1,) and v[0] == 1.5
+
+
+EXTRAS = ("cpu_baseline", "load_probe", "strong_1b", "config_points")
+
+
+def _run_main(monkeypatch, argv, called):
+    """bench.main() in this process on a reduced shard: the JSON line it prints, with the four
+    measurements that only a --full run makes replaced by stubs that record their call."""
+    import io
+    for name in EXTRAS:
+        monkeypatch.setattr(bench, name, lambda *a, _n=name, **k: called.append(_n) or {"stub": _n})
+    buf = io.StringIO()
+    monkeypatch.setattr(bench, "_guard_stdout", lambda: None)
+    monkeypatch.setattr(bench, "JSON_OUT", buf)
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py"] + argv)
+    assert bench.main() == 0
+    lines = buf.getvalue().splitlines()
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path, monkeypatch):
+    """A plain run makes none of the --full measurements, times exactly --steps iterations and, with
+    --dump-outputs, writes what the last timed iteration returned; the seeded shard makes a second
+    run with the same arguments write the same bits."""
+    import numpy as np
+    from sparkglm_amd import Engine
+    rows, steps, warm = 100_000, 3, 1
+    outs = []
+    for d in ("d1", "d2"):
+        called = []
+        line = _run_main(monkeypatch, ["--gpus", "1", "--rows", str(rows), "--steps", str(steps), "--warmup", str(warm),
+                                       "--dump-outputs", str(tmp_path / d)], called)
+        assert called == []
+        assert line["cpu_baseline"] is None
+        assert not {"load", "strong_scaling_1b_logit", "configs_n1"} & set(line)
+        assert line["steps"] == steps and line["warmup"] == warm and line["ms_per_step"] > 0
+        assert line["unit"] == "rows/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert abs(line["value"] - rows / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+        assert sorted(os.listdir(tmp_path / d)) == ["coefs.npy", "deviance.npy"]
+        outs.append((np.load(tmp_path / d / "coefs.npy"), np.load(tmp_path / d / "deviance.npy")))
+    (c1, v1), (c2, v2) = outs
+    assert c1.dtype == np.float64 and c1.shape == (256,) and v1.dtype == np.float64 and v1.shape == (1,)
+    assert np.array_equal(c1, c2) and np.array_equal(v1, v2)
+    # the same path by hand: fit, then warm + steps iterations from the fitted coefficients
+    wl = bench.WORKLOADS["logit256"]
+    with Engine(0) as eng:
+        eng.synth(wl["kind"], 0, rows, wl["p"], wl["seed"])
+        f = eng.fit_glm("binomial", "logit", tol=1e-6)
+        b, _ = eng.irls_iterations(np.array(f.coefs), warm, "binomial", "logit")
+        b, dev = eng.irls_iterations(b, steps, "binomial", "logit")
+    assert np.array_equal(c1, b) and v1[0] == dev
+
+
+@pytest.mark.gpu
+def test_full_run_makes_the_extra_measurements(monkeypatch):
+    """--full: the CPU baseline, the load probe, the 1B x 32 strong point and the other configs' N = 1
+    points are measured after the headline and carried by the same line; the --no-* options skip
+    single ones."""
+    called = []
+    argv = ["--gpus", "1", "--rows", "100000", "--steps", "2", "--warmup", "1", "--full"]
+    line = _run_main(monkeypatch, argv, called)
+    assert sorted(called) == sorted(EXTRAS)
+    assert line["load"] == {"stub": "load_probe"} and line["configs_n1"] == {"stub": "config_points"}
+    assert line["strong_scaling_1b_logit"] == {"stub": "strong_1b"} and line["cpu_baseline"] == {"stub": "cpu_baseline"}
+    called.clear()
+    line = _run_main(monkeypatch, argv + ["--no-strong", "--no-load"], called)
+    assert sorted(called) == ["config_points", "cpu_baseline"]
+    assert "load" not in line and "strong_scaling_1b_logit" not in line
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,rows", [("lm20", 200_000), ("poisson64", 400_000), ("gamma2048", 20_000),
                                        ("logit512", 100_000)])
 def test_config_point_runs_on_the_device(name, rows):
-    """The default bench run's configs_n1 points (bench.config_point) at reduced rows: each fits,
+    """A --full bench run's configs_n1 points (bench.config_point) at reduced rows: each fits,
     times its iterations and carries a roofline object with the bound SURVEY 8(d) assigns."""
     r = bench.config_point(name, 0, rows=rows)
     assert r["rows"] == rows and r["p"] == bench.WORKLOADS[name]["p"]

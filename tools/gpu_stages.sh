@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU session stages (one gpurun call runs the listed ones in order; each GPU step under its own timeout):
-#   test      pytest -m gpu + smoke()            bench    the default bench line (configs[1] + 1B x 32)
+#   test      pytest -m gpu + smoke()            bench    the default workload's --full bench line (configs[1] + 1B x 32 + configs_n1)
 #   benchw    WORKLOADS="..." bench lines         lm       configs[0] LM timeline + rocprof
 #   sweep     mid-width sweep (+ rocprof)        cap      full-size configs[3] Gram capture
 #   rehearse8 8 ranks over gloo on one GPU        pmcab    PMC of one workload under PMCAB_LIBS
@@ -10,6 +10,8 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 STAGES=${1:-cap,test,bench}
+OUT=${OUT:-out}  # where the bench stages (bench, rehearse8) leave their lines
+mkdir -p "$OUT" && OUT=$(cd "$OUT" && pwd) || exit 1
 if [[ ,$STAGES, == *,cap,* ]]; then
   timeout -k 10 300 python -u tools/gram_split_capture.py > gpurun_out/cap.log 2>&1 || { echo "capture failed"; tail -20 gpurun_out/cap.log; exit 1; }
   tail -3 gpurun_out/cap.log
@@ -39,12 +41,12 @@ if [[ ,$STAGES, == *,lm,* ]]; then  # configs[0] host overhead: wall per fit, th
   timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats -d "$GRAFT_REPO_ROOT/gpurun_out/prof_lm" -o lm --output-format csv -- python tools/lm_timeline.py 100 > gpurun_out/prof_lm.log 2>&1 || { echo "lm prof failed"; tail gpurun_out/prof_lm.log; exit 1; }
 fi
 if [[ ,$STAGES, == *,rehearse8,* ]]; then  # 8 ranks sharing this GPU over gloo (the 8-GPU launch path)
-  timeout -k 10 900 python bench.py --gpus 8 --rows 10000000 --steps 3 --warmup 1 --no-load > gpurun_out/bench_gpus8.json 2> gpurun_out/bench_gpus8.err || { echo "rehearsal failed"; tail -20 gpurun_out/bench_gpus8.err; exit 1; }
-  python -c "import json; d=json.load(open('gpurun_out/bench_gpus8.json')); s=d['strong_scaling_1b_logit']; print('gpus8', d['n_gpus'], d['ms_per_step'], d['iters_to_converge'], s['n_gpus'], s['iters_to_converge'], repr(s['deviance']))"
+  timeout -k 10 900 python bench.py --full --gpus 8 --rows 10000000 --steps 3 --warmup 1 --no-load > "$OUT/bench_gpus8.json" 2> "$OUT/bench_gpus8.err" || { echo "rehearsal failed"; tail -20 "$OUT/bench_gpus8.err"; exit 1; }
+  python -c "import json; d=json.load(open('$OUT/bench_gpus8.json')); s=d['strong_scaling_1b_logit']; print('gpus8', d['n_gpus'], d['ms_per_step'], d['iters_to_converge'], s['n_gpus'], s['iters_to_converge'], repr(s['deviance']))"
 fi
 if [[ ,$STAGES, == *,bench,* ]]; then
-  timeout -k 10 600 python bench.py --steps 10 --warmup 2 > gpurun_out/bench.json 2> gpurun_out/bench.err || { echo "bench failed"; tail -20 gpurun_out/bench.err; exit 1; }
-  python -c "import json; d=json.load(open('gpurun_out/bench.json')); r=d['roofline']; s=d.get('strong_scaling_1b_logit') or {}; print(d['ms_per_step'], r['kernel'], r['kernel_ms'], r['frac'], d['time_to_converge_s'], s.get('ms_per_iter'), s.get('time_to_converge_s'))"
+  timeout -k 10 600 python bench.py --full --steps 10 --warmup 2 > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
+  python -c "import json; d=json.load(open('$OUT/bench.json')); r=d['roofline']; s=d.get('strong_scaling_1b_logit') or {}; print(d['ms_per_step'], r['kernel'], r['kernel_ms'], r['frac'], d['time_to_converge_s'], s.get('ms_per_iter'), s.get('time_to_converge_s'))"
 fi
 if [[ ,$STAGES, == *,pmcab,* ]]; then  # PMC of one workload (PMCAB_WL name:PN:PP:PKIND:PF:PL) under each library of PMCAB_LIBS
   export TMPDIR=/tmp
