@@ -63,7 +63,9 @@ extern "C" {
                               lm_device_reruns; 8: sglm_create(devs, ndev) as SURVEY 8(b) names it,
                               the one-device form renamed sglm_create_device (sglm_create_multi stays:
                               the group handle at any ndev), SGLM_KERNEL_NARROW_SPLIT retired,
-                              sglm_stats.lm_onepass_fits */
+                              sglm_stats.lm_onepass_fits.  Added since, without a version change (new
+                              symbols only): sglm_vcov, sglm_influence, sglm_predict_new_se,
+                              sglm_get_influence_ms, enum sglm_resid_type */
 
 enum sglm_status {
   SGLM_OK = 0,
@@ -321,6 +323,38 @@ int sglm_predict_glm(sglm_engine *h, const double *beta, int family, int link, i
 int sglm_predict_new(sglm_engine *h, const double *X, int64_t n, int64_t p, int64_t ldx,
                      const double *beta, const double *offset, const double *m, int family, int link,
                      int type, double *out);
+
+/* ---- per-row diagnostics (R's hatvalues / residuals / cooks.distance / predict(se.fit = TRUE)) ----
+ * Resident designs with p <= 256 on the fused / narrow path; procedural shards, wider designs and
+ * SGLM_FORCE_WIDE return SGLM_EINVAL before any launch.  All rest on the row quadratic form
+ * q_i = x_i' C x_i, C = inv(X'WX) (influence.hip).  Residuals are on the engine's count scale
+ * (mu = unlink(eta, m)): divide binomial residuals by m for R's proportion scale. */
+enum sglm_resid_type { SGLM_RESID_RESPONSE = 0, SGLM_RESID_WORKING = 1, SGLM_RESID_PEARSON = 2, SGLM_RESID_DEVIANCE = 3 };
+
+/* Unscaled covariance inv(X'WX) at beta, col-major [p*p]: one IRLS pass at beta (collective over a
+ * communicator, as sglm_irls_pass) and the fit's own solve rule; SGLM_ESINGULAR as the fit. */
+int sglm_vcov(sglm_engine *h, const sglm_glm_opts *opts, const double *beta, double *cov);
+
+/* Per-row diagnostics of the resident rows at beta (computes sglm_vcov internally, so it is
+ * collective too).  Any output may be NULL: hat [n_local] leverage h = w q; resid [n_local] of
+ * resid_type (enum sglm_resid_type); cooks [n_local] = (r_P / (1 - h))^2 h / (dispersion p) with the
+ * Pearson residual r_P whatever resid_type is; sum_hat: sum of h over the local rows, summed in a
+ * fixed order (calls are run-to-run bitwise identical).  dispersion <= 0 is SGLM_EINVAL.  With hat,
+ * cooks and sum_hat all NULL the quadratic forms are skipped.  A multi-device handle returns its
+ * shards' rows concatenated in row order; with a communicator each rank gets its own rows against
+ * the global C.  Gaussian / identity covers LM: w = 1, C = inv(X'X), dispersion = sigma^2. */
+int sglm_influence(sglm_engine *h, const sglm_glm_opts *opts, const double *beta, int resid_type,
+                   double dispersion, double *hat, double *resid, double *cooks, double *sum_hat);
+
+/* se.fit on the link scale for NEW rows: out[i] = sqrt(max(0, dispersion * x_i' cov x_i)), X
+ * column-major n x p (ldx >= n, p <= 256), cov col-major [p*p] (sglm_vcov, or sglm_prelm.xtxi).
+ * Streams X through sglm_predict_new's scratch; the resident shard is untouched. */
+int sglm_predict_new_se(sglm_engine *h, const double *X, int64_t n, int64_t p, int64_t ldx,
+                        const double *cov, double dispersion, double *out);
+
+/* Kernel time of the last sglm_influence call on this handle (HIP events; a multi-device handle:
+ * its slowest shard; -1 before any call). */
+int sglm_get_influence_ms(sglm_engine *h, double *kernel_ms);
 
 int sglm_get_stats(sglm_engine *h, sglm_stats *out);
 /* The kernel an engine would run a pass of an n x p shard with (enum sglm_pass_kernel, -1 on bad

@@ -32,8 +32,10 @@ EXPORTS = [
     "sglm_pval_normal", "sglm_pval_t", "sglm_create_device", "sglm_create_multi", "sglm_handle_devices", "sglm_reserve", "sglm_set_rows",
     "sglm_predict_glm", "sglm_predict_new", "sglm_local_comm_create", "sglm_local_comm_destroy",
     "sglm_local_comm_rank", "sglm_local_allreduce", "sglm_set_comm_rank", "sglm_pass_kernel_for",
+    "sglm_vcov", "sglm_influence", "sglm_predict_new_se", "sglm_get_influence_ms",
 ]
 PREDICT_LINK, PREDICT_RESPONSE = 0, 1
+RESID_TYPES = {"response": 0, "working": 1, "pearson": 2, "deviance": 3}  # enum sglm_resid_type
 
 dp = C.POINTER(C.c_double)
 
@@ -171,6 +173,10 @@ def load():
         "sglm_local_allreduce": ([C.c_void_p, dp, C.c_int64, C.c_void_p, C.c_int], C.c_int),
         "sglm_pass_kernel_for": ([C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int64],
                                  C.c_int),
+        "sglm_vcov": ([h, C.POINTER(GlmOpts), dp, dp], C.c_int),
+        "sglm_influence": ([h, C.POINTER(GlmOpts), dp, C.c_int, C.c_double, dp, dp, dp, dp], C.c_int),
+        "sglm_predict_new_se": ([h, dp, C.c_int64, C.c_int64, C.c_int64, dp, C.c_double, dp], C.c_int),
+        "sglm_get_influence_ms": ([h, dp], C.c_int),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("SGLM_LIB") and not hasattr(lib, name):

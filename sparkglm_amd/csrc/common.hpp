@@ -140,6 +140,31 @@ struct WideGramArgs {
   int64_t nb_lim;       // blocks of this launch's rows: pieces are clipped to [b0, min(b1, nb_lim))
 };
 
+// Row quadratic forms q_i = x_i' C x_i and the per-row diagnostics built on them (influence.hip).
+constexpr int INFL_TILE = 256;  // doubles per 16 x 16 tile of C~ (MFMA operand order, influence_tiles)
+struct InflArgs {
+  const double* X;      // col-major, leading dimension ld; columns >= p are never read
+  int64_t ld;
+  int p;
+  int64_t n;            // rows; rows >= n are never read or stored
+  const double* ct;     // C~ tiles [P16 (P16 + 1) / 2][INFL_TILE] (null with need_q = 0)
+  int need_q;           // 0: no MFMA product (residuals only)
+  // influence_kernel: the row stage at beta
+  const double* beta;   // device [p]
+  const double* y;
+  const double* m;      // may be null
+  const double* off;    // may be null
+  const double* prior;  // may be null
+  int family, link, resid_type;
+  double dispersion;    // phi of Cook's distance / of the qform_kernel's sqrt(phi q)
+  double* hat;          // outputs [n], any may be null
+  double* resid;
+  double* cooks;
+  double* hpart;        // [grid] per-workgroup sums of h (null: not wanted)
+  // qform_kernel: out[i] = sqrt(max(0, dispersion * q_i))
+  double* out;
+};
+
 // Arguments of the final-statistics pass (stats_kernel).
 struct StatsArgs {
   const double* y;

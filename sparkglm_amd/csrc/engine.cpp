@@ -518,6 +518,7 @@ struct sglm_engine : public Backend {
     }
     xs_cap = vs_cap = 0;
     dsmall_cap = 0;
+    free_influence();
     for (int k = 0; k < 2; ++k) {
       if (hstage[k]) (void)hipHostFree(hstage[k]);
       if (evstage[k]) (void)hipEventDestroy(evstage[k]);
@@ -1142,6 +1143,151 @@ struct sglm_engine : public Backend {
     HIPCHK(hipHostMalloc(&hred, sizeof(double) * need, hipHostMallocDefault));
     HIPCHK(hipHostMalloc(&hbeta, sizeof(double) * need, hipHostMallocDefault));
     red_cap = need;
+    return SGLM_OK;
+  }
+
+  // ---- per-row diagnostics (influence.hip): leverage, residuals, Cook's distance, se.fit ----
+  double *dct = nullptr, *hct = nullptr;          // C~ tiles: device / pinned [MAX_P16 (MAX_P16 + 1) / 2][INFL_TILE]
+  double* dinf[3] = {nullptr, nullptr, nullptr};  // hat, resid, cooks of the resident rows, allocated when first asked for
+  int64_t inf_cap[3] = {0, 0, 0};
+  double* dhpart = nullptr;                       // per-workgroup sums of h, then their sum
+  int hpart_cap = 0;
+  hipEvent_t evi0 = nullptr, evi1 = nullptr;
+  double influence_ms = -1.0;                     // kernel time of the last influence call (-1: none yet)
+  void free_influence() {
+    for (double** ptr : {&dct, &dinf[0], &dinf[1], &dinf[2], &dhpart}) {
+      if (*ptr) (void)hipFree(*ptr);
+      *ptr = nullptr;
+    }
+    if (hct) (void)hipHostFree(hct);
+    hct = nullptr;
+    inf_cap[0] = inf_cap[1] = inf_cap[2] = 0;
+    hpart_cap = 0;
+    if (evi0) (void)hipEventDestroy(evi0);
+    if (evi1) (void)hipEventDestroy(evi1);
+    evi0 = evi1 = nullptr;
+  }
+  static int dev_alloc(double** ptr, size_t bytes, const char* what) {
+    const hipError_t e = hipMalloc(ptr, bytes);
+    if (e != hipSuccess) {
+      *ptr = nullptr;
+      (void)hipGetLastError();
+      set_error(hip_msg(e, what));
+      return SGLM_ENOMEM;
+    }
+    return SGLM_OK;
+  }
+  // cov (col-major pp x pp) -> C~ tiles on the device
+  int upload_cov(const double* cov, int64_t pp) {
+    constexpr size_t CT_BYTES = sizeof(double) * (size_t)(MAX_P16 * (MAX_P16 + 1) / 2) * INFL_TILE;
+    if (!dct)
+      if (int rc = dev_alloc(&dct, CT_BYTES, "hipMalloc(covariance tiles)")) return rc;
+    if (!hct) HIPCHK(hipHostMalloc(&hct, CT_BYTES, hipHostMallocDefault));
+    const int64_t P = (pp + 15) / 16;
+    influence_tiles(cov, (int)pp, hct);
+    HIPCHK(hipMemcpyAsync(dct, hct, sizeof(double) * (size_t)(P * (P + 1) / 2) * INFL_TILE, hipMemcpyHostToDevice, st));
+    return SGLM_OK;
+  }
+  // hat / resid / cooks / sum of h of this shard's rows at beta against cov (the global C); any output null
+  int influence_local(const double* beta, const double* cov, int family, int link, int rtype, double disp, double* hat,
+                      double* resid, double* cooks, double* sum_hat) {
+    HIPCHK(hipSetDevice(device));
+    if (int rc = check_loaded()) return rc;
+    double* outs[3] = {hat, resid, cooks};
+    for (int k = 0; k < 3; ++k)
+      if (outs[k] && inf_cap[k] < n_pad) {
+        if (dinf[k]) HIPCHK(hipFree(dinf[k]));
+        dinf[k] = nullptr;
+        inf_cap[k] = 0;
+        if (int rc = dev_alloc(&dinf[k], sizeof(double) * (size_t)n_pad, "hipMalloc(diagnostics vector)")) return rc;
+        inf_cap[k] = n_pad;
+      }
+    const int P = (int)((p + 15) / 16);
+    const int g = influence_grid(P, ncu, n);
+    if (hpart_cap < g + 1) {
+      if (dhpart) HIPCHK(hipFree(dhpart));
+      dhpart = nullptr;
+      hpart_cap = 0;
+      if (int rc = dev_alloc(&dhpart, sizeof(double) * (size_t)(g + 1), "hipMalloc(leverage partials)")) return rc;
+      hpart_cap = g + 1;
+    }
+    if (!evi0) HIPCHK(hipEventCreate(&evi0));
+    if (!evi1) HIPCHK(hipEventCreate(&evi1));
+    InflArgs a{};
+    a.need_q = (hat || cooks || sum_hat) ? 1 : 0;
+    if (a.need_q)
+      if (int rc = upload_cov(cov, p)) return rc;
+    std::memcpy(hbeta, beta, sizeof(double) * p);
+    HIPCHK(hipMemcpyAsync(dbeta, hbeta, sizeof(double) * p, hipMemcpyHostToDevice, st));
+    a.X = dX;
+    a.ld = n_pad;
+    a.p = (int)p;
+    a.n = n;
+    a.ct = dct;
+    a.beta = dbeta;
+    a.y = dy;
+    a.m = dm;
+    a.off = doff;
+    a.prior = dprior;
+    a.family = family;
+    a.link = link;
+    a.resid_type = rtype;
+    a.dispersion = disp;
+    a.hat = hat ? dinf[0] : nullptr;
+    a.resid = resid ? dinf[1] : nullptr;
+    a.cooks = cooks ? dinf[2] : nullptr;
+    a.hpart = sum_hat ? dhpart : nullptr;
+    HIPCHK(launch_influence(P, a, g, st, evi0, evi1));
+    if (sum_hat) {
+      HIPCHK(launch_influence_sum(dhpart, g, dhpart + g, st));
+      HIPCHK(hipMemcpyAsync(sum_hat, dhpart + g, sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    for (int k = 0; k < 3; ++k)
+      if (outs[k] && n > 0) HIPCHK(hipMemcpyAsync(outs[k], dinf[k], sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, evi0, evi1));
+    influence_ms = ms;
+    return SGLM_OK;
+  }
+  // out[i] = sqrt(max(0, disp * x_i' cov x_i)) of NEW rows, streamed through predict_new's scratch
+  int predict_new_se(const double* X, int64_t nn, int64_t pp, int64_t ldx, const double* cov, double disp, double* out) {
+    HIPCHK(hipSetDevice(device));
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nn, ((int64_t)1 << 27) / std::max<int64_t>(pp, 1)));
+    if (pp * chunk > xs_cap) {
+      if (dxs) HIPCHK(hipFree(dxs));
+      dxs = nullptr;
+      xs_cap = 0;
+      if (int rc = dev_alloc(&dxs, sizeof(double) * (size_t)(pp * chunk), "hipMalloc(new rows)")) return rc;
+      xs_cap = pp * chunk;
+    }
+    if (chunk > vs_cap) {
+      vs_cap = 0;
+      for (double** q : {&dvs, &dms, &dos}) {
+        if (*q) HIPCHK(hipFree(*q));
+        *q = nullptr;
+        if (int rc = dev_alloc(q, sizeof(double) * (size_t)chunk, "hipMalloc(new rows)")) return rc;
+      }
+      vs_cap = chunk;
+    }
+    if (int rc = upload_cov(cov, pp)) return rc;
+    const int P = (int)((pp + 15) / 16);
+    for (int64_t r0 = 0; r0 < nn; r0 += chunk) {
+      const int64_t nr = std::min(chunk, nn - r0);
+      if (int rc = h2d_block(dxs, nr, X + r0, ldx, nr, pp)) return rc;
+      InflArgs a{};
+      a.X = dxs;
+      a.ld = nr;
+      a.p = (int)pp;
+      a.n = nr;
+      a.ct = dct;
+      a.need_q = 1;
+      a.dispersion = disp;
+      a.out = dvs;
+      HIPCHK(launch_qform(P, a, influence_grid(P, ncu, nr), st));
+      HIPCHK(hipMemcpyAsync(out + r0, dvs, sizeof(double) * nr, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
     return SGLM_OK;
   }
 
@@ -2496,6 +2642,111 @@ int sglm_predict_new(sglm_engine* h, const double* X, int64_t n, int64_t p, int6
   if (n == 0) return SGLM_OK;
   sglm_engine* e = h->group() ? h->subs[0] : h;  // new rows are scored on the first device
   return e->predict_new(X, n, p, ldx, beta, offset, m, family, link, type, out);
+}
+
+// inv(X'WX) at beta: the pass of sglm_irls_pass (collective over a communicator) and the engine's
+// solve rule (Cholesky, or the LU inverse below LU_SWITCH_RATIO; SGLM_ESINGULAR as the fit).
+static int vcov_impl(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, double* cov) {
+  const int64_t p = h->ncols();
+  std::vector<double> packed((size_t)packed_len(p)), x((size_t)p);
+  int rc = h->pass(MODE_IRLS, beta, 0.0, 0.0, opts->family, opts->link, packed.data());
+  if (rc) return rc;
+  std::unique_ptr<SolverIface> solver = h->make_solver(p);
+  const double t0 = now_ms();
+  const int srv = solver->solve(packed.data(), x.data());
+  if (srv) {
+    if (srv == SGLM_ESINGULAR) set_error("breeze.linalg.MatrixSingularException: X'WX is singular");
+    return srv;
+  }
+  rc = solver->inverse(cov);
+  h->solve_ms += now_ms() - t0;
+  h->solve_path = solver->path();
+  return rc;
+}
+
+int sglm_vcov(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, double* cov) {
+  if (int rc = check_handle(h)) return rc;
+  if (!opts || !beta || !cov || !family_link_valid(opts->family, opts->link)) {
+    set_error("requirement failed: opts with a supported family/link, beta, cov");
+    return SGLM_EINVAL;
+  }
+  if (int rc = check_ready(h)) return rc;
+  return vcov_impl(h, opts, beta, cov);
+}
+
+static int influence_shards(sglm_engine* h, const double* beta, const double* cov, const sglm_glm_opts* opts, int rtype,
+                            double disp, double* hat, double* resid, double* cooks, double* sum_hat) {
+  if (h->group()) {  // shard order: the outputs concatenated in row order, sum h summed in shard order
+    double total = 0.0;
+    for (size_t d = 0; d < h->subs.size(); ++d) {
+      const int64_t lo = h->sub_lo[d];
+      double part = 0.0;
+      if (int rc = influence_shards(h->subs[d], beta, cov, opts, rtype, disp, hat ? hat + lo : nullptr,
+                                    resid ? resid + lo : nullptr, cooks ? cooks + lo : nullptr,
+                                    sum_hat ? &part : nullptr))
+        return rc;
+      total += part;
+      h->influence_ms = d == 0 ? h->subs[d]->influence_ms : std::max(h->influence_ms, h->subs[d]->influence_ms);
+    }
+    if (sum_hat) *sum_hat = total;
+    return SGLM_OK;
+  }
+  return h->influence_local(beta, cov, opts->family, opts->link, rtype, disp, hat, resid, cooks, sum_hat);
+}
+
+int sglm_influence(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, int resid_type, double dispersion,
+                   double* hat, double* resid, double* cooks, double* sum_hat) {
+  if (!opts || !beta || !family_link_valid(opts->family, opts->link) || resid_type < SGLM_RESID_RESPONSE ||
+      resid_type > SGLM_RESID_DEVIANCE) {
+    set_error("requirement failed: opts with a supported family/link, beta, a residual type of enum sglm_resid_type");
+    return SGLM_EINVAL;
+  }
+  if (!(dispersion > 0.0)) {
+    set_error("requirement failed: dispersion > 0");
+    return SGLM_EINVAL;
+  }
+  if (int rc = check_handle(h)) return rc;
+  if (int rc = check_ready(h)) return rc;
+  // the row kernel covers resident designs on the fused / narrow paths' range only: refused before any launch
+  auto out_of_scope = [](const sglm_engine* e) { return e->procx.on || e->wide; };
+  bool refuse = !h->group() && out_of_scope(h);
+  for (const sglm_engine* s : h->subs) refuse = refuse || out_of_scope(s);
+  if (refuse) {
+    set_error("requirement failed: per-row diagnostics need a resident design with p <= " +
+              std::to_string(16 * MAX_P16) + " columns on the fused / narrow path (procedural shards, wider "
+              "designs and SGLM_FORCE_WIDE are not supported)");
+    return SGLM_EINVAL;
+  }
+  const int64_t p = h->ncols();
+  std::vector<double> cov((size_t)(p * p));
+  if (int rc = vcov_impl(h, opts, beta, cov.data())) return rc;
+  return influence_shards(h, beta, cov.data(), opts, resid_type, dispersion, hat, resid, cooks, sum_hat);
+}
+
+int sglm_predict_new_se(sglm_engine* h, const double* X, int64_t n, int64_t p, int64_t ldx, const double* cov,
+                        double dispersion, double* out) {
+  if (int rc = check_handle(h)) return rc;
+  if (!X || !cov || !out || n < 0 || p <= 0 || ldx < n || !(dispersion > 0.0)) {
+    set_error("requirement failed: X, cov, out, n >= 0, p >= 1, ldx >= n, dispersion > 0");
+    return SGLM_EINVAL;
+  }
+  if (p > 16 * MAX_P16) {
+    set_error("requirement failed: se.fit of new rows needs p <= " + std::to_string(16 * MAX_P16) + " columns");
+    return SGLM_EINVAL;
+  }
+  if (n == 0) return SGLM_OK;
+  sglm_engine* e = h->group() ? h->subs[0] : h;  // new rows are scored on the first device
+  return e->predict_new_se(X, n, p, ldx, cov, dispersion, out);
+}
+
+int sglm_get_influence_ms(sglm_engine* h, double* kernel_ms) {
+  if (int rc = check_handle(h)) return rc;
+  if (!kernel_ms) {
+    set_error("requirement failed: kernel_ms");
+    return SGLM_EINVAL;
+  }
+  *kernel_ms = h->influence_ms;
+  return SGLM_OK;
 }
 
 int sglm_pass_kernel_for(int64_t n, int64_t p, int fused_split, int flags, int family, int link, char* name,

@@ -1,0 +1,293 @@
+// influence.hip -- per-row diagnostics of a resident design with p <= 256 (gfx950).
+//
+//   q_i = x_i' C x_i,  C = inv(X'WX)      the row quadratic form (leverage h = w q, se.fit = sqrt(phi q))
+//
+// The Gram kernels' MFMA with the roles transposed: k runs over COLUMNS, one operand is X, the
+// other a 16 x 16 block of C.  C is symmetric, so only the block triangle c <= b is multiplied,
+// with the off-diagonal blocks doubled on the host (C~, influence_tiles):
+//   q_i = sum_b sum_{c <= b} x_ic' C~_cb x_ib
+// -- P16 (P16 + 1) / 2 tiles, as many fp64 MFMA flops per row as the Gram pass.
+//
+// One wave owns 16 rows (RS row blocks of 16 each).  Per column block c and k-step s it holds
+//   xv[c][s] = X[row l % 16, column 16 c + 4 s + l / 16]
+// which is the B operand of v_mfma_f64_16x16x4_f64 (B[k = l / 16][n = l % 16]) of the transposed
+// product T_b' = sum_{c <= b} C~_cb' X_c' (A = C~_cb', 16 x 4 per step: lane l holds
+// C~[16 c + 4 s + l / 16][16 b + l % 16]).  Its result D[m][n] = T[row n][column 16 b + m] comes
+// out with lane l, register v holding m = l / 16 + 4 v, n = l % 16 -- the column 16 b + 4 v + l / 16
+// of row l % 16, exactly the element xv[b][v] the same lane already holds.  So the design is read
+// from HBM once, straight into registers (16 lanes x 8 B = 128 B contiguous per column), serves as
+// MFMA operand, as the factor of the row reduction rowsum(T_b o X_b) and as the eta = x'beta
+// operand, and the reduction needs no data movement beyond one sum over the four lane groups.
+//
+// C~ reaches the waves through LDS: for block column b the workgroup copies the b + 1 tiles (c, b)
+// (contiguous in the host's tile order, <= 32 KB) from global memory -- C~ is <= 272 KB and stays in
+// L2 -- prefetched into registers one block column ahead, so the L2 latency hides behind the MFMAs.
+// A workgroup step covers 64 * RS rows; C~ is re-read from L2 once per step.
+#include <hip/hip_ext.h>
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "common.hpp"
+#include "kernels.hpp"
+#include "rowmath.hpp"
+
+namespace sglm {
+
+namespace {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+constexpr int INFL_NW = 4;            // waves per workgroup
+constexpr int INFL_NT = 64 * INFL_NW;
+// row blocks of 16 per wave: two while the kernel stays within 256 VGPRs without scratch (P16 <= 7;
+// two workgroups per CU, and no AGPRs: the fp64 MFMA's AGPR form runs at 60 %)
+constexpr int infl_rs(int P16) { return P16 <= 7 ? 2 : 1; }
+constexpr int infl_wg_per_cu(int P16) { return P16 <= 4 ? 4 : 2; }
+
+__device__ __forceinline__ double group_sum(double v) {  // over the four lane groups l / 16
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  return v;
+}
+
+template <int P16, bool ROWS>
+__device__ __forceinline__ void influence_body(const InflArgs& a) {
+  constexpr int RS = infl_rs(P16);
+  constexpr int STEP = 16 * RS * INFL_NW;                      // rows per workgroup step
+  constexpr int PF = (P16 * INFL_TILE + INFL_NT - 1) / INFL_NT;  // prefetch registers per thread
+  __shared__ double panel[P16 * INFL_TILE];
+  __shared__ double sbeta[16 * P16];
+  __shared__ double swave[INFL_NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = lane & 15, g = lane >> 4;
+  if (ROWS) {
+    for (int c = tid; c < 16 * P16; c += INFL_NT) sbeta[c] = c < a.p ? a.beta[c] : 0.0;
+    __syncthreads();
+  }
+  const bool need_q = a.need_q != 0;
+  double pf[PF];
+#pragma unroll
+  for (int k = 0; k < PF; ++k) pf[k] = 0.0;
+  if (need_q) pf[0] = a.ct[tid];  // block column 0: one tile
+  double hsum = 0.0;
+  const int64_t nsteps = (a.n + STEP - 1) / STEP;
+  for (int64_t step = blockIdx.x; step < nsteps; step += gridDim.x) {
+    double xv[RS][P16][4];
+    int64_t row[RS];
+#pragma unroll
+    for (int r = 0; r < RS; ++r) {
+      row[r] = step * STEP + (int64_t)((wave * RS + r) * 16 + i);
+      // Unconditional loads from clamped addresses: a row >= n reads row n - 1 (its results are never
+      // stored; an MFMA column and a lane's sums belong to one row, so nothing crosses rows), a column
+      // >= p reads column p - 1 -- only the last column block can hold one (p > 16 (P16 - 1)) -- and
+      // meets the zeros of C~ and beta there.  Masked loads would keep 4 P16 masks live.
+      const int64_t rr = row[r] < a.n ? row[r] : a.n - 1;
+      // the blocks before the last: one running pointer (column 4 u + g, u = 4 c + s), one 64-bit add per load
+      const int64_t ld = a.ld;
+      const double* xp = a.X + rr + (int64_t)g * ld;
+      const int64_t ld4 = 4 * ld;
+#pragma unroll
+      for (int c = 0; c < P16 - 1; ++c)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          xv[r][c][s] = *xp;
+          xp += ld4;
+        }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int col = min(16 * (P16 - 1) + 4 * s + g, a.p - 1);
+        xv[r][P16 - 1][s] = a.X[rr + (int64_t)col * ld];
+      }
+    }
+    double eta[RS], q[RS];
+#pragma unroll
+    for (int r = 0; r < RS; ++r) eta[r] = q[r] = 0.0;
+    if (ROWS) {
+      // (the index is made opaque per step: beta is loop-invariant, and hoisted out of the step loop
+      // its 4 P16 values per lane would hold 8 P16 VGPRs next to the design's)
+      int gb = g;
+      asm volatile("" : "+v"(gb));
+#pragma unroll
+      for (int c = 0; c < P16; ++c)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const double bv = sbeta[16 * c + 4 * s + gb];
+#pragma unroll
+          for (int r = 0; r < RS; ++r) eta[r] = fma(xv[r][c][s], bv, eta[r]);
+        }
+#pragma unroll
+      for (int r = 0; r < RS; ++r) eta[r] = group_sum(eta[r]);
+    }
+    if (need_q) {
+#pragma unroll
+      for (int b = 0; b < P16; ++b) {
+        __syncthreads();  // the previous block column's tiles are consumed
+#pragma unroll
+        for (int k = 0; k < PF; ++k)
+          if (k * INFL_NT < (b + 1) * INFL_TILE) panel[k * INFL_NT + tid] = pf[k];
+        __syncthreads();
+        {  // the next block column (the first one of the next step after the last)
+          const int nb = (b + 1 < P16) ? b + 1 : 0;
+          // (the scalar base is made opaque: the tiles' offsets exceed the loads' immediate field, and
+          // the compiler otherwise keeps one precomputed 64-bit address per tile live -- T pairs)
+          const double* src = a.ct + (int64_t)(nb * (nb + 1) / 2) * INFL_TILE;
+          asm volatile("" : "+s"(src));
+#pragma unroll
+          for (int k = 0; k < PF; ++k)
+            if (k * INFL_NT < (nb + 1) * INFL_TILE) pf[k] = src[k * INFL_NT + tid];
+        }
+        d4 acc[RS][2];
+#pragma unroll
+        for (int r = 0; r < RS; ++r) acc[r][0] = acc[r][1] = d4{0.0, 0.0, 0.0, 0.0};
+        // tile c + 1's operands are read from LDS before tile c's MFMAs issue; the scheduling barrier
+        // keeps the compiler from hoisting the whole block column's reads (8 (b + 1) VGPRs) instead
+        double av[2][4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) av[0][s] = panel[s * 64 + lane];
+#pragma unroll
+        for (int c = 0; c <= b; ++c) {
+          if (c < b) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) av[(c + 1) & 1][s] = panel[(c + 1) * INFL_TILE + s * 64 + lane];
+          }
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int r = 0; r < RS; ++r)
+              acc[r][s & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[c & 1][s], xv[r][c][s], acc[r][s & 1], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int r = 0; r < RS; ++r)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) q[r] = fma(acc[r][0][v] + acc[r][1][v], xv[r][b][v], q[r]);
+      }
+#pragma unroll
+      for (int r = 0; r < RS; ++r) q[r] = group_sum(q[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < RS; ++r) {
+      if (g != 0 || row[r] >= a.n) continue;  // 16 lanes store 16 consecutive rows
+      const int64_t ri = row[r];
+      if (!ROWS) {
+        a.out[ri] = sqrt(fmax(0.0, a.dispersion * q[r]));
+        continue;
+      }
+      const double e = eta[r] + (a.off ? a.off[ri] : 0.0);
+      const InflRow w = influence_row(a.family, a.link, a.resid_type, e, a.y[ri], a.m ? a.m[ri] : 1.0,
+                                      a.prior ? a.prior[ri] : 1.0);
+      const double h = w.w * q[r];
+      if (a.resid) a.resid[ri] = w.resid;
+      if (a.hat) a.hat[ri] = h;
+      if (a.cooks) {
+        const double t = w.rp / (1.0 - h);
+        a.cooks[ri] = (t * t) * h / (a.dispersion * (double)a.p);
+      }
+      hsum += h;
+    }
+  }
+  if (ROWS && a.hpart) {  // lanes, then waves, in a fixed order
+    hsum += __shfl_xor(hsum, 1);
+    hsum += __shfl_xor(hsum, 2);
+    hsum += __shfl_xor(hsum, 4);
+    hsum += __shfl_xor(hsum, 8);
+    if (lane == 0) swave[wave] = hsum;
+    __syncthreads();
+    if (tid == 0) {
+      double s = swave[0];
+      for (int k = 1; k < INFL_NW; ++k) s += swave[k];
+      a.hpart[blockIdx.x] = s;
+    }
+  }
+}
+
+template <int P16>
+__global__ void __launch_bounds__(INFL_NT, 2) influence_kernel(InflArgs a) {
+  influence_body<P16, true>(a);
+}
+template <int P16>
+__global__ void __launch_bounds__(INFL_NT, 2) qform_kernel(InflArgs a) {
+  influence_body<P16, false>(a);
+}
+
+__global__ void __launch_bounds__(256) influence_sum_kernel(const double* __restrict__ part, int nparts,
+                                                            double* __restrict__ out) {
+  __shared__ double ss[256];
+  double s = 0.0;
+  for (int k = threadIdx.x; k < nparts; k += 256) s += part[k];
+  ss[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = ss[0];
+    for (int k = 1; k < 256; ++k) t += ss[k];
+    out[0] = t;
+  }
+}
+
+int steps_of(int P16, int64_t n) {
+  const int64_t step = 16 * infl_rs(P16) * INFL_NW;
+  return (int)std::min<int64_t>((n + step - 1) / step, (int64_t)1 << 30);
+}
+
+}  // namespace
+
+#define INFL_CASES(K)                                                                                      \
+  switch (P16) {                                                                                           \
+    K(1) K(2) K(3) K(4) K(5) K(6) K(7) K(8) K(9) K(10) K(11) K(12) K(13) K(14) K(15) K(16)                 \
+    default: return hipErrorInvalidValue;                                                                  \
+  }
+
+// workgroups of influence_kernel<P16> one CU holds (registers and LDS: the runtime's own count)
+static hipError_t resident_wgs(int P16, int* out) {
+#define K(N) \
+  case N: return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, influence_kernel<N>, INFL_NT, 0);
+  INFL_CASES(K)
+#undef K
+}
+
+// One workgroup per resident slot (capped at infl_wg_per_cu): the grid -- and with it the order of the
+// sum of h -- depends on the shape and the device only.
+int influence_grid(int P16, int ncu, int64_t n) {
+  int wgs = 1;
+  if (resident_wgs(P16, &wgs) != hipSuccess || wgs < 1) wgs = 1;
+  wgs = std::min(wgs, infl_wg_per_cu(P16));
+  return std::max(1, std::min(steps_of(P16, n), ncu * wgs));
+}
+
+void influence_tiles(const double* C, int p, double* out) {
+  const int P16 = (p + 15) / 16;
+  for (int b = 0; b < P16; ++b)
+    for (int c = 0; c <= b; ++c) {
+      double* t = out + (int64_t)(b * (b + 1) / 2 + c) * INFL_TILE;
+      const double f = c == b ? 1.0 : 2.0;
+      for (int s = 0; s < 4; ++s)
+        for (int l = 0; l < 64; ++l) {
+          const int r = 16 * c + 4 * s + (l >> 4), cc = 16 * b + (l & 15);
+          t[s * 64 + l] = (r < p && cc < p) ? f * C[r + (int64_t)cc * p] : 0.0;
+        }
+    }
+}
+
+hipError_t launch_influence(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+#define K(N) \
+  case N: hipExtLaunchKernelGGL(influence_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
+  INFL_CASES(K)
+#undef K
+  return hipGetLastError();
+}
+
+hipError_t launch_qform(int P16, const InflArgs& a, int grid, hipStream_t st) {
+#define K(N) \
+  case N: hipLaunchKernelGGL(qform_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, a); break;
+  INFL_CASES(K)
+#undef K
+  return hipGetLastError();
+}
+
+hipError_t launch_influence_sum(const double* part, int nparts, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(influence_sum_kernel, dim3(1), dim3(256), 0, st, part, nparts, out);
+  return hipGetLastError();
+}
+
+}  // namespace sglm

@@ -56,6 +56,16 @@ int narrow_rows_per_wg(int P16); // rows one workgroup streams per block step (w
 hipError_t launch_narrow(int P16, const PassArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
                          hipEvent_t e1 = nullptr);
 
+// per-row diagnostics (influence.hip): p <= 256
+int influence_grid(int P16, int ncu, int64_t n);  // workgroups (each owns the steps g, g + grid, ...: a fixed order)
+// C (col-major p x p, symmetric) -> C~ in the kernels' operand order: the block triangle c <= b of
+// 16 x 16 tiles (tile b (b + 1) / 2 + c), off-diagonal tiles doubled, zero past p; out [T][INFL_TILE]
+void influence_tiles(const double* C, int p, double* out);
+hipError_t launch_influence(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
+                            hipEvent_t e1 = nullptr);
+hipError_t launch_qform(int P16, const InflArgs& a, int grid, hipStream_t st);
+hipError_t launch_influence_sum(const double* part, int nparts, double* out, hipStream_t st);  // fixed order
+
 // wide path (wide.hip)
 int wide_panels(int p);
 int64_t wide_stride();

@@ -585,6 +585,38 @@ __device__ __forceinline__ bool poisson_init_row(const double* c, const double* 
   return true;
 }
 
+// Per-row diagnostics at eta (influence.hip): the pass's working weight w = pw / (V g'^2)
+// (pass_row_ref's expression, 0 where pw = 0), the Pearson residual (y - mu) sqrt(pw / V) that Cook's
+// distance needs, and the residual of the requested type on the engine's count scale
+// (mu = unlink(eta, m)): response y - mu, working (y - mu) g'(mu), Pearson, or deviance
+// sign(y - mu) sqrt(factor * unit_dev) with the family factor the host applies to the deviance sum
+// (driver.cpp family_dev_factor).  Reference-order functions only; out of line like pass_row_ref.
+enum ResidType : int { RESID_RESPONSE = 0, RESID_WORKING = 1, RESID_PEARSON = 2, RESID_DEVIANCE = 3 };
+struct InflRow {
+  double w, rp, resid;
+};
+__device__ __noinline__ InflRow influence_row(int fam, int lnk, int rtype, double eta, double y, double m, double pw) {
+  const double mu = unlink_fn(fam, lnk, eta, m);
+  const double g = lprime_fn(fam, lnk, mu, m);
+  const double v = variance_fn(fam, mu, m);
+  const double e = y + (-1.0 * mu);
+  InflRow r;
+  r.w = pw * (1.0 / (v * (g * g)));
+  r.rp = e * sqrt(pw / v);
+  if (rtype == RESID_RESPONSE) {
+    r.resid = e;
+  } else if (rtype == RESID_WORKING) {
+    r.resid = e * g;
+  } else if (rtype == RESID_PEARSON) {
+    r.resid = r.rp;
+  } else {
+    const double d = (fam == FAM_GAUSSIAN ? 1.0 : 2.0) * unit_dev(fam, y, mu, m, pw);
+    const double s = sqrt(fmax(d, 0.0));
+    r.resid = e > 0.0 ? s : (e < 0.0 ? -s : 0.0);
+  }
+  return r;
+}
+
 // Dispatch of the in-pass statistics rows: three family-specific accumulators (s2, s3, s4) that
 // the kernel stores into the slots stats_slots() names.
 template <int FAM>

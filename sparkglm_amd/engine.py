@@ -42,6 +42,15 @@ class FitLM:
     npart: int
 
 
+@dataclass
+class Influence:
+    """Per-row diagnostics (R's hatvalues / residuals / cooks.distance) and sum(hat)."""
+    hat: np.ndarray
+    resid: np.ndarray
+    cooks: np.ndarray
+    sum_hat: float
+
+
 def _vec(a, n):
     if a is None:
         return None
@@ -294,6 +303,69 @@ class Engine:
         L.check(self._lib.sglm_predict_new(self._h, L.ptr(X), n, p, max(n, 1), L.ptr(b), L.ptr(offset), L.ptr(m),
                                            o.family, o.link, _ptype(type), L.ptr(out)), "sglm_predict_new")
         return out
+
+    # ---- per-row diagnostics ----
+    def vcov(self, beta, family="binomial", link="logit"):
+        """Unscaled covariance inv(X'WX) at beta (p x p): one pass and the fit's solve rule."""
+        o = glm_opts(family, link)
+        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+        if b.shape[0] != self.p:
+            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
+                                             f"beta {b.shape[0]} rows")
+        cov = np.zeros((self.p, self.p), order="F")
+        L.check(self._lib.sglm_vcov(self._h, C.byref(o), L.ptr(b), cov.ctypes.data_as(L.dp)), "sglm_vcov")
+        return cov
+
+    def influence(self, beta, family="binomial", link="logit", resid="deviance", dispersion=1.0) -> Influence:
+        """Leverage, residuals of type `resid` ("deviance" | "pearson" | "working" | "response", on the
+        count scale: divide binomial residuals by m for R's proportions), Cook's distance and sum(hat)
+        of the resident rows at beta."""
+        if resid not in L.RESID_TYPES:
+            raise L.IllegalArgumentException(f"requirement failed: resid must be one of {sorted(L.RESID_TYPES)}, "
+                                             f"got {resid!r}")
+        o = glm_opts(family, link)
+        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+        if b.shape[0] != self.p:
+            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
+                                             f"beta {b.shape[0]} rows")
+        hat, res, cooks = np.empty(self.n), np.empty(self.n), np.empty(self.n)
+        sh = C.c_double()
+        L.check(self._lib.sglm_influence(self._h, C.byref(o), L.ptr(b), L.RESID_TYPES[resid], float(dispersion),
+                                         L.ptr(hat), L.ptr(res), L.ptr(cooks), C.byref(sh)), "sglm_influence")
+        return Influence(hat, res, cooks, sh.value)
+
+    def residuals(self, beta, family="binomial", link="logit", resid="deviance"):
+        """Residuals only (no covariance product in the kernel)."""
+        if resid not in L.RESID_TYPES:
+            raise L.IllegalArgumentException(f"requirement failed: resid must be one of {sorted(L.RESID_TYPES)}, "
+                                             f"got {resid!r}")
+        o = glm_opts(family, link)
+        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+        res = np.empty(self.n)
+        L.check(self._lib.sglm_influence(self._h, C.byref(o), L.ptr(b), L.RESID_TYPES[resid], 1.0, None, L.ptr(res),
+                                         None, None), "sglm_influence")
+        return res
+
+    def predict_new_se(self, X, cov, dispersion=1.0):
+        """se.fit on the link scale of new rows: sqrt(dispersion * x' cov x), cov from vcov() / xtxi."""
+        X = np.asfortranarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise L.IllegalArgumentException("requirement failed: X must be a matrix")
+        n, p = X.shape
+        cov = np.asfortranarray(cov, dtype=np.float64)
+        if cov.shape != (p, p):
+            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {p} columns, "
+                                             f"cov is {cov.shape}")
+        out = np.empty(n)
+        L.check(self._lib.sglm_predict_new_se(self._h, L.ptr(X), n, p, max(n, 1), cov.ctypes.data_as(L.dp),
+                                              float(dispersion), L.ptr(out)), "sglm_predict_new_se")
+        return out
+
+    def influence_ms(self) -> float:
+        """Kernel time of the last influence() call (HIP events)."""
+        ms = C.c_double()
+        L.check(self._lib.sglm_get_influence_ms(self._h, C.byref(ms)), "sglm_get_influence_ms")
+        return ms.value
 
     def stats(self) -> dict:
         s = L.Stats()

@@ -85,20 +85,57 @@ class GLMModel:
     npart: int
 
     def predict(self, newData: Frame, type: str = "response", offset: Optional[Frame] = None,
-                m: Optional[Frame] = None, device: int = 0) -> Frame:
+                m: Optional[Frame] = None, device: int = 0, cov=None, dispersion: Optional[float] = None) -> Frame:
         """Extension (the reference has no GLM predict): (index, value) rows of the
         linear predictor newX * coefs (+ offset) on the "link" scale, or of mu = unlink(eta, m)
         on the "response" scale (m = binomial trials, default 1) -- R's predict.glm(type=).
         Runs on the GPU through sglm_predict_new; newData's columns are taken by the model's
-        names."""
+        names.
+
+        With `cov` (the unscaled covariance of GLM.vcov) the frame gains an `se` column, R's
+        se.fit: sqrt(dispersion * x' cov x) on the link scale (sglm_predict_new_se), times
+        |dmu/deta| on the response scale (the delta method).  `dispersion` defaults to R's rule
+        (_dispersion).  Without `cov` the result is unchanged."""
         _require(len(set(self.xnames) - set(newData.columns)) == 0,
                  "Not all predictors in the estimation data are in the data to be predicted")
         fam, lnk = _engine_family_link(self.family, self.link)
         newX = newData.select(*self.xnames).to_matrix()
-        vals = _engine(device).predict_new(newX, np.asarray(self.coefs, dtype=np.float64).reshape(-1), fam, lnk,
-                                           type, None if offset is None else offset.to_vector(),
-                                           None if m is None else m.to_vector())
-        return Frame({"index": np.arange(len(vals), dtype=np.int64), "value": vals}, newData.npartitions)
+        beta = np.asarray(self.coefs, dtype=np.float64).reshape(-1)
+        off = None if offset is None else offset.to_vector()
+        mv = None if m is None else m.to_vector()
+        vals = _engine(device).predict_new(newX, beta, fam, lnk, type, off, mv)
+        cols = {"index": np.arange(len(vals), dtype=np.int64), "value": vals}
+        if cov is not None:
+            phi = _dispersion(self) if dispersion is None else float(dispersion)
+            se = _engine(device).predict_new_se(newX, cov, phi)
+            if type == "response":
+                eta = vals if lnk == "identity" else _engine(device).predict_new(newX, beta, fam, lnk, "link", off, mv)
+                se = se * np.abs(_dmu_deta(lnk, eta, 1.0 if mv is None else mv))
+            cols["se"] = se
+        return Frame(cols, newData.npartitions)
+
+
+def _dispersion(obj) -> float:
+    """R's summary.glm rule: 1 for binomial and poisson, the Pearson estimate for gaussian and gamma."""
+    fam, _ = _engine_family_link(obj.family, obj.link)
+    return 1.0 if fam in ("binomial", "poisson") else float(obj.pDispersion)
+
+
+def _dmu_deta(link: str, eta, m=1.0):
+    """d mu / d eta of mu = unlink(eta, m) for the six links (the delta method of se.fit)."""
+    eta = np.asarray(eta, dtype=np.float64)
+    if link == "logit":
+        e = np.exp(-np.abs(eta))
+        return m * e / (1.0 + e) ** 2
+    if link == "probit":
+        return m * np.exp(-0.5 * eta * eta) / np.sqrt(2.0 * np.pi)
+    if link == "cloglog":
+        return m * np.exp(eta - np.exp(eta))
+    if link == "identity":
+        return np.ones_like(eta)
+    if link == "log":
+        return np.exp(eta)
+    return -1.0 / (eta * eta)  # inverse
 
 
 def _engine_family_link(family: str, link: str):
@@ -225,6 +262,36 @@ class GLM:
         finally:
             strict = saved
         return GLM.createObj(x, y, pre, family, link)
+
+    @staticmethod
+    def _load(obj: GLMModel, y: Frame, x: Frame, offset, m, prior, device):
+        _check_inputs(y, x)
+        fam, lnk = _engine_family_link(obj.family, obj.link)
+        eng = _engine(device)
+        eng.set_data(x.select(*obj.xnames).to_matrix(), y.to_vector(), None if m is None else m.to_vector(),
+                     None if offset is None else offset.to_vector(), None if prior is None else prior.to_vector())
+        return eng, fam, lnk, np.asarray(obj.coefs, dtype=np.float64).reshape(-1)
+
+    @staticmethod
+    def vcov(obj: GLMModel, y: Frame, x: Frame, offset: Frame = None, m: Frame = None, prior: Frame = None,
+             device: int = 0) -> np.ndarray:
+        """Extension: the unscaled covariance inv(X'WX) at the fitted coefficients (R's
+        summary(fit)$cov.unscaled); multiply by the dispersion for vcov(fit)."""
+        eng, fam, lnk, beta = GLM._load(obj, y, x, offset, m, prior, device)
+        return eng.vcov(beta, fam, lnk)
+
+    @staticmethod
+    def influence(obj: GLMModel, y: Frame, x: Frame, offset: Frame = None, m: Frame = None, prior: Frame = None,
+                  type: str = "deviance", device: int = 0):
+        """Extension: R's hatvalues / residuals(type=) / cooks.distance of the fitted model on its
+        estimation data, as an engine.Influence.  The dispersion of Cook's distance is 1 for binomial
+        and poisson and obj.pDispersion for gaussian and gamma (R's rule).  Binomial residuals are on
+        the count scale (divide by m for R's proportion scale)."""
+        if type not in L.RESID_TYPES:
+            raise L.IllegalArgumentException(f"requirement failed: type must be one of {sorted(L.RESID_TYPES)}, "
+                                             f"got {type!r}")
+        eng, fam, lnk, beta = GLM._load(obj, y, x, offset, m, prior, device)
+        return eng.influence(beta, fam, lnk, resid=type, dispersion=_dispersion(obj))
 
     @staticmethod
     def summary_string(obj: GLMModel) -> str:

@@ -45,9 +45,11 @@ class LMModel:
         self.nrow = nrow
         self.npart = npart
 
-    def predict(self, newData: Frame, device: int = 0) -> Frame:
+    def predict(self, newData: Frame, device: int = 0, xtxi=None) -> Frame:
         """LM.scala:29-61: (index, value) rows of newX * coefs, on the GPU (sglm_predict_new: the
         new rows stream through a scratch buffer; a design resident on the device stays put).
+        With `xtxi` (inv(X'X), LM.fit_components) the frame gains an `se` column, R's se.fit
+        sigma sqrt(x' inv(X'X) x) (sglm_predict_new_se); without it the result is unchanged.
 
         As the reference, newX is newData's whole matrix in its own column order (LM.scala:40,
         54: dfToDenseMatrix / dataFrameToMatrix of newData), so a frame with extra columns fails
@@ -65,7 +67,10 @@ class LMModel:
         else:
             newX = newData.select(*self.xnames).to_matrix()
         vals = _engine(device).predict_new(newX, np.asarray(self.coefs, dtype=np.float64).reshape(-1))
-        return Frame({"index": np.arange(len(vals), dtype=np.int64), "value": vals}, newData.npartitions)
+        cols = {"index": np.arange(len(vals), dtype=np.int64), "value": vals}
+        if xtxi is not None:
+            cols["se"] = _engine(device).predict_new_se(newX, xtxi, float(self.sigma) ** 2)
+        return Frame(cols, newData.npartitions)
 
     def summary(self) -> "SummaryLM":
         return SummaryLM(self)
@@ -153,6 +158,17 @@ class LM:
         f = eng.fit_lm()
         return LMModel(x.columns, y.columns[0], f.coefs.reshape(-1, 1), list(f.stderr), f.sigma, f.r2, f.fstat,
                        float(y.count()), x.rdd.partitions.size())
+
+    @staticmethod
+    def influence(obj: LMModel, x: Frame, y: Frame, device: int = 0):
+        """Extension: R's hatvalues / residuals / cooks.distance of the fitted model on its estimation
+        data (an engine.Influence): the gaussian / identity diagnostics with w = 1, C = inv(X'X) and
+        dispersion sigma^2; the residuals are y - X coefs."""
+        _require(x.count() == y.count(), "The two DataFrames must have the same number of rows")
+        eng = _engine(device)
+        eng.set_data(x.select(*obj.xnames).to_matrix(), y.to_vector())
+        return eng.influence(np.asarray(obj.coefs, dtype=np.float64).reshape(-1), "gaussian", "identity",
+                             resid="response", dispersion=float(obj.sigma) ** 2)
 
     @staticmethod
     def fit_components(x: Frame, y: Frame, device: int = 0) -> PreLM:
