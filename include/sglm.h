@@ -65,7 +65,8 @@ extern "C" {
                               the group handle at any ndev), SGLM_KERNEL_NARROW_SPLIT retired,
                               sglm_stats.lm_onepass_fits.  Added since, without a version change (new
                               symbols only): sglm_vcov, sglm_influence, sglm_predict_new_se,
-                              sglm_get_influence_ms, enum sglm_resid_type */
+                              sglm_get_influence_ms, enum sglm_resid_type; (new values only:) SGLM_SQRT and
+                              the non-canonical (family, link) pairs of enum sglm_link's table */
 
 enum sglm_status {
   SGLM_OK = 0,
@@ -79,9 +80,20 @@ enum sglm_status {
 /* Families: the reference fits only binomial (GLM.scala:486-590); the rest follow R's
  * family objects on the reference's IRLS skeleton. */
 enum sglm_family { SGLM_BINOMIAL = 0, SGLM_GAUSSIAN = 1, SGLM_POISSON = 2, SGLM_GAMMA = 3 };
+/* The (family, link) pairs, R's three links per family; any other pair is SGLM_EINVAL:
+ *   binomial  logit, probit, cloglog
+ *   gaussian  identity, log, inverse
+ *   poisson   log, identity, sqrt
+ *   gamma     inverse, identity, log
+ * With a non-canonical link of gaussian / poisson / gamma the mean can leave the family's range during
+ * the iterations (R's validmu / valideta: poisson and gamma need mu finite and > 0, sqrt eta > 0; gaussian
+ * eta finite, inverse eta != 0).  There is no step-halving: such a fit returns SGLM_EINVAL ("no valid set
+ * of coefficients: mu left the poisson range at iteration k"), and sglm_irls_pass returns a non-finite
+ * scalars[0]. */
 enum sglm_link {
   SGLM_LOGIT = 0, SGLM_PROBIT = 1, SGLM_CLOGLOG = 2, /* binomial (GLM.scala:190-251) */
-  SGLM_IDENTITY = 3, SGLM_LOG = 4, SGLM_INVERSE = 5   /* gaussian / poisson / gamma */
+  SGLM_IDENTITY = 3, SGLM_LOG = 4, SGLM_INVERSE = 5,  /* gaussian / poisson / gamma */
+  SGLM_SQRT = 6                                       /* poisson */
 };
 
 /* How mu is formed on the first iteration. */
@@ -199,7 +211,9 @@ typedef struct {
   int solve_path;           /* enum sglm_solve_path of the last solve, -1 before any */
   int pass_kernel;          /* enum sglm_pass_kernel of the last pass (the engine's own choice: the K1 / K1r
                                threshold, its row limit, the narrow / wide paths) */
-  char pass_kernel_name[64];/* that kernel's name as rocprofv3 lists it, e.g. "irls_pass_r_kernel<16,binomial,logit>" */
+  char pass_kernel_name[64];/* that kernel's name as rocprofv3 lists it, e.g. "irls_pass_r_kernel<16,binomial,logit>";
+                             the link slot reads "runtime" for the pairs that run their family's run-time-link
+                             instantiation (every non-canonical pair but gamma / log) */
   int64_t lm_device_fits;   /* LM fits done in one device round trip (Gram pass, device Cholesky, residual pass;
                                resident p <= 64 shards without a communicator; SGLM_LM_DEVICE=0 disables) */
   int64_t lm_device_reruns; /* of those, fits whose device coefficients were not the host solve's bit for bit (the

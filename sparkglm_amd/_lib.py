@@ -15,8 +15,11 @@ LIB_PATH = os.environ.get("SGLM_LIB") or os.path.join(HERE, "lib", "libsglm_hip.
 
 SGLM_OK, SGLM_EINVAL, SGLM_ESINGULAR, SGLM_EHIP, SGLM_ECOMM, SGLM_ENOMEM = range(6)
 FAMILIES = {"binomial": 0, "gaussian": 1, "poisson": 2, "gamma": 3}
-LINKS = {"logit": 0, "probit": 1, "cloglog": 2, "identity": 3, "log": 4, "inverse": 5}
+LINKS = {"logit": 0, "probit": 1, "cloglog": 2, "identity": 3, "log": 4, "inverse": 5, "sqrt": 6}
 CANONICAL_LINK = {"gaussian": "identity", "poisson": "log", "gamma": "inverse"}
+# the links of each extension family (R's family objects; include/sglm.h enum sglm_link), canonical first
+FAMILY_LINKS = {"gaussian": ("identity", "log", "inverse"), "poisson": ("log", "identity", "sqrt"),
+                "gamma": ("inverse", "identity", "log")}
 INIT_SINGLE, INIT_MULTIPLE = 0, 1
 NS = 8
 S_DEV, S_PEARSON, S_LL, S_BAD, S_AUX0, S_AUX1, S_AUX2, S_SUMW = range(8)

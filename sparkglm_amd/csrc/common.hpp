@@ -20,7 +20,62 @@ enum PassMode : int {
 };
 
 enum Family : int { FAM_BINOMIAL = 0, FAM_GAUSSIAN = 1, FAM_POISSON = 2, FAM_GAMMA = 3 };
-enum Link : int { LNK_LOGIT = 0, LNK_PROBIT = 1, LNK_CLOGLOG = 2, LNK_IDENTITY = 3, LNK_LOG = 4, LNK_INVERSE = 5 };
+enum Link : int {
+  LNK_LOGIT = 0, LNK_PROBIT = 1, LNK_CLOGLOG = 2, LNK_IDENTITY = 3, LNK_LOG = 4, LNK_INVERSE = 5, LNK_SQRT = 6
+};
+// Link template argument of the per-family instantiations that read the link from their arguments at
+// run time (PassArgs::link ...) and take the out-of-line reference row functions for every row.
+constexpr int LNK_RT = -1;
+
+// The (family, link) pairs of the engine (R's family objects: three links per family).
+constexpr bool family_link_pair(int fam, int lnk) {
+  return (fam == FAM_BINOMIAL && (lnk == LNK_LOGIT || lnk == LNK_PROBIT || lnk == LNK_CLOGLOG)) ||
+         (fam == FAM_GAUSSIAN && (lnk == LNK_IDENTITY || lnk == LNK_LOG || lnk == LNK_INVERSE)) ||
+         (fam == FAM_POISSON && (lnk == LNK_LOG || lnk == LNK_IDENTITY || lnk == LNK_SQRT)) ||
+         (fam == FAM_GAMMA && (lnk == LNK_INVERSE || lnk == LNK_IDENTITY || lnk == LNK_LOG));
+}
+// The non-canonical pairs of the extension families: the only ones whose mu = unlink(eta) can leave the
+// family's range (R's validmu / valideta), which the row functions report as a NaN unit deviance
+// (rowmath.hpp link_row_valid) and the drivers as SGLM_EINVAL.
+constexpr bool noncanonical_pair(int fam, int lnk) {
+  return family_link_pair(fam, lnk) && fam != FAM_BINOMIAL &&
+         !((fam == FAM_GAUSSIAN && lnk == LNK_IDENTITY) || (fam == FAM_POISSON && lnk == LNK_LOG) ||
+           (fam == FAM_GAMMA && lnk == LNK_INVERSE));
+}
+
+// The one dispatch of a run-time (family, link) onto the kernels' compile-time <FAM, LNK> instantiations
+// (every launcher goes through it): a dedicated instantiation for the binomial links, the three canonical
+// pairs and gamma / log; the other pairs run their family's LNK_RT instantiation.  f(Fam, Lnk) receives
+// the pair as std::integral_constant-like tags; false: the pair has no instantiation (the launcher returns
+// hipErrorInvalidValue -- it never runs another link's kernel).
+template <int V>
+struct IntTag {
+  static constexpr int value = V;
+};
+template <class F>
+inline bool dispatch_family_link(int fam, int lnk, F&& f) {
+  if (!family_link_pair(fam, lnk)) return false;
+  if (fam == FAM_BINOMIAL) {
+    if (lnk == LNK_LOGIT) f(IntTag<FAM_BINOMIAL>{}, IntTag<LNK_LOGIT>{});
+    else if (lnk == LNK_PROBIT) f(IntTag<FAM_BINOMIAL>{}, IntTag<LNK_PROBIT>{});
+    else f(IntTag<FAM_BINOMIAL>{}, IntTag<LNK_CLOGLOG>{});
+  } else if (fam == FAM_GAUSSIAN) {
+    if (lnk == LNK_IDENTITY) f(IntTag<FAM_GAUSSIAN>{}, IntTag<LNK_IDENTITY>{});
+    else f(IntTag<FAM_GAUSSIAN>{}, IntTag<LNK_RT>{});
+  } else if (fam == FAM_POISSON) {
+    if (lnk == LNK_LOG) f(IntTag<FAM_POISSON>{}, IntTag<LNK_LOG>{});
+    else f(IntTag<FAM_POISSON>{}, IntTag<LNK_RT>{});
+  } else {
+    if (lnk == LNK_INVERSE) f(IntTag<FAM_GAMMA>{}, IntTag<LNK_INVERSE>{});
+    else if (lnk == LNK_LOG) f(IntTag<FAM_GAMMA>{}, IntTag<LNK_LOG>{});
+    else f(IntTag<FAM_GAMMA>{}, IntTag<LNK_RT>{});
+  }
+  return true;
+}
+// the link slot of the instantiation dispatch_family_link picks (LNK_RT or the link itself)
+constexpr int dispatched_link(int fam, int lnk) {
+  return (noncanonical_pair(fam, lnk) && !(fam == FAM_GAMMA && lnk == LNK_LOG)) ? LNK_RT : lnk;
+}
 
 // Which families carry their final statistics in the narrow pass (PassArgs::stats_in_pass;
 // rowmath.hpp pass_row_stats): binomial / logit (without m), Poisson / log, Gamma / inverse.

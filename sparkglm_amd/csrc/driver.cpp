@@ -28,14 +28,29 @@ static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 const char* get_error() { return g_err.c_str(); }
 
-int family_link_valid(int family, int link) {
-  switch (family) {
-    case FAM_BINOMIAL: return link == LNK_LOGIT || link == LNK_PROBIT || link == LNK_CLOGLOG;
-    case FAM_GAUSSIAN: return link == LNK_IDENTITY;
-    case FAM_POISSON: return link == LNK_LOG;
-    case FAM_GAMMA: return link == LNK_INVERSE;
-    default: return 0;
-  }
+int family_link_valid(int family, int link) { return family_link_pair(family, link) ? 1 : 0; }
+
+// The non-canonical pairs (common.hpp noncanonical_pair) can leave their family's range: a pass marks
+// such a row with a NaN unit deviance (rowmath.hpp link_row_valid), so a non-finite deviance means that
+// no valid set of coefficients was reached -- R stops there too, and like the reference this driver has
+// no step-halving.  The canonical pairs keep their behaviour on non-finite deviances.
+static const char* const kFamilyName[] = {"binomial", "gaussian", "poisson", "gamma"};
+static int range_error(int family, int iter) {
+  char buf[160];
+  std::snprintf(buf, sizeof buf, "requirement failed: no valid set of coefficients: %s left the %s range at iteration %d",
+                family == FAM_GAUSSIAN ? "eta" : "mu", kFamilyName[family], iter);
+  set_error(buf);
+  return SGLM_EINVAL;
+}
+// link(mu0) of the initial pass (the extension families' links), checked before the first pass
+static bool start_valid(int family, int link, double mu0) {
+  const double eta0 = link == LNK_IDENTITY ? mu0
+                      : link == LNK_LOG    ? std::log(mu0)
+                      : link == LNK_INVERSE ? 1.0 / mu0
+                                            : std::sqrt(mu0);
+  if (!std::isfinite(eta0)) return false;
+  if (family == FAM_GAUSSIAN) return !(link == LNK_INVERSE && eta0 == 0.0);
+  return std::isfinite(mu0) && mu0 > 0.0 && !(link == LNK_SQRT && !(eta0 > 0.0));
 }
 
 double family_dev_factor(int family) { return family == FAM_GAUSSIAN ? 1.0 : 2.0; }
@@ -111,10 +126,13 @@ int glm_drive(Backend& be, const sglm_glm_opts& o, sglm_preglm* out) {
   const double ymean = sums[0] / nrow;  // GLM.scala:263 / 423
   const double fac = family_dev_factor(o.family);
   const int init_mode = (o.init_mode == SGLM_INIT_MULTIPLE) ? MODE_INIT_MULTI : MODE_INIT_SINGLE;
+  const bool check_range = noncanonical_pair(o.family, o.link);
+  if (check_range && !start_valid(o.family, o.link, ymean)) return range_error(o.family, 0);
 
   rc = be.pass(init_mode, nullptr, ymean, 0.0, o.family, o.link, packed.data());
   if (rc) return rc;
   double dev = fac * packed[tri_count(p) + p + S_DEV];
+  if (check_range && !std::isfinite(dev)) return range_error(o.family, 0);
   const double null_dev = dev;  // GLM.scala:272 / 444
   double deltad = 1.0, d_prev = 0.0;  // d_prev: |deltad| of the iteration before (speculation)
   int iter = 0;
@@ -138,7 +156,10 @@ int glm_drive(Backend& be, const sglm_glm_opts& o, sglm_preglm* out) {
     bool spec = false;
     if (be.has_dev_pass() && iter >= 2 && d_prev > 0.0 && !(o.max_iter > 0 && iter + 1 >= o.max_iter)) {
       const double dk = std::fabs(deltad);
-      spec = dk * dk * dk < 0.1 * o.tol * d_prev * d_prev;
+      // (the non-canonical pairs: Fisher scoring is not Newton's method there and converges linearly, so
+      // the next change is predicted as d_k * (d_k / d_{k-1}); under the quadratic rule 60 of 70 test fits
+      // ran one deviance-only pass too early and repeated it in full)
+      spec = check_range ? dk * dk < 0.1 * o.tol * d_prev : dk * dk * dk < 0.1 * o.tol * d_prev * d_prev;
     }
     if (spec) {
       rc = be.pass_dev(MODE_IRLS, beta.data(), ymean, 0.0, o.family, o.link, packed.data());
@@ -155,6 +176,7 @@ int glm_drive(Backend& be, const sglm_glm_opts& o, sglm_preglm* out) {
     dev = fac * packed[tri_count(p) + p + S_DEV];
     deltad = dev - dev_old;
     iter = iter + 1;
+    if (check_range && !std::isfinite(dev)) return range_error(o.family, iter);
     if (out->dev_trace && iter < out->max_trace) out->dev_trace[iter] = dev;
     if (o.verbose) {  // println(iter.toString + "\t" + deltad.toString)  (GLM.scala:304)
       char buf[64];
@@ -205,6 +227,8 @@ int irls_iterate(Backend& be, const sglm_glm_opts& o, double* beta, int iters, d
     int rc = be.pass(MODE_IRLS, beta, 0.0, 0.0, o.family, o.link, packed.data());
     if (rc) return rc;
     if (last_dev) *last_dev = family_dev_factor(o.family) * packed[tri_count(p) + p + S_DEV];
+    if (noncanonical_pair(o.family, o.link) && !std::isfinite(packed[tri_count(p) + p + S_DEV]))
+      return range_error(o.family, it);
     const double t0 = now_ms();
     const int srv = solver->solve(packed.data(), beta);
     be.solve_ms += now_ms() - t0;

@@ -323,9 +323,12 @@ namespace {
 int pass_kernel_choice(int64_t n_pad, int P16, bool narrow, bool wide, bool proc, int fused_split, int family,
                        int link, char* name, size_t len) {
   static const char* fam[] = {"binomial", "gaussian", "poisson", "gamma"};
-  static const char* lnk[] = {"logit", "probit", "cloglog", "identity", "log", "inverse"};
+  static const char* lnk[] = {"logit", "probit", "cloglog", "identity", "log", "inverse", "sqrt"};
   const char* f = (family >= 0 && family < 4) ? fam[family] : "?";
-  const char* l = (link >= 0 && link < 6) ? lnk[link] : "?";
+  // the link slot of the instantiation the launchers' dispatch picks (common.hpp dispatch_family_link):
+  // the pairs without a dedicated one run their family's run-time-link instantiation
+  const int il = dispatched_link(family, link);
+  const char* l = il == LNK_RT ? "runtime" : (il >= 0 && il < 7) ? lnk[il] : "?";
   int k;
   if (wide) {
     k = proc ? SGLM_KERNEL_WIDE_PROC : SGLM_KERNEL_WIDE;

@@ -321,7 +321,7 @@ __device__ __forceinline__ void row_stage(double* lds, int buf, int wb, const Pa
       // (P16 = 16: the row arithmetic of K1r's row_stage_r, so that K1 and K1r are bitwise
       // interchangeable -- tests/test_gpu_fused_split.py)
       else pass_row(FAM, LNK, a.mode, eta, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux,
-                    P16 == 16);
+                    P16 == 16, false, nullptr, a.link);
     }
     lds[G::OFF_W + wb * 2 * RB + r] = w;
     lds[G::OFF_W + wb * 2 * RB + RB + r] = wz;
@@ -790,7 +790,8 @@ __device__ __forceinline__ void row_stage_r(double* lds, int buf, const PassArgs
       if (a.mode == MODE_IRLS) eta = eta + off;
       if (FAM == FAM_BINOMIAL && init_fast_row(FAM, a.mode, a.m != nullptr) && y >= 0.0 && y <= 1.0)
         pass_row_init(lds + R::OFF_INIT, y, off, pw, w, wz, s_dev, s_aux);
-      else pass_row(FAM, LNK, a.mode, eta, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true);
+      else pass_row(FAM, LNK, a.mode, eta, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
+                    false, nullptr, a.link);
     }
     lds[R::OFF_W + buf * 2 * RB + r] = w;
     lds[R::OFF_W + buf * 2 * RB + RB + r] = wz;
@@ -1057,23 +1058,12 @@ __global__ void __launch_bounds__(64 * GeoR<P16>::NW, 3) irls_pass_r_kernel(Pass
 template <int P16>
 static hipError_t launch_pass_k1(const PassArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   const dim3 g(grid), b(64 * Geo<P16>::NW);
-  const int mode_fam = (a.mode == MODE_LM_GRAM) ? FAM_GAUSSIAN : a.family;
-  const int mode_lnk = (a.mode == MODE_LM_GRAM) ? LNK_IDENTITY : a.link;
-  if (mode_fam == FAM_BINOMIAL && mode_lnk == LNK_LOGIT)
-    hipExtLaunchKernelGGL((irls_pass_kernel<P16, FAM_BINOMIAL, LNK_LOGIT>), g, b, 0, st, e0, e1, 0, a);
-  else if (mode_fam == FAM_BINOMIAL && mode_lnk == LNK_PROBIT)
-    hipExtLaunchKernelGGL((irls_pass_kernel<P16, FAM_BINOMIAL, LNK_PROBIT>), g, b, 0, st, e0, e1, 0, a);
-  else if (mode_fam == FAM_BINOMIAL)
-    hipExtLaunchKernelGGL((irls_pass_kernel<P16, FAM_BINOMIAL, LNK_CLOGLOG>), g, b, 0, st, e0, e1, 0, a);
-  else if (mode_fam == FAM_GAUSSIAN)
-    hipExtLaunchKernelGGL((irls_pass_kernel<P16, FAM_GAUSSIAN, LNK_IDENTITY>), g, b, 0, st, e0, e1, 0, a);
-  else if (mode_fam == FAM_POISSON)
-    hipExtLaunchKernelGGL((irls_pass_kernel<P16, FAM_POISSON, LNK_LOG>), g, b, 0, st, e0, e1, 0, a);
-  else if (mode_fam == FAM_GAMMA)
-    hipExtLaunchKernelGGL((irls_pass_kernel<P16, FAM_GAMMA, LNK_INVERSE>), g, b, 0, st, e0, e1, 0, a);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  const int fam = (a.mode == MODE_LM_GRAM) ? FAM_GAUSSIAN : a.family;
+  const int lnk = (a.mode == MODE_LM_GRAM) ? LNK_IDENTITY : a.link;
+  const bool ok = dispatch_family_link(fam, lnk, [&](auto F, auto L) {
+    hipExtLaunchKernelGGL((irls_pass_kernel<P16, decltype(F)::value, decltype(L)::value>), g, b, 0, st, e0, e1, 0, a);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // K1r launch for the family/link of the pass (LM passes: the Gaussian identity row stage).
@@ -1082,14 +1072,11 @@ static hipError_t launch_pass_r_fl(const PassArgs& a, int grid, hipStream_t st, 
   const int fam = (a.mode == MODE_LM_GRAM) ? FAM_GAUSSIAN : a.family;
   const int lnk = (a.mode == MODE_LM_GRAM) ? LNK_IDENTITY : a.link;
   const dim3 g(grid), b(64 * GeoR<P16>::NW);
-  if (fam == FAM_BINOMIAL && lnk == LNK_LOGIT) hipExtLaunchKernelGGL((irls_pass_r_kernel<P16, FAM_BINOMIAL, LNK_LOGIT>), g, b, 0, st, e0, e1, 0, a);
-  else if (fam == FAM_BINOMIAL && lnk == LNK_PROBIT) hipExtLaunchKernelGGL((irls_pass_r_kernel<P16, FAM_BINOMIAL, LNK_PROBIT>), g, b, 0, st, e0, e1, 0, a);
-  else if (fam == FAM_BINOMIAL) hipExtLaunchKernelGGL((irls_pass_r_kernel<P16, FAM_BINOMIAL, LNK_CLOGLOG>), g, b, 0, st, e0, e1, 0, a);
-  else if (fam == FAM_GAUSSIAN) hipExtLaunchKernelGGL((irls_pass_r_kernel<P16, FAM_GAUSSIAN, LNK_IDENTITY>), g, b, 0, st, e0, e1, 0, a);
-  else if (fam == FAM_POISSON) hipExtLaunchKernelGGL((irls_pass_r_kernel<P16, FAM_POISSON, LNK_LOG>), g, b, 0, st, e0, e1, 0, a);
-  else if (fam == FAM_GAMMA) hipExtLaunchKernelGGL((irls_pass_r_kernel<P16, FAM_GAMMA, LNK_INVERSE>), g, b, 0, st, e0, e1, 0, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  const bool ok = dispatch_family_link(fam, lnk, [&](auto F, auto L) {
+    hipExtLaunchKernelGGL((irls_pass_r_kernel<P16, decltype(F)::value, decltype(L)::value>), g, b, 0, st, e0, e1, 0,
+                          a);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace sglm

@@ -135,6 +135,11 @@ __global__ void unlink_kernel(double* __restrict__ v, const double* __restrict__
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     v[i] = unlink_fn(FAM, LNK, v[i], m ? m[i] : 1.0);
 }
+// the non-canonical pairs of the extension families (rowmath.hpp unlink_fn_x): the link is an argument
+__global__ void unlink_x_kernel(double* __restrict__ v, int64_t n, int link) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    v[i] = unlink_fn_x(link, v[i]);
+}
 
 // Block partial sums of y (GLM.scala:420-423 ySums) -- fixed order per block.
 __global__ void ysum_kernel(const double* __restrict__ y, int64_t n, double* __restrict__ part) {
@@ -191,7 +196,13 @@ __global__ void __launch_bounds__(256) stats_kernel(StatsArgs a) {
     } else if (a.eta) {
       eta = a.eta[i];
     }
-    stats_row(FAM, LNK, a.mode, eta, a.y[i], m, pw, a.mu0, ybar, a.m != nullptr, acc);
+    if constexpr (link_by_link(FAM, LNK)) {  // the non-canonical pairs: mu by the link
+      const RowAcc r = stats_row_ref_x(FAM, link_of<LNK>(a.link), a.mode, eta, a.y[i], pw, a.mu0);
+#pragma unroll
+      for (int k = 0; k < NS; ++k) acc.s[k] += r.s[k];
+    } else {
+      stats_row(FAM, LNK, a.mode, eta, a.y[i], m, pw, a.mu0, ybar, a.m != nullptr, acc);
+    }
   }
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
@@ -540,20 +551,14 @@ hipError_t launch_stats(const StatsArgs& a, int grid, hipStream_t st) {
       case 7: hipLaunchKernelGGL((stats_kernel<FAM_GAUSSIAN, LNK_IDENTITY, 56>), gr, bl, 0, st, a); break;
       default: hipLaunchKernelGGL((stats_kernel<FAM_GAUSSIAN, LNK_IDENTITY, 64>), gr, bl, 0, st, a); break;
     }
-  } else if (a.mode == MODE_LM_RESID || (a.family == FAM_GAUSSIAN && a.link == LNK_IDENTITY))
+  } else if (a.mode == MODE_LM_RESID) {
     hipLaunchKernelGGL((stats_kernel<FAM_GAUSSIAN, LNK_IDENTITY>), gr, bl, 0, st, a);
-  else if (a.family == FAM_BINOMIAL && a.link == LNK_LOGIT)
-    hipLaunchKernelGGL((stats_kernel<FAM_BINOMIAL, LNK_LOGIT>), gr, bl, 0, st, a);
-  else if (a.family == FAM_BINOMIAL && a.link == LNK_PROBIT)
-    hipLaunchKernelGGL((stats_kernel<FAM_BINOMIAL, LNK_PROBIT>), gr, bl, 0, st, a);
-  else if (a.family == FAM_BINOMIAL && a.link == LNK_CLOGLOG)
-    hipLaunchKernelGGL((stats_kernel<FAM_BINOMIAL, LNK_CLOGLOG>), gr, bl, 0, st, a);
-  else if (a.family == FAM_POISSON && a.link == LNK_LOG)
-    hipLaunchKernelGGL((stats_kernel<FAM_POISSON, LNK_LOG>), gr, bl, 0, st, a);
-  else if (a.family == FAM_GAMMA && a.link == LNK_INVERSE)
-    hipLaunchKernelGGL((stats_kernel<FAM_GAMMA, LNK_INVERSE>), gr, bl, 0, st, a);
-  else
-    return hipErrorInvalidValue;
+  } else {
+    const bool ok = dispatch_family_link(a.family, a.link, [&](auto F, auto L) {
+      hipLaunchKernelGGL((stats_kernel<decltype(F)::value, decltype(L)::value>), gr, bl, 0, st, a);
+    });
+    if (!ok) return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
@@ -581,21 +586,14 @@ hipError_t launch_unlink(double* v, const double* m, int64_t n, int family, int 
   if (blocks > 65536) blocks = 65536;
   if (blocks < 1) blocks = 1;
   const dim3 g((unsigned)blocks), b(256);
-  if (family == FAM_BINOMIAL && link == LNK_LOGIT)
-    hipLaunchKernelGGL((unlink_kernel<FAM_BINOMIAL, LNK_LOGIT>), g, b, 0, st, v, m, n);
-  else if (family == FAM_BINOMIAL && link == LNK_PROBIT)
-    hipLaunchKernelGGL((unlink_kernel<FAM_BINOMIAL, LNK_PROBIT>), g, b, 0, st, v, m, n);
-  else if (family == FAM_BINOMIAL && link == LNK_CLOGLOG)
-    hipLaunchKernelGGL((unlink_kernel<FAM_BINOMIAL, LNK_CLOGLOG>), g, b, 0, st, v, m, n);
-  else if (family == FAM_GAUSSIAN)
-    return hipSuccess;  // identity
-  else if (family == FAM_POISSON)
-    hipLaunchKernelGGL((unlink_kernel<FAM_POISSON, LNK_LOG>), g, b, 0, st, v, m, n);
-  else if (family == FAM_GAMMA)
-    hipLaunchKernelGGL((unlink_kernel<FAM_GAMMA, LNK_INVERSE>), g, b, 0, st, v, m, n);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  if (family == FAM_GAUSSIAN && link == LNK_IDENTITY) return hipSuccess;  // identity
+  const bool ok = dispatch_family_link(family, link, [&](auto F, auto L) {
+    if constexpr (link_by_link(decltype(F)::value, decltype(L)::value))
+      hipLaunchKernelGGL(unlink_x_kernel, g, b, 0, st, v, n, link);
+    else
+      hipLaunchKernelGGL((unlink_kernel<decltype(F)::value, decltype(L)::value>), g, b, 0, st, v, m, n);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_ysum(const double* y, int64_t n, double* part, int nparts, hipStream_t st) {

@@ -207,8 +207,10 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
   // initial pass's unit deviance at mu0 and lgamma(y + 1) (rowmath.hpp poisson_init_table), the
   // IRLS passes' y log y (poisson_ylogy_table, pass_row ylogy)
   constexpr bool PTAB = !IRLS && FAM == FAM_POISSON && (G::LDS + 2 * POIS_TAB + 8) * 8 <= 160 * 1024;
-  constexpr bool YTAB = IRLS && FAM == FAM_POISSON && (G::LDS + POIS_TAB) * 8 <= 160 * 1024;
-  static_assert(FAM != FAM_POISSON || PTAB || YTAB, "the Poisson tables fit every narrow variant's LDS");
+  // (the y log y table serves the log link's fast path only; the LNK_RT rows take pass_row_ref)
+  constexpr bool YTAB = IRLS && FAM == FAM_POISSON && LNK == LNK_LOG && (G::LDS + POIS_TAB) * 8 <= 160 * 1024;
+  static_assert(FAM != FAM_POISSON || PTAB || YTAB || (IRLS && LNK != LNK_LOG),
+                "the Poisson tables fit every narrow variant's LDS");
   __shared__ double lds[G::LDS + (PTAB ? 2 * POIS_TAB + 8 : (YTAB ? POIS_TAB : 0))];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -223,7 +225,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
   if constexpr (PTAB) {
     for (int k = threadIdx.x; k < POIS_TAB; k += 64 * G::NW) poisson_init_table(ptab, a.mu0, k);
     if (threadIdx.x == 0) {
-      const InitConst ic = init_const(FAM, LNK, a.mode, a.mu0);
+      const InitConst ic = init_const(FAM, link_of<LNK>(a.link), a.mode, a.mu0, link_by_link(FAM, LNK));
       for (int k = 0; k < 6; ++k) pconst[k] = ic.v[k];
     }
     __syncthreads();
@@ -412,7 +414,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
             pass_row_stats<FAM>(et, y, off, pw, w, wz, s_dev, s_aux, s_pear, s_ll, s_bad, true, ylogy);
           else if (!(PTAB && poisson_init_row(pconst, ptab, y, off, pw, w, wz, s_dev, s_aux, s_ll))) {
             pass_row(FAM, LNK, mode, et, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
-                     !IRLS, ylogy);
+                     !IRLS, ylogy, a.link);
             if constexpr (LMX) s_pear += y * y;
             if constexpr (INIT_CONST)
               if (mode != MODE_LM_GRAM) s_ll += init_stats_const<FAM>(y, pw);
@@ -473,7 +475,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
             pass_row_stats<FAM>(eta, yv, ov, pv, w, wz, s_dev, s_aux, s_pear, s_ll, s_bad, true, ylogy);
           else if (!(PTAB && poisson_init_row(pconst, ptab, yv, ov, pv, w, wz, s_dev, s_aux, s_ll))) {
             pass_row(FAM, LNK, mode, eta, yv, mv, ov, pv, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
-                     !IRLS, ylogy);
+                     !IRLS, ylogy, a.link);
             if constexpr (LMX) s_pear += yv * yv;
             if constexpr (INIT_CONST)
               if (mode != MODE_LM_GRAM) s_ll += init_stats_const<FAM>(yv, pv);
@@ -533,7 +535,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
           pass_row_stats<FAM>(eta, y, off, pw, w, wz, s_dev, s_aux, s_pear, s_ll, s_bad, true, ylogy);
         else if (!(PTAB && poisson_init_row(pconst, ptab, y, off, pw, w, wz, s_dev, s_aux, s_ll))) {
           pass_row(FAM, LNK, mode, eta, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
-                   !IRLS, ylogy);
+                   !IRLS, ylogy, a.link);
           if constexpr (LMX) s_pear += y * y;
           if constexpr (INIT_CONST)
             if (mode != MODE_LM_GRAM) s_ll += init_stats_const<FAM>(y, pw);
@@ -614,7 +616,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
           pass_row_stats<FAM>(et, y, off, pw, w, wz, s_dev, s_aux, s_pear, s_ll, s_bad, true, ylogy);
         else if (!(PTAB && poisson_init_row(pconst, ptab, y, off, pw, w, wz, s_dev, s_aux, s_ll))) {
           pass_row(FAM, LNK, mode, et, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
-                   !IRLS, ylogy);
+                   !IRLS, ylogy, a.link);
           if constexpr (LMX) s_pear += y * y;
           if constexpr (INIT_CONST)
             if (mode != MODE_LM_GRAM) s_ll += init_stats_const<FAM>(y, pw);
@@ -798,21 +800,10 @@ hipError_t launch_narrow_p(const PassArgs& a, int grid, hipStream_t st, hipEvent
   const dim3 gr(grid), bl(64 * NGeo<P16>::NW);
   const int fam = (a.mode == MODE_LM_GRAM) ? FAM_GAUSSIAN : a.family;
   const int lnk = (a.mode == MODE_LM_GRAM) ? LNK_IDENTITY : a.link;
-  if (fam == FAM_BINOMIAL && lnk == LNK_LOGIT)
-    launch_narrow_fl<P16, FAM_BINOMIAL, LNK_LOGIT>(a, gr, bl, st, e0, e1);
-  else if (fam == FAM_BINOMIAL && lnk == LNK_PROBIT)
-    launch_narrow_fl<P16, FAM_BINOMIAL, LNK_PROBIT>(a, gr, bl, st, e0, e1);
-  else if (fam == FAM_BINOMIAL)
-    launch_narrow_fl<P16, FAM_BINOMIAL, LNK_CLOGLOG>(a, gr, bl, st, e0, e1);
-  else if (fam == FAM_GAUSSIAN)
-    launch_narrow_fl<P16, FAM_GAUSSIAN, LNK_IDENTITY>(a, gr, bl, st, e0, e1);
-  else if (fam == FAM_POISSON)
-    launch_narrow_fl<P16, FAM_POISSON, LNK_LOG>(a, gr, bl, st, e0, e1);
-  else if (fam == FAM_GAMMA)
-    launch_narrow_fl<P16, FAM_GAMMA, LNK_INVERSE>(a, gr, bl, st, e0, e1);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  const bool ok = dispatch_family_link(fam, lnk, [&](auto F, auto L) {
+    launch_narrow_fl<P16, decltype(F)::value, decltype(L)::value>(a, gr, bl, st, e0, e1);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace

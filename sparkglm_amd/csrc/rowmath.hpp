@@ -7,7 +7,7 @@
 //   devBinomial row value   GLM.scala:166-167   (summed, times 2 on the host)
 //   pearsonCalc             GLM.scala:90-101
 //   llBinomial              GLM.scala:132-143   (Breeze Binomial(m.toInt, mu).logProbabilityOf)
-// Extension families (gaussian/identity, poisson/log, gamma/inverse, prior weights)
+// Extension families (gaussian, poisson, gamma with R's three links each; prior weights)
 // follow R's family objects on the same skeleton.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -131,6 +131,46 @@ __device__ __forceinline__ double lprime_fn(int fam, int lnk, double mu, double 
   return -1.0 / (mu * mu);
 }
 
+// The extension families' links by the link alone (R's make.link: identity, log, inverse, sqrt) -- the
+// non-canonical pairs (common.hpp noncanonical_pair).  link_fn / unlink_fn / lprime_fn above select by
+// family and serve the binomial links and the canonical pairs only; they and the functions built on them
+// stay as they are, so that the canonical instantiations' code does not move.
+__device__ __forceinline__ double link_fn_x(int lnk, double mu) {
+  if (lnk == LNK_IDENTITY) return mu;
+  if (lnk == LNK_LOG) return log(mu);
+  if (lnk == LNK_INVERSE) return 1.0 / mu;
+  return sqrt(mu);
+}
+__device__ __forceinline__ double unlink_fn_x(int lnk, double eta) {
+  if (lnk == LNK_IDENTITY) return eta;
+  if (lnk == LNK_LOG) return exp(eta);
+  if (lnk == LNK_INVERSE) return 1.0 / eta;
+  return eta * eta;
+}
+__device__ __forceinline__ double lprime_fn_x(int lnk, double mu) {
+  if (lnk == LNK_IDENTITY) return 1.0;
+  if (lnk == LNK_LOG) return 1.0 / mu;
+  if (lnk == LNK_INVERSE) return -1.0 / (mu * mu);
+  return 0.5 / sqrt(mu);
+}
+// whether an instantiation's rows take the _x functions (a compile-time constant at every call site)
+constexpr bool link_by_link(int fam, int lnk) { return lnk == LNK_RT || noncanonical_pair(fam, lnk); }
+
+// The link of an instantiation: its template argument, or (LNK_RT) the run-time link of its arguments.
+template <int LNK>
+__device__ __forceinline__ int link_of(int rt_link) {
+  return LNK == LNK_RT ? rt_link : LNK;
+}
+
+// R's validmu / valideta for the non-canonical pairs (common.hpp noncanonical_pair): gaussian needs a
+// finite eta (inverse: eta != 0); poisson and gamma a finite mu > 0 (sqrt: eta > 0).  A row outside
+// cannot be fitted -- the reference has no step-halving -- and pass_row_ref marks it with a NaN unit
+// deviance (pass_row_ref_x), which costs the pass no accumulator and makes the drivers stop with SGLM_EINVAL.
+__device__ __forceinline__ bool link_row_valid(int fam, int lnk, double eta, double mu) {
+  if (fam == FAM_GAUSSIAN) return isfinite(eta) && !(lnk == LNK_INVERSE && eta == 0.0);
+  return isfinite(mu) && mu > 0.0 && !(lnk == LNK_SQRT && !(eta > 0.0));
+}
+
 __device__ __forceinline__ double variance_fn(int fam, double mu, double m) {
   if (fam == FAM_BINOMIAL) return mu * (1.0 + (-1.0 * (mu / m)));
   if (fam == FAM_GAUSSIAN) return 1.0;
@@ -207,6 +247,27 @@ __device__ __noinline__ RowWZ pass_row_ref(int fam, int lnk, int mode, double et
   r.dev = unit_dev(fam, y, mode == MODE_IRLS ? mu : mu0, m, pw);
   return r;
 }
+// pass_row_ref for the non-canonical pairs: the same operation order with the links selected by link,
+// and the validity of the row (link_row_valid) carried as a NaN unit deviance.  An invalid row yields
+// NaN / Inf arithmetic only -- no index depends on mu.
+__device__ __noinline__ RowWZ pass_row_ref_x(int fam, int lnk, int mode, double eta, double y, double m, double off,
+                                             double pw, double mu0) {
+  double mu;
+  if (mode == MODE_IRLS) {
+    mu = unlink_fn_x(lnk, eta);
+  } else {
+    eta = link_fn_x(lnk, mu0);
+    mu = (mode == MODE_INIT_SINGLE) ? mu0 : unlink_fn_x(lnk, eta);
+  }
+  const double g = lprime_fn_x(lnk, mu);
+  const double v = variance_fn(fam, mu, m);
+  RowWZ r;
+  r.w = pw * (1.0 / (v * (g * g)));
+  const double z = (eta + ((y + (-1.0 * mu)) * g)) + (-1.0 * off);
+  r.wz = r.w * z;
+  r.dev = link_row_valid(fam, lnk, eta, mu) ? unit_dev(fam, y, mode == MODE_IRLS ? mu : mu0, m, pw) : NAN;
+  return r;
+}
 
 // The initial pass of a binomial fit without m (GLM.scala:263-272, 429-444): mu = mu0
 // (fitSingle) or unlink(link(mu0)) (fitMultiple) is the same for every row, so link, lPrime and
@@ -217,11 +278,12 @@ __device__ __noinline__ RowWZ pass_row_ref(int fam, int lnk, int mode, double et
 struct InitConst {
   double v[6];
 };
-__device__ __forceinline__ InitConst init_const(int fam, int lnk, int mode, double mu0) {
+// (by_link: the non-canonical pairs' links, link_by_link -- a compile-time constant at the call sites)
+__device__ __forceinline__ InitConst init_const(int fam, int lnk, int mode, double mu0, bool by_link = false) {
   InitConst c;
-  const double e0 = link_fn(fam, lnk, mu0, 1.0);
-  const double mu = (mode == MODE_INIT_SINGLE) ? mu0 : unlink_fn(fam, lnk, e0, 1.0);
-  const double g = lprime_fn(fam, lnk, mu, 1.0);
+  const double e0 = by_link ? link_fn_x(lnk, mu0) : link_fn(fam, lnk, mu0, 1.0);
+  const double mu = (mode == MODE_INIT_SINGLE) ? mu0 : (by_link ? unlink_fn_x(lnk, e0) : unlink_fn(fam, lnk, e0, 1.0));
+  const double g = by_link ? lprime_fn_x(lnk, mu) : lprime_fn(fam, lnk, mu, 1.0);
   c.v[0] = e0;
   c.v[1] = mu;
   c.v[2] = g;
@@ -262,7 +324,7 @@ __device__ __forceinline__ void pass_row_init(const double* c, double y, double 
 __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta, double y, double m, double off,
                                          double pw, double mu0, double ybar, bool has_m, double& w, double& wz,
                                          double& s_dev, double& s_aux, bool small_exp = false,
-                                         bool init_fast = false, const double* ylogy = nullptr) {
+                                         bool init_fast = false, const double* ylogy = nullptr, int rt_link = 0) {
   (void)ybar;
   if (fam == FAM_BINOMIAL && lnk == LNK_LOGIT && mode == MODE_IRLS && !has_m && fabs(eta) < 8.0 && y >= 0.0 &&
       y <= 1.0) {
@@ -284,7 +346,7 @@ __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta,
     s_aux += pw;
     return;
   }
-  if (fam == FAM_POISSON && mode == MODE_IRLS && fabs(eta) < 700.0 && y >= 0.0 && y < 1e300) {
+  if (fam == FAM_POISSON && lnk == LNK_LOG && mode == MODE_IRLS && fabs(eta) < 700.0 && y >= 0.0 && y < 1e300) {
     // Poisson / log (R's poisson()): mu = exp(eta), g' = 1/mu, V = mu, so
     //   w = 1/(V g'^2) = mu,  w*z = mu (eta - off) + (y - mu),
     //   dev row = y log(y/mu) - (y - mu) with log(y/mu) = log(y) - eta
@@ -300,7 +362,8 @@ __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta,
     s_aux += pw;
     return;
   }
-  if (fam == FAM_GAMMA && mode == MODE_IRLS && eta > 1e-150 && eta < 1e150 && y > 1e-150 && y < 1e150) {
+  if (fam == FAM_GAMMA && lnk == LNK_INVERSE && mode == MODE_IRLS && eta > 1e-150 && eta < 1e150 && y > 1e-150 &&
+      y < 1e150) {
     // Gamma / inverse (R's Gamma()): mu = 1/eta, g' = -1/mu^2, V = mu^2, so
     //   w = mu^2,  w*z = mu^2 (eta - off) - (y - mu),
     //   dev row = -(log(y/mu) - (y - mu)/mu) = -(log(y eta) - (y eta - 1))
@@ -312,6 +375,21 @@ __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta,
     w = pw * mu2;
     wz = pw * (mu2 * (eta - off) - (y - mu));
     s_dev += pw * (-(log_pos(ye) - (ye - 1.0)));
+    s_aux += pw;
+    return;
+  }
+  if (fam == FAM_GAMMA && lnk == LNK_LOG && mode == MODE_IRLS && fabs(eta) < 300.0 && y > 1e-150 && y < 1e150) {
+    // Gamma / log (R's Gamma(link = "log")): mu = exp(eta), g' = 1/mu, V = mu^2, so the working weight
+    // is the prior weight itself, and with r = exp(-eta) = 1/mu
+    //   w = pw,  w*z = pw ((eta - off) + (y r - 1)),
+    //   dev row = -(log(y/mu) - (y - mu)/mu) = -(log(y r) - (y r - 1))
+    // -- one exp and one log, no division.  |eta| < 300 keeps r and y r normal and finite for log_pos
+    // and implies the row's validity (mu = exp(eta) finite and > 0); other rows take pass_row_ref.
+    const double r = small_exp ? exp_small(-eta) : exp(-eta);
+    const double yr = y * r;
+    w = pw;
+    wz = pw * ((eta - off) + (yr - 1.0));
+    s_dev += pw * (-(log_pos(yr) - (yr - 1.0)));
     s_aux += pw;
     return;
   }
@@ -330,7 +408,9 @@ __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta,
     pass_row_init(c.v, y, off, pw, w, wz, s_dev, s_aux);
     return;
   }
-  const RowWZ r = pass_row_ref(fam, lnk, mode, eta, y, m, off, pw, mu0);
+  // (LNK_RT instantiations: every row takes the reference functions at the arguments' link)
+  const RowWZ r = link_by_link(fam, lnk) ? pass_row_ref_x(fam, lnk == LNK_RT ? rt_link : lnk, mode, eta, y, m, off, pw, mu0)
+                                         : pass_row_ref(fam, lnk, mode, eta, y, m, off, pw, mu0);
   w = r.w;
   wz = r.wz;
   s_dev += r.dev;
@@ -375,6 +455,30 @@ __device__ __noinline__ RowAcc stats_row_ref(int fam, int lnk, int mode, double 
     acc.s[S_LL] += pw * ll;
     acc.s[S_BAD] += bad;
   } else if (fam == FAM_GAUSSIAN) {
+    acc.s[S_LL] += log(pw);
+  } else if (fam == FAM_POISSON) {
+    acc.s[S_LL] += pw * (y * log(mu) - mu - lgamma(y + 1.0));
+  } else {
+    acc.s[S_LL] += pw * log(y);
+    acc.s[S_AUX0] += pw * (y / mu);
+    acc.s[S_AUX1] += pw * log(mu);
+  }
+  return acc;
+}
+
+// stats_row_ref for the non-canonical pairs (extension families only): mu by the link.
+__device__ __noinline__ RowAcc stats_row_ref_x(int fam, int lnk, int mode, double eta, double y, double pw,
+                                               double mu0) {
+  RowAcc acc;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) acc.s[k] = 0.0;
+  const double mu = (mode == MODE_IRLS) ? unlink_fn_x(lnk, eta) : mu0;
+  const double v = variance_fn(fam, mu, 1.0);
+  const double r = y + (-1.0 * mu);
+  acc.s[S_DEV] += unit_dev(fam, y, mu, 1.0, pw);
+  acc.s[S_PEARSON] += pw * (r * r) / v;
+  acc.s[S_SUMW] += pw;
+  if (fam == FAM_GAUSSIAN) {
     acc.s[S_LL] += log(pw);
   } else if (fam == FAM_POISSON) {
     acc.s[S_LL] += pw * (y * log(mu) - mu - lgamma(y + 1.0));
@@ -596,8 +700,9 @@ struct InflRow {
   double w, rp, resid;
 };
 __device__ __noinline__ InflRow influence_row(int fam, int lnk, int rtype, double eta, double y, double m, double pw) {
-  const double mu = unlink_fn(fam, lnk, eta, m);
-  const double g = lprime_fn(fam, lnk, mu, m);
+  const bool x = noncanonical_pair(fam, lnk);  // the links selected by link (link_fn_x ...)
+  const double mu = x ? unlink_fn_x(lnk, eta) : unlink_fn(fam, lnk, eta, m);
+  const double g = x ? lprime_fn_x(lnk, mu) : lprime_fn(fam, lnk, mu, m);
   const double v = variance_fn(fam, mu, m);
   const double e = y + (-1.0 * mu);
   InflRow r;

@@ -457,7 +457,8 @@ __device__ __forceinline__ void wide_rows_body(const WideRowArgs& a) {
           et = et + off;
           if (a.eta_out) a.eta_out[row] = et;
         }
-        pass_row(FAM, LNK, a.mode, et, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w[r], wz[r], s_dev, s_aux);
+        pass_row(FAM, LNK, a.mode, et, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w[r], wz[r], s_dev, s_aux, false,
+                 false, nullptr, a.link);
       }
     }
 #pragma unroll
@@ -499,6 +500,15 @@ __global__ void __launch_bounds__(256) wide_rows_kernel(WideRowArgs a) {
 // at normal priority 1285.7, the row kernels spanning 862 ms beside 1124 ms of Gram).
 template <int FAM, int LNK>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) wide_rows_ov_kernel(WideRowArgs a) {
+  if (a.xs_out) __builtin_amdgcn_s_setprio(1);
+  wide_rows_body<FAM, LNK, 2, true>(a);
+}
+// The overlapped row stage of the non-canonical pairs (gamma / log and the LNK_RT instantiations): a
+// kernel of its own name, so that the register budget above (tests/test_residency.py counts and bounds
+// the wide_rows_ov_kernel instantiations) stays a statement about the six canonical kernels; these keep
+// the same budget (tests/test_links.py).
+template <int FAM, int LNK>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) wide_rows_link_ov_kernel(WideRowArgs a) {
   if (a.xs_out) __builtin_amdgcn_s_setprio(1);
   wide_rows_body<FAM, LNK, 2, true>(a);
 }
@@ -676,33 +686,29 @@ int64_t wide_stride() { return (int64_t)PT * PT * 256 + PANEL; }
   };
 SGLM_ROW_LAUNCH(wide_rows_kernel)
 SGLM_ROW_LAUNCH(wide_rows_ov_kernel)
+SGLM_ROW_LAUNCH(wide_rows_link_ov_kernel)
 #undef SGLM_ROW_LAUNCH
 
-template <template <int, int> class K>
+// KX: the kernel of the non-canonical pairs (rowmath.hpp link_by_link)
+template <template <int, int> class K, template <int, int> class KX>
 static hipError_t launch_rows_fl(int fam, int lnk, dim3 g, dim3 b, hipStream_t st, const WideRowArgs& a) {
-  if (fam == FAM_BINOMIAL && lnk == LNK_LOGIT)
-    K<FAM_BINOMIAL, LNK_LOGIT>::go(g, b, st, a);
-  else if (fam == FAM_BINOMIAL && lnk == LNK_PROBIT)
-    K<FAM_BINOMIAL, LNK_PROBIT>::go(g, b, st, a);
-  else if (fam == FAM_BINOMIAL)
-    K<FAM_BINOMIAL, LNK_CLOGLOG>::go(g, b, st, a);
-  else if (fam == FAM_GAUSSIAN)
-    K<FAM_GAUSSIAN, LNK_IDENTITY>::go(g, b, st, a);
-  else if (fam == FAM_POISSON)
-    K<FAM_POISSON, LNK_LOG>::go(g, b, st, a);
-  else if (fam == FAM_GAMMA)
-    K<FAM_GAMMA, LNK_INVERSE>::go(g, b, st, a);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  const bool ok = dispatch_family_link(fam, lnk, [&](auto F, auto L) {
+    constexpr int f = decltype(F)::value, l = decltype(L)::value;
+    // (gamma / log too: its inline fast path put the overlapped kernel 16 bytes into scratch at the 96
+    // VGPR budget, and the row stage is a few per cent of a wide pass -- both wide kernels run every
+    // non-canonical pair through the family's LNK_RT instantiation, so they stay bitwise alike)
+    if constexpr (l == LNK_RT || noncanonical_pair(f, l)) KX<f, LNK_RT>::go(g, b, st, a);
+    else K<f, l>::go(g, b, st, a);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_wide_rows(const WideRowArgs& a, int grid, hipStream_t st, bool ov) {
   const dim3 g(grid), b(256);
   const int fam = (a.mode == MODE_LM_GRAM) ? FAM_GAUSSIAN : a.family;
   const int lnk = (a.mode == MODE_LM_GRAM) ? LNK_IDENTITY : a.link;
-  return ov ? launch_rows_fl<wide_rows_ov_kernel_t>(fam, lnk, g, b, st, a)
-            : launch_rows_fl<wide_rows_kernel_t>(fam, lnk, g, b, st, a);
+  return ov ? launch_rows_fl<wide_rows_ov_kernel_t, wide_rows_link_ov_kernel_t>(fam, lnk, g, b, st, a)
+            : launch_rows_fl<wide_rows_kernel_t, wide_rows_kernel_t>(fam, lnk, g, b, st, a);
 }
 
 hipError_t launch_proc_gen(const ProcGenArgs& a, int grid, hipStream_t st) {

@@ -15,8 +15,10 @@ Faithful-to-the-reference behaviour (``strict = True``, the default):
   * the first iteration uses mu = mean(y) on one partition, unlink(link(mean(y))) on
     several (GLM.scala:263 vs 370-371); npart reports the partition count.
 With ``strict = False`` every overload runs on partitioned data and honours its offset.
-The extension families "gaussian", "poisson" and "gamma" (canonical links; prior weights
-through `fit_weighted`) follow R's family objects on the same IRLS skeleton.  Their `loglik`
+The extension families "gaussian", "poisson" and "gamma" (R's three links each: identity / log /
+inverse, log / identity / sqrt, inverse / identity / log; prior weights through `fit_weighted`)
+follow R's family objects on the same IRLS skeleton.  With a non-canonical link a fit whose mean
+leaves the family's range raises IllegalArgumentException (no step-halving).  Their `loglik`
 is R's logLik; `aic` stays createObj's -2 loglik + 2p (GLM.scala:70), which counts the
 coefficients only -- R's AIC(glm) for gaussian and Gamma adds 2 for the dispersion parameter,
 so it is 2 higher than `aic` here for those two families.
@@ -122,7 +124,7 @@ def _dispersion(obj) -> float:
 
 
 def _dmu_deta(link: str, eta, m=1.0):
-    """d mu / d eta of mu = unlink(eta, m) for the six links (the delta method of se.fit)."""
+    """d mu / d eta of mu = unlink(eta, m) for the seven links (the delta method of se.fit)."""
     eta = np.asarray(eta, dtype=np.float64)
     if link == "logit":
         e = np.exp(-np.abs(eta))
@@ -135,15 +137,17 @@ def _dmu_deta(link: str, eta, m=1.0):
         return np.ones_like(eta)
     if link == "log":
         return np.exp(eta)
+    if link == "sqrt":
+        return 2.0 * eta
     return -1.0 / (eta * eta)  # inverse
 
 
 def _engine_family_link(family: str, link: str):
     f = family.lower()
     if f in ("gaussian", "poisson", "gamma"):
-        canon = L.CANONICAL_LINK[f]
-        _require(link == canon, f"family {family} supports only the {canon} link")
-        return f, canon
+        allowed = L.FAMILY_LINKS[f]
+        _require(link in allowed, f"family {family} supports only the {', '.join(allowed)} links")
+        return f, link
     # binomial, including any unrecognised family string (GLM.scala:486-590)
     if link == "logit":
         return "binomial", "logit"
