@@ -611,9 +611,10 @@ struct TilesR {
 // K1r's LDS: a ring of NBUF row-block buffers -- as deep as 160 KB allows (4 up to P16 = 8, 3 up to
 // 12, 2 above): the DMA of block b + NBUF is issued when block b is consumed, so a row wave finds the
 // next block landed instead of waiting out its HBM latency.  (With two buffers that wait sat on the
-// row waves' per-block path; the deeper ring measured +1-9 % at P16 = 9..12 and +-0 at 16,
+// row waves' per-block path; the deeper ring measured +1-9 % at P16 = 9..12,
 // profiles/r04_midp_ab_run2_ring.txt -- at the mid widths the clock and the row stage's VALU bound
-// the pass more than the DMA latency did)
+// the pass more than the DMA latency did, DESIGN.md 8.  At P16 = 16 the depth stays two whatever is
+// asked for -- 32-row buffers fit no third -- and Gram waves 0..3 issue the DMA, pass_body_r.)
 template <int P16>
 struct GeoR {
   using G = Geo<P16>;
@@ -632,7 +633,7 @@ struct GeoR {
   static constexpr int RW = RB / RG, LPR = 64 / RW, CPG = 32 / LPR;
   static constexpr int BETAG_STRIDE = CPG * NT + 2;       // lane group stride of betag (+2: distinct banks)
   static constexpr int PER_BUF = XB + 4 * RB + 2 * RB + RB;  // X | y, m, offset, prior | w, w*z | eta
-  static constexpr int NCNT = 10;                         // counters: flag | ready[4] | done[4] (uint32)
+  static constexpr int NCNT = 10;                         // counters: flag | ready[4] | done[4] | landed[1] of P16 = 16 (uint32)
   static constexpr int FIXED = G::NCE + NW * NS + LPR * BETAG_STRIDE + NCNT / 2 + 6;
   static constexpr int LDS_MAX = 160 * 1024 / 8;
   static constexpr int NBUF = 4 * PER_BUF + FIXED <= LDS_MAX ? 4 : (3 * PER_BUF + FIXED <= LDS_MAX ? 3 : 2);
@@ -801,8 +802,64 @@ __device__ __forceinline__ void row_stage_r(double* lds, int buf, const PassArgs
   }
 }
 
+// Per-phase cycle sums of K1r's waves (s_memtime), a development build only: make variant
+// NAME=stamps DEFS=-DSGLM_K1R_STAMPS=1 (2: also the first k-step of every block), read back by
+// tools/k1r_stamps.py through sglm_k1r_stamps (kernels.hip).  Every wave of the middle workgroup
+// sums the cycles between its laps and stores the sums with ordinary vector stores at the end of
+// the kernel.  Row waves: 0 wait_landed, 1 flag round, 2 row stage, 3 wait for ready (tail blocks),
+// 4 X'Wz, 5 wait for done, 6 DMA issue; Gram waves: 0 wait for ready, 1 the block's k-steps (2: the
+// first of them, taken out of 1), 3 eta store and done, and where they issue the DMA (P16 = 16) 8 wait
+// for done, 9 DMA issue, 10 landing; slot 15 of every wave: its blocks.  lap_h also counts the lap by
+// its length (Gram waves: wait for ready in slots 4-7; row waves: wait_landed 7-10, flag round 11-14).  Each
+// lap waits for the wave's outstanding LDS operations, so it sits only where the wave has none
+// by construction (level 2 puts one inside the Gram block and is for the k-step profile only).
+#ifndef SGLM_K1R_STAMPS
+#define SGLM_K1R_STAMPS 0
+#endif
+#if SGLM_K1R_STAMPS
+constexpr int K1R_STAMP_SLOTS = 16;
+static __device__ unsigned long long k1r_stamps[12 * K1R_STAMP_SLOTS];
+#endif
+struct StampsR {
+#if SGLM_K1R_STAMPS
+  unsigned long long t = 0, s[K1R_STAMP_SLOTS] = {};
+  __device__ __forceinline__ void start() { t = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void lap(int i) {
+    const unsigned long long now = __builtin_amdgcn_s_memtime();
+    s[i] += now - t;
+    t = now;
+  }
+  // lap(i) and the lap's length counted into four slots from h: up to 1K, 4K, 16K cycles, longer
+  __device__ __forceinline__ void lap_h(int i, int h) {
+    const unsigned long long now = __builtin_amdgcn_s_memtime(), d = now - t;
+    s[i] += d;
+    t = now;
+    const int b = (d > 1024) + (d > 4096) + (d > 16384);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[h + k] += b == k;
+  }
+  __device__ __forceinline__ void count() { s[K1R_STAMP_SLOTS - 1] += 1; }
+  __device__ __forceinline__ void flush(int wv, int lane) {
+    if (blockIdx.x == gridDim.x / 2 && lane < K1R_STAMP_SLOTS) {
+      unsigned long long v = 0;
+#pragma unroll
+      for (int i = 0; i < K1R_STAMP_SLOTS; ++i)
+        if (lane == i) v = s[i];
+      k1r_stamps[wv * K1R_STAMP_SLOTS + lane] = v;
+    }
+  }
+#else
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ void lap(int) {}
+  __device__ __forceinline__ void lap_h(int, int) {}
+  __device__ __forceinline__ void count() {}
+  __device__ __forceinline__ void flush(int, int) {}
+#endif
+};
+
 template <int P16, int WV>
-__device__ __forceinline__ void gram_steps_r(const double* lds, int buf, int lane, d4 (&acc)[TilesR<P16, WV>::NT]) {
+__device__ __forceinline__ void gram_steps_r(const double* lds, int buf, int lane, d4 (&acc)[TilesR<P16, WV>::NT],
+                                             StampsR& st) {
   using G = Geo<P16>;
   using T = TilesR<P16, WV>;
   const double* xs = lds + GeoR<P16>::OFF_X + buf * GeoR<P16>::XB;
@@ -842,6 +899,7 @@ __device__ __forceinline__ void gram_steps_r(const double* lds, int buf, int lan
     // arbitration: waves 0-3 finished their Gram ~7K cycles before waves 4-7)
     if constexpr (!T::ROW) __builtin_amdgcn_s_setprio((WV >> 2) & 1 ? 0 : 1);
     kstep(j);
+    if (SGLM_K1R_STAMPS >= 2 && j == 0) st.lap(2);
     if constexpr (!T::ROW) __builtin_amdgcn_s_setprio((WV >> 2) & 1 ? 1 : 0);
     kstep(j + 1);
   }
@@ -853,7 +911,12 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
   using R = GeoR<P16>;
   using T = TilesR<P16, WV>;
   constexpr bool row_wave = T::ROW;
-  constexpr int si = row_wave ? WV - 8 : 0;  // DMA issuer index (row waves)
+  // P16 = 16 (two buffers): Gram waves 0..3 -- one per SIMD, the ones that finish a block first --
+  // issue the LDS-DMA instead of the row waves (GDMA below); otherwise the row waves do
+  constexpr bool GDMA = P16 == 16;
+  constexpr bool issuer = GDMA ? WV < 4 : row_wave;
+  constexpr int si = row_wave ? WV - 8 : 0;  // row wave index
+  constexpr int di = GDMA ? WV & 3 : si;     // DMA issuer index
   const int wg = blockIdx.x, nwg = gridDim.x;
   const int64_t b0 = (a.nblocks * wg) / nwg, b1 = (a.nblocks * (wg + 1)) / nwg;
   const bool do_gram = !a.no_gram;
@@ -866,16 +929,32 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
 
   // lane parts of the DMA source addresses (bytes): column quad q's 4 columns at cq * ld, rows
   // in the slot swizzle of stage_block, which depends on q mod 4 only
-  uint32_t voff[4];
-  const int li = lane & 15, lcq = lane >> 4;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) voff[k] = (uint32_t)(((int64_t)lcq * a.ld + ((2 * li) ^ ((8 * k + 2 * lcq) & 31))) * 8);
-  const uint32_t vvoff = (uint32_t)(lane < 16 ? 16 * lane : 16 * 16);
   constexpr int NB = R::NBUF, PER = R::QPW + 1;  // ring depth; vector-memory operations per staged block
-  if (row_wave)
+  auto lane_offsets = [&](int ln, uint32_t (&voff)[4], uint32_t& vvoff) {
+    const int li = ln & 15, lcq = ln >> 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) voff[k] = (uint32_t)(((int64_t)lcq * a.ld + ((2 * li) ^ ((8 * k + 2 * lcq) & 31))) * 8);
+    vvoff = (uint32_t)(ln < 16 ? 16 * ln : 16 * 16);
+  };
+  uint32_t voff[4], vvoff;
+  lane_offsets(lane, voff, vvoff);
+  auto stage = [&](int buf, int64_t blk) {
+    if constexpr (GDMA) {
+      // a Gram wave has no registers to keep the offsets in across its MFMAs: computed per block,
+      // from a lane id the compiler cannot hoist
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      uint32_t vo[4], vvo;
+      lane_offsets(ln, vo, vvo);
+      stage_block_r<P16>(lds, buf, a, blk, di, vo, vvo);
+    } else {
+      stage_block_r<P16>(lds, buf, a, blk, di, voff, vvoff);
+    }
+  };
+  if (issuer)
 #pragma unroll
     for (int k = 0; k < NB; ++k)
-      if (b0 + k < b1) stage_block_r<P16>(lds, k, a, b0 + k, si, voff, vvoff);
+      if (b0 + k < b1) stage(k, b0 + k);
   if (row_wave) __builtin_amdgcn_s_setprio(2);
   // wait until this wave's DMA of a block has landed while `later` blocks staged after it may fly
   auto wait_landed = [&](int64_t later) {
@@ -903,8 +982,18 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
   // block with one of them alone on the MFMA pipe; the row waves stage block b+NBUF into block b's
   // slot after done(b).  (The row stage of b+NBUF rewrites w(b): it follows the flag round of
   // b+NBUF, i.e. every row wave's DMA of b+NBUF, each issued after done(b).)
+  // GDMA (P16 = 16, two buffers; measured with the StampsR build, DESIGN.md 4 K1r: the row waves'
+  // chain DMA issue -> landing -> flag round -> row stage -> X'Wz -> done was the block period, the
+  // DMA issue alone a quarter of it -- the issue stalls on the memory system -- while Gram waves
+  // 0..3 sat 4-7K cycles of every block at ready): after its Gram of block b a Gram wave 0..3 waits
+  // for done(b), stages its quarter of block b+2, waits for it to land and bumps landed[s]; its
+  // SIMD's other Gram wave has the MFMA pipe meanwhile.  The row waves wait for landed[s] = 4 per use
+  // of the slot instead of their own DMA and flag round.  (Per-slot like ready and done: the two
+  // blocks of the prologue land in any order.)
   unsigned* ready = flag + 1;     // [NB]
   unsigned* done = flag + 1 + 4;  // [NB]
+  auto landed = [&](int s) { return s == 0 ? flag : flag + 9; };  // [2] (GDMA)
+  static_assert(!GDMA || (NB == 2 && R::NCNT >= 10), "landed counters");
   constexpr int RG = R::RG, LA = R::LA;
   auto spin = [&](unsigned* c, unsigned target) {
     while (__hip_atomic_load(c, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < target) __builtin_amdgcn_s_sleep(1);
@@ -913,14 +1002,20 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
     if (lane == 0) __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
   };
   auto next_buf = [](int b) { return b + 1 == NB ? 0 : b + 1; };
+  StampsR st;
+  st.start();
   if constexpr (row_wave) {
     // row stages of the first LA blocks (slots 0 .. LA-1), each after its flag round
 #pragma unroll
     for (int c = 0; c < LA; ++c) {
       if (b0 + c < b1) {
-        wait_landed(std::min<int64_t>(b1 - b0 - 1, NB - 1) - c);
-        bump(flag);
-        spin(flag, 4u * (c + 1));
+        if constexpr (GDMA) {
+          spin(landed(c), 4u);
+        } else {
+          wait_landed(std::min<int64_t>(b1 - b0 - 1, NB - 1) - c);
+          bump(flag);
+          spin(flag, 4u * (c + 1));
+        }
         row_stage_r<P16, FAM, LNK>(lds, c, a, b0 + c, si, lane, s_dev, s_aux);
         bump(ready + c);
       }
@@ -929,43 +1024,85 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
     unsigned rnd = 0;  // uses of slot cur before block blk
 #pragma unroll 1
     for (int64_t blk = b0; blk < b1; ++blk) {
-      if (blk + LA < b1) {  // the row stage of block blk + LA
-        wait_landed(std::min<int64_t>(b1 - 1, blk + NB - 1) - (blk + LA));
-        bump(flag);
-        spin(flag, (unsigned)(4 * (blk + LA - b0 + 1)));
-        int sl = cur + LA;
-        if (sl >= NB) sl -= NB;
-        row_stage_r<P16, FAM, LNK>(lds, sl, a, blk + LA, si, lane, s_dev, s_aux);
-        bump(ready + sl);
-      }
+      auto row_stage_ahead = [&] {
+        if (blk + LA < b1) {  // the row stage of block blk + LA
+          int sl = cur + LA;
+          unsigned rs = rnd;  // uses of slot sl before block blk + LA
+          if (sl >= NB) sl -= NB, ++rs;
+          if constexpr (GDMA) {
+            spin(landed(sl), 4u * (rs + 1));
+            st.lap_h(0, 7);
+          } else {
+            wait_landed(std::min<int64_t>(b1 - 1, blk + NB - 1) - (blk + LA));
+            st.lap_h(0, 7);
+            bump(flag);
+            spin(flag, (unsigned)(4 * (blk + LA - b0 + 1)));
+            st.lap_h(1, 11);
+          }
+          row_stage_r<P16, FAM, LNK>(lds, sl, a, blk + LA, si, lane, s_dev, s_aux);
+          bump(ready + sl);
+          st.lap(2);
+        }
+      };
+      // GDMA: X'Wz first -- done(blk) is what the DMA of block blk + 2 waits for
+      if constexpr (!GDMA) row_stage_ahead();
       // X'Wz of block blk reads every row wave's w*z of it: the flag round above ordered them (each
       // row wave bumps flag after its row stage of blk); the last LA blocks have no such round
-      if (blk + LA >= b1) spin(ready + cur, (unsigned)(RG * (rnd + 1)));
+      // (GDMA: no flag round among the row waves, every block waits for ready)
+      if (GDMA || blk + LA >= b1) spin(ready + cur, (unsigned)(RG * (rnd + 1)));
+      st.lap(3);
       if (do_gram) xz_rows_r<P16, si>(lds, cur, lane, xz);
       bump(done + cur);  // this row wave's reads of block blk (X'Wz) are complete
-      if (blk + NB < b1) {
-        spin(done + cur, 12u * (rnd + 1));
-        stage_block_r<P16>(lds, cur, a, blk + NB, si, voff, vvoff);
-      }
+      st.lap(4);
+      if constexpr (GDMA) row_stage_ahead();
+      if constexpr (!GDMA)
+        if (blk + NB < b1) {
+          spin(done + cur, 12u * (rnd + 1));
+          st.lap(5);
+          stage(cur, blk + NB);
+          st.lap(6);
+        }
+      st.count();
       cur = next_buf(cur);
       if (cur == 0) ++rnd;
     }
   } else {
+    if constexpr (GDMA && issuer) {  // the prologue's blocks
+      wait_vmcnt<0>();
+#pragma unroll
+      for (int k = 0; k < NB; ++k)
+        if (b0 + k < b1) bump(landed(k));
+    }
     int cur = 0;
     unsigned rnd = 0;
 #pragma unroll 1
     for (int64_t blk = b0; blk < b1; ++blk) {
       spin(ready + cur, (unsigned)(RG * (rnd + 1)));
-      if (do_gram) gram_steps_r<P16, WV>(lds, cur, lane, acc);
+      st.lap_h(0, 4);
+      if (do_gram) gram_steps_r<P16, WV>(lds, cur, lane, acc, st);
+      st.lap(1);
       if constexpr (WV == 0)  // the row stage's eta of this block (IRLS passes that keep it)
         if (a.eta_out && a.mode == MODE_IRLS && lane < RB && blk * RB + lane < a.n)
           a.eta_out[blk * RB + lane] = lds[R::OFF_ETA + cur * RB + lane];
       bump(done + cur);
+      st.lap(3);
+      if constexpr (GDMA && issuer)
+        if (blk + NB < b1) {
+          spin(done + cur, 12u * (rnd + 1));
+          st.lap(8);
+          stage(cur, blk + NB);
+          st.lap(9);
+          wait_vmcnt<0>();
+          bump(landed(cur));
+          st.lap(10);
+        }
+      st.count();
       cur = next_buf(cur);
       if (cur == 0) ++rnd;
     }
   }
   if (row_wave) __builtin_amdgcn_s_setprio(0);
+  st.flush(WV, lane);
 
   // ---- epilogue: this workgroup's partial (the layout of K1's) ----
   double* out = a.partials + (int64_t)wg * a.stride;

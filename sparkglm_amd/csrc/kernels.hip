@@ -619,3 +619,12 @@ hipError_t launch_synth(int kind, int64_t row0, int64_t n, int p, uint64_t seed,
 }
 
 }  // namespace sglm
+
+#if SGLM_K1R_STAMPS
+// the stamped development build's cycle sums of the last K1r pass at an even column-block count
+// (fused.hpp StampsR): 12 waves x K1R_STAMP_SLOTS
+extern "C" int sglm_k1r_stamps(unsigned long long* out, int n) {
+  if (n != 12 * sglm::K1R_STAMP_SLOTS || hipDeviceSynchronize() != hipSuccess) return -1;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(sglm::k1r_stamps), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -1;
+}
+#endif
