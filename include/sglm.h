@@ -65,7 +65,8 @@ extern "C" {
                               the group handle at any ndev), SGLM_KERNEL_NARROW_SPLIT retired,
                               sglm_stats.lm_onepass_fits.  Added since, without a version change (new
                               symbols only): sglm_vcov, sglm_influence, sglm_predict_new_se,
-                              sglm_get_influence_ms, enum sglm_resid_type; (new values only:) SGLM_SQRT and
+                              sglm_get_influence_ms, enum sglm_resid_type, sglm_vcov_robust,
+                              sglm_get_sandwich_ms, enum sglm_hc_type; (new values only:) SGLM_SQRT and
                               the non-canonical (family, link) pairs of enum sglm_link's table */
 
 enum sglm_status {
@@ -369,6 +370,26 @@ int sglm_predict_new_se(sglm_engine *h, const double *X, int64_t n, int64_t p, i
 /* Kernel time of the last sglm_influence call on this handle (HIP events; a multi-device handle:
  * its slowest shard; -1 before any call). */
 int sglm_get_influence_ms(sglm_engine *h, double *kernel_ms);
+
+/* ---- heteroskedasticity-consistent ("sandwich") covariance: sandwich::vcovHC types HC0-HC3 ----
+ * V = C M C with the bread C = inv(X'WX) at beta (sglm_vcov's matrix) and the meat
+ * M = sum_i omega_i x_i x_i' over every row of every shard,
+ *   omega_i = u_i^2 / (1 - h_i)^k,  u_i = w_i (y_i - mu_i) g'(mu_i),  h_i = w_i x_i' C x_i,
+ * k = 0 (HC0, HC1), 1 (HC2), 2 (HC3); HC1 multiplies V by n / (n - p), n the global row count (rows of
+ * prior weight 0 included, as vcovHC counts them; their omega is exactly 0).  The dispersion cancels:
+ * V is the final covariance for every family.  Gaussian / identity without prior weights is White's
+ * estimator for LM.  Same scope as the per-row diagnostics (resident, p <= 256; else SGLM_EINVAL before
+ * any launch).  Reads the design three times: sglm_vcov's pass, the score-weight kernel (influence.hip)
+ * and a Gram pass weighted by omega, reduced and all-reduced as every pass -- collective like sglm_vcov.
+ * The resident data and a later fit are unchanged.  A non-finite M or V (a row with leverage 1 under
+ * HC2 / HC3) is SGLM_EINVAL. */
+enum sglm_hc_type { SGLM_HC0 = 0, SGLM_HC1 = 1, SGLM_HC2 = 2, SGLM_HC3 = 3 };
+/* cov [p*p] col-major = C M C (x n/(n-p) for HC1), exactly symmetric; meat [p*p] col-major, may be NULL. */
+int sglm_vcov_robust(sglm_engine *h, const sglm_glm_opts *opts, const double *beta, int hc_type,
+                     double *cov, double *meat);
+/* Kernel times of the last sglm_vcov_robust call: score kernel, meat pass kernel (HIP events; a
+ * multi-device handle: its slowest shard; -1 before any call). */
+int sglm_get_sandwich_ms(sglm_engine *h, double *score_ms, double *meat_ms);
 
 int sglm_get_stats(sglm_engine *h, sglm_stats *out);
 /* The kernel an engine would run a pass of an n x p shard with (enum sglm_pass_kernel, -1 on bad

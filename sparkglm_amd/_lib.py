@@ -36,9 +36,11 @@ EXPORTS = [
     "sglm_predict_glm", "sglm_predict_new", "sglm_local_comm_create", "sglm_local_comm_destroy",
     "sglm_local_comm_rank", "sglm_local_allreduce", "sglm_set_comm_rank", "sglm_pass_kernel_for",
     "sglm_vcov", "sglm_influence", "sglm_predict_new_se", "sglm_get_influence_ms",
+    "sglm_vcov_robust", "sglm_get_sandwich_ms",
 ]
 PREDICT_LINK, PREDICT_RESPONSE = 0, 1
 RESID_TYPES = {"response": 0, "working": 1, "pearson": 2, "deviance": 3}  # enum sglm_resid_type
+HC_TYPES = {"HC0": 0, "HC1": 1, "HC2": 2, "HC3": 3}  # enum sglm_hc_type
 
 dp = C.POINTER(C.c_double)
 
@@ -180,6 +182,8 @@ def load():
         "sglm_influence": ([h, C.POINTER(GlmOpts), dp, C.c_int, C.c_double, dp, dp, dp, dp], C.c_int),
         "sglm_predict_new_se": ([h, dp, C.c_int64, C.c_int64, C.c_int64, dp, C.c_double, dp], C.c_int),
         "sglm_get_influence_ms": ([h, dp], C.c_int),
+        "sglm_vcov_robust": ([h, C.POINTER(GlmOpts), dp, C.c_int, dp, dp], C.c_int),
+        "sglm_get_sandwich_ms": ([h, dp, dp], C.c_int),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("SGLM_LIB") and not hasattr(lib, name):

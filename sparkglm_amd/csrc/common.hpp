@@ -211,12 +211,15 @@ struct InflArgs {
   const double* off;    // may be null
   const double* prior;  // may be null
   int family, link, resid_type;
+  // score_kernel: omega = u^2 / (1 - h)^hc_k, u = w (y - mu) g'(mu), h = w q (hc_k = 0: need_q = 0).
+  // (In the alignment gap before dispersion: the argument block of the other two kernels keeps its layout.)
+  int hc_k;
   double dispersion;    // phi of Cook's distance / of the qform_kernel's sqrt(phi q)
   double* hat;          // outputs [n], any may be null
   double* resid;
   double* cooks;
   double* hpart;        // [grid] per-workgroup sums of h (null: not wanted)
-  // qform_kernel: out[i] = sqrt(max(0, dispersion * q_i))
+  // qform_kernel: out[i] = sqrt(max(0, dispersion * q_i)); score_kernel: out[i] = omega_i
   double* out;
 };
 

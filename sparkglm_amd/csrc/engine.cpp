@@ -1157,8 +1157,15 @@ struct sglm_engine : public Backend {
   int hpart_cap = 0;
   hipEvent_t evi0 = nullptr, evi1 = nullptr;
   double influence_ms = -1.0;                     // kernel time of the last influence call (-1: none yet)
+  // sandwich covariance (sglm_vcov_robust): the score weights omega of the resident rows [n_pad], and
+  // -- only while that call's meat pass runs -- the vector the pass takes for its prior weights
+  double* domega = nullptr;
+  int64_t omega_cap = 0;
+  const double* meat_w = nullptr;
+  double score_ms = -1.0, meat_ms = -1.0;         // kernel times of the last sglm_vcov_robust call (-1: none yet)
   void free_influence() {
-    for (double** ptr : {&dct, &dinf[0], &dinf[1], &dinf[2], &dhpart}) {
+    omega_cap = 0;
+    for (double** ptr : {&dct, &dinf[0], &dinf[1], &dinf[2], &dhpart, &domega}) {
       if (*ptr) (void)hipFree(*ptr);
       *ptr = nullptr;
     }
@@ -1251,6 +1258,61 @@ struct sglm_engine : public Backend {
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, evi0, evi1));
     influence_ms = ms;
+    return SGLM_OK;
+  }
+  // omega_i = u_i^2 / (1 - h_i)^k of this shard's rows at beta against cov (the global C) into domega,
+  // zeros on the padding rows: enqueued on the stream, timed by evi0 / evi1 (score_sync)
+  int score_local(const double* beta, const double* cov, int family, int link, int k) {
+    HIPCHK(hipSetDevice(device));
+    if (int rc = check_loaded()) return rc;
+    if (omega_cap < n_pad) {
+      if (domega) HIPCHK(hipFree(domega));
+      domega = nullptr;
+      omega_cap = 0;
+      if (int rc = dev_alloc(&domega, sizeof(double) * (size_t)n_pad, "hipMalloc(score weights)")) return rc;
+      omega_cap = n_pad;
+    }
+    if (!evi0) HIPCHK(hipEventCreate(&evi0));
+    if (!evi1) HIPCHK(hipEventCreate(&evi1));
+    const int P = (int)((p + 15) / 16);
+    InflArgs a{};
+    a.need_q = k > 0 ? 1 : 0;
+    if (a.need_q)
+      if (int rc = upload_cov(cov, p)) return rc;
+    std::memcpy(hbeta, beta, sizeof(double) * p);
+    HIPCHK(hipMemcpyAsync(dbeta, hbeta, sizeof(double) * p, hipMemcpyHostToDevice, st));
+    a.X = dX;
+    a.ld = n_pad;
+    a.p = (int)p;
+    a.n = n;
+    a.ct = dct;
+    a.beta = dbeta;
+    a.y = dy;
+    a.m = dm;
+    a.off = doff;
+    a.prior = dprior;
+    a.family = family;
+    a.link = link;
+    a.out = domega;
+    a.hc_k = k;
+    // the padding rows of X are zero, but the pass multiplies them by their weight: 0, not what the
+    // allocation held
+    if (n_pad > n) HIPCHK(hipMemsetAsync(domega + n, 0, sizeof(double) * (size_t)(n_pad - n), st));
+    if (n > 0) {
+      HIPCHK(launch_score(P, a, influence_grid(P, ncu, n), st, evi0, evi1));
+    } else {
+      HIPCHK(hipEventRecord(evi0, st));
+      HIPCHK(hipEventRecord(evi1, st));
+    }
+    return SGLM_OK;
+  }
+  // the score kernel is done (the meat pass stages its zero beta in the same pinned buffer): its time
+  int score_sync() {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, evi0, evi1));
+    score_ms = ms;
     return SGLM_OK;
   }
   // out[i] = sqrt(max(0, disp * x_i' cov x_i)) of NEW rows, streamed through predict_new's scratch
@@ -1464,9 +1526,17 @@ struct sglm_engine : public Backend {
     a.stats_in_pass = (narrow && mode == MODE_IRLS && stats_in_pass_family(family, link) &&
                        !(family == FAM_BINOMIAL && dm) &&
                        (family == FAM_BINOMIAL || (dev_only && consts_family == family))) ? 1 : 0;
-    lp_stats = a.stats_in_pass != 0;
-    note_kernel(mode == MODE_LM_GRAM ? FAM_GAUSSIAN : family, mode == MODE_LM_GRAM ? LNK_IDENTITY : link);
-    a.eta_out = (mode == MODE_IRLS && !a.stats_in_pass) ? deta : nullptr;
+    if (meat_w) {
+      // the sandwich's meat X' diag(omega) X (sglm_vcov_robust): a gaussian / identity pass at beta = 0
+      // whose prior weights are omega; nothing of the shard's own vectors but y, no eta store, and the
+      // fit's kernel record (sglm_stats.pass_kernel, pass_has_stats) stays what it was
+      a.prior = meat_w;
+      a.m = a.off = nullptr;
+    } else {
+      lp_stats = a.stats_in_pass != 0;
+      note_kernel(mode == MODE_LM_GRAM ? FAM_GAUSSIAN : family, mode == MODE_LM_GRAM ? LNK_IDENTITY : link);
+    }
+    a.eta_out = (mode == MODE_IRLS && !a.stats_in_pass && !meat_w) ? deta : nullptr;
     a.no_gram = dev_only ? 1 : 0;
     a.fused_split = fused_split;
     a.lm_extras = (mode == MODE_LM_GRAM && narrow && lm_extras_pass) ? 1 : 0;
@@ -2724,6 +2794,117 @@ int sglm_influence(sglm_engine* h, const sglm_glm_opts* opts, const double* beta
   std::vector<double> cov((size_t)(p * p));
   if (int rc = vcov_impl(h, opts, beta, cov.data())) return rc;
   return influence_shards(h, beta, cov.data(), opts, resid_type, dispersion, hat, resid, cooks, sum_hat);
+}
+
+// The score weights of every shard (enqueued on all of them, then awaited); kernel time: the slowest shard.
+static int score_shards(sglm_engine* h, const double* beta, const double* cov, const sglm_glm_opts* opts, int k) {
+  std::vector<sglm_engine*> one{h};
+  const std::vector<sglm_engine*>& shards = h->group() ? h->subs : one;
+  for (sglm_engine* s : shards)
+    if (int rc = s->score_local(beta, cov, opts->family, opts->link, k)) return rc;
+  for (sglm_engine* s : shards) {
+    if (int rc = s->score_sync()) return rc;
+    h->score_ms = s == shards[0] ? s->score_ms : std::max(h->score_ms, s->score_ms);
+  }
+  return SGLM_OK;
+}
+
+namespace {
+// While it lives, the passes of the handle's shards weight their rows by the score weights.
+struct MeatPassScope {
+  std::vector<sglm_engine*> shards;
+  explicit MeatPassScope(sglm_engine* h) {
+    if (h->group()) shards = h->subs;
+    else shards.push_back(h);
+    for (sglm_engine* s : shards) s->meat_w = s->domega;
+  }
+  ~MeatPassScope() {
+    for (sglm_engine* s : shards) s->meat_w = nullptr;
+  }
+};
+}  // namespace
+
+int sglm_vcov_robust(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, int hc_type, double* cov,
+                     double* meat) {
+  if (!opts || !beta || !cov || !family_link_valid(opts->family, opts->link)) {
+    set_error("requirement failed: opts with a supported family/link, beta, cov");
+    return SGLM_EINVAL;
+  }
+  if (hc_type < SGLM_HC0 || hc_type > SGLM_HC3) {
+    set_error("requirement failed: hc_type one of SGLM_HC0, SGLM_HC1, SGLM_HC2, SGLM_HC3 (enum sglm_hc_type)");
+    return SGLM_EINVAL;
+  }
+  if (int rc = check_handle(h)) return rc;
+  if (int rc = check_ready(h)) return rc;
+  // as the per-row diagnostics, whose kernel computes the score weights: refused before any launch
+  auto out_of_scope = [](const sglm_engine* e) { return e->procx.on || e->wide; };
+  bool refuse = !h->group() && out_of_scope(h);
+  for (const sglm_engine* s : h->subs) refuse = refuse || out_of_scope(s);
+  if (refuse) {
+    set_error("requirement failed: the sandwich covariance needs a resident design with p <= " +
+              std::to_string(16 * MAX_P16) + " columns on the fused / narrow path (procedural shards, wider "
+              "designs and SGLM_FORCE_WIDE are not supported)");
+    return SGLM_EINVAL;
+  }
+  const int64_t p = h->ncols();
+  const int k = hc_type == SGLM_HC2 ? 1 : (hc_type == SGLM_HC3 ? 2 : 0);
+  std::vector<double> C((size_t)(p * p)), M((size_t)(p * p)), T((size_t)(p * p)), x((size_t)p);
+  if (int rc = vcov_impl(h, opts, beta, C.data())) return rc;
+  if (int rc = score_shards(h, beta, C.data(), opts, k)) return rc;
+  std::vector<double> packed((size_t)packed_len(p)), zero((size_t)p, 0.0);
+  {
+    MeatPassScope scope(h);
+    if (int rc = h->pass(MODE_IRLS, zero.data(), 0.0, 0.0, FAM_GAUSSIAN, LNK_IDENTITY, packed.data())) return rc;
+  }
+  if (h->group()) {
+    for (size_t d = 0; d < h->subs.size(); ++d)
+      h->meat_ms = d == 0 ? h->subs[d]->last_pass_ms : std::max(h->meat_ms, h->subs[d]->last_pass_ms);
+  } else {
+    h->meat_ms = h->last_pass_ms;
+  }
+  unpack_gram(packed.data(), p, M.data(), x.data());
+  double nrows = (double)(h->group() ? h->g_n : h->n);  // HC1: every row of every shard, weight 0 included
+  if (hc_type == SGLM_HC1 && !h->group())
+    if (int rc = h->allreduce_small(&nrows, 1)) return rc;
+  bool finite = true;
+  for (double v : M) finite = finite && std::isfinite(v);
+  // V = C M C on the host (p <= 256), one triangle of the second product mirrored
+  for (int64_t j = 0; j < p && finite; ++j)
+    for (int64_t i = 0; i < p; ++i) {
+      double s = 0.0;
+      for (int64_t l = 0; l < p; ++l) s += C[(size_t)(i + l * p)] * M[(size_t)(l + j * p)];
+      T[(size_t)(i + j * p)] = s;
+    }
+  const double f = hc_type == SGLM_HC1 ? nrows / (nrows - (double)p) : 1.0;
+  for (int64_t j = 0; j < p && finite; ++j)
+    for (int64_t i = 0; i <= j; ++i) {
+      double s = 0.0, t = 0.0;  // (T C)_ij and (T C)_ji: V = (V + V') / 2
+      for (int64_t l = 0; l < p; ++l) {
+        s += T[(size_t)(i + l * p)] * C[(size_t)(l + j * p)];
+        t += T[(size_t)(j + l * p)] * C[(size_t)(l + i * p)];
+      }
+      const double v = f * (0.5 * (s + t));
+      finite = finite && std::isfinite(v);
+      cov[i + j * p] = cov[j + i * p] = v;
+    }
+  if (!finite) {
+    set_error("requirement failed: the sandwich covariance is not finite (a row with leverage 1 under HC2 / HC3, "
+              "or a row whose mean leaves the family's range at beta)");
+    return SGLM_EINVAL;
+  }
+  if (meat) std::memcpy(meat, M.data(), sizeof(double) * M.size());
+  return SGLM_OK;
+}
+
+int sglm_get_sandwich_ms(sglm_engine* h, double* score_ms, double* meat_ms) {
+  if (int rc = check_handle(h)) return rc;
+  if (!score_ms || !meat_ms) {
+    set_error("requirement failed: score_ms, meat_ms");
+    return SGLM_EINVAL;
+  }
+  *score_ms = h->score_ms;
+  *meat_ms = h->meat_ms;
+  return SGLM_OK;
 }
 
 int sglm_predict_new_se(sglm_engine* h, const double* X, int64_t n, int64_t p, int64_t ldx, const double* cov,

@@ -23,6 +23,10 @@
 // (contiguous in the host's tile order, <= 32 KB) from global memory -- C~ is <= 272 KB and stays in
 // L2 -- prefetched into registers one block column ahead, so the L2 latency hides behind the MFMAs.
 // A workgroup step covers 64 * RS rows; C~ is re-read from L2 once per step.
+//
+// score_kernel is the same body writing one vector, the sandwich covariance's score weights
+//   omega_i = u_i^2 / (1 - h_i)^k,  u_i = w_i (y_i - mu_i) g'(mu_i),  h_i = w_i q_i
+// (k = 0: no MFMA product), which the engine then feeds to a Gram pass as prior weights.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -51,8 +55,13 @@ __device__ __forceinline__ double group_sum(double v) {  // over the four lane g
   return v;
 }
 
-template <int P16, bool ROWS>
+// what the kernel does with a row: the diagnostics at beta, sqrt(phi q) alone, or the sandwich
+// estimator's score weight omega = u^2 / (1 - h)^k
+enum InflMode : int { INFL_ROWS = 0, INFL_QFORM = 1, INFL_SCORE = 2 };
+
+template <int P16, int MODE>
 __device__ __forceinline__ void influence_body(const InflArgs& a) {
+  constexpr bool ROWS = MODE != INFL_QFORM;
   constexpr int RS = infl_rs(P16);
   constexpr int STEP = 16 * RS * INFL_NW;                      // rows per workgroup step
   constexpr int PF = (P16 * INFL_TILE + INFL_NT - 1) / INFL_NT;  // prefetch registers per thread
@@ -175,6 +184,20 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
         continue;
       }
       const double e = eta[r] + (a.off ? a.off[ri] : 0.0);
+      if constexpr (MODE == INFL_SCORE) {
+        // u = w (y - mu) g'(mu): the working weight times the working residual; a row of prior weight
+        // 0 contributes exactly 0 whatever its mu
+        const double pw = a.prior ? a.prior[ri] : 1.0;
+        const InflRow w = influence_row(a.family, a.link, RESID_WORKING, e, a.y[ri], a.m ? a.m[ri] : 1.0, pw);
+        const double u = w.w * w.resid;
+        double om = u * u;
+        if (a.hc_k > 0) {
+          const double d = 1.0 - w.w * q[r];
+          om /= a.hc_k > 1 ? d * d : d;
+        }
+        a.out[ri] = pw == 0.0 ? 0.0 : om;
+        continue;
+      }
       const InflRow w = influence_row(a.family, a.link, a.resid_type, e, a.y[ri], a.m ? a.m[ri] : 1.0,
                                       a.prior ? a.prior[ri] : 1.0);
       const double h = w.w * q[r];
@@ -187,7 +210,7 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
       hsum += h;
     }
   }
-  if (ROWS && a.hpart) {  // lanes, then waves, in a fixed order
+  if (MODE == INFL_ROWS && a.hpart) {  // lanes, then waves, in a fixed order
     hsum += __shfl_xor(hsum, 1);
     hsum += __shfl_xor(hsum, 2);
     hsum += __shfl_xor(hsum, 4);
@@ -204,11 +227,15 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
 
 template <int P16>
 __global__ void __launch_bounds__(INFL_NT, 2) influence_kernel(InflArgs a) {
-  influence_body<P16, true>(a);
+  influence_body<P16, INFL_ROWS>(a);
 }
 template <int P16>
 __global__ void __launch_bounds__(INFL_NT, 2) qform_kernel(InflArgs a) {
-  influence_body<P16, false>(a);
+  influence_body<P16, INFL_QFORM>(a);
+}
+template <int P16>
+__global__ void __launch_bounds__(INFL_NT, 2) score_kernel(InflArgs a) {
+  influence_body<P16, INFL_SCORE>(a);
 }
 
 __global__ void __launch_bounds__(256) influence_sum_kernel(const double* __restrict__ part, int nparts,
@@ -272,6 +299,14 @@ void influence_tiles(const double* C, int p, double* out) {
 hipError_t launch_influence(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
 #define K(N) \
   case N: hipExtLaunchKernelGGL(influence_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
+  INFL_CASES(K)
+#undef K
+  return hipGetLastError();
+}
+
+hipError_t launch_score(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+#define K(N) \
+  case N: hipExtLaunchKernelGGL(score_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
   INFL_CASES(K)
 #undef K
   return hipGetLastError();

@@ -64,6 +64,9 @@ void influence_tiles(const double* C, int p, double* out);
 hipError_t launch_influence(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
                             hipEvent_t e1 = nullptr);
 hipError_t launch_qform(int P16, const InflArgs& a, int grid, hipStream_t st);
+// the sandwich estimator's score weights of the rows < n into a.out (hat / resid / cooks / hpart unused)
+hipError_t launch_score(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
+                        hipEvent_t e1 = nullptr);
 hipError_t launch_influence_sum(const double* part, int nparts, double* out, hipStream_t st);  // fixed order
 
 // wide path (wide.hip)

@@ -695,6 +695,8 @@ __device__ __forceinline__ bool poisson_init_row(const double* c, const double* 
 // (mu = unlink(eta, m)): response y - mu, working (y - mu) g'(mu), Pearson, or deviance
 // sign(y - mu) sqrt(factor * unit_dev) with the family factor the host applies to the deviance sum
 // (driver.cpp family_dev_factor).  Reference-order functions only; out of line like pass_row_ref.
+// The sandwich estimator's score weight (influence.hip score_kernel) is built on the same call: with
+// RESID_WORKING, u = w * resid = w (y - mu) g'(mu) is the row's score contribution per unit of x.
 enum ResidType : int { RESID_RESPONSE = 0, RESID_WORKING = 1, RESID_PEARSON = 2, RESID_DEVIANCE = 3 };
 struct InflRow {
   double w, rp, resid;

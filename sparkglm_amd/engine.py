@@ -361,6 +361,31 @@ class Engine:
                                               float(dispersion), L.ptr(out)), "sglm_predict_new_se")
         return out
 
+    def vcov_robust(self, beta, family="binomial", link="logit", type="HC3", return_meat=False):
+        """Heteroskedasticity-consistent covariance C M C at beta (p x p; sandwich::vcovHC types
+        "HC0".."HC3"): the bread C = vcov(beta), the meat M = X' diag(omega) X from the score-weight
+        kernel and a Gram pass.  It is the final covariance (the dispersion cancels).  With
+        `return_meat` the pair (V, M)."""
+        if type not in L.HC_TYPES:
+            raise L.IllegalArgumentException(f"requirement failed: type must be one of {sorted(L.HC_TYPES)}, "
+                                             f"got {type!r}")
+        o = glm_opts(family, link)
+        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+        if b.shape[0] != self.p:
+            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
+                                             f"beta {b.shape[0]} rows")
+        cov = np.zeros((self.p, self.p), order="F")
+        meat = np.zeros((self.p, self.p), order="F") if return_meat else None
+        L.check(self._lib.sglm_vcov_robust(self._h, C.byref(o), L.ptr(b), L.HC_TYPES[type], cov.ctypes.data_as(L.dp),
+                                           None if meat is None else meat.ctypes.data_as(L.dp)), "sglm_vcov_robust")
+        return (cov, meat) if return_meat else cov
+
+    def sandwich_ms(self):
+        """Kernel times (score kernel, meat pass) of the last vcov_robust() call (HIP events)."""
+        a, b = C.c_double(), C.c_double()
+        L.check(self._lib.sglm_get_sandwich_ms(self._h, C.byref(a), C.byref(b)), "sglm_get_sandwich_ms")
+        return a.value, b.value
+
     def influence_ms(self) -> float:
         """Kernel time of the last influence() call (HIP events)."""
         ms = C.c_double()

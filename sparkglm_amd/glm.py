@@ -200,6 +200,21 @@ def _pre_struct(pre: PreGLM):
     return s, (coefs, se)
 
 
+def _check_cov_type(type):
+    if type != "const" and type not in L.HC_TYPES:
+        raise L.IllegalArgumentException(f"requirement failed: type must be one of "
+                                         f"{['const'] + sorted(L.HC_TYPES)}, got {type!r}")
+
+
+def _coef_table(names, beta, V, pval) -> Frame:
+    """The coeftest columns from a covariance: se = sqrt(diag V), stat = estimate / se, pval(stat)."""
+    est = np.asarray(beta, dtype=np.float64).reshape(-1)
+    se = np.sqrt(np.diag(V))
+    stat = est / se
+    return Frame({"name": list(names), "estimate": est, "se": se, "stat": stat,
+                  "pvalue": np.array([pval(float(t)) for t in stat])})
+
+
 class GLM:
     """Namespace mirroring `object GLM` (GLM.scala:55-1026)."""
 
@@ -278,11 +293,24 @@ class GLM:
 
     @staticmethod
     def vcov(obj: GLMModel, y: Frame, x: Frame, offset: Frame = None, m: Frame = None, prior: Frame = None,
-             device: int = 0) -> np.ndarray:
+             device: int = 0, type: str = "const") -> np.ndarray:
         """Extension: the unscaled covariance inv(X'WX) at the fitted coefficients (R's
-        summary(fit)$cov.unscaled); multiply by the dispersion for vcov(fit)."""
+        summary(fit)$cov.unscaled); multiply by the dispersion for vcov(fit).  `type` "HC0".."HC3":
+        the sandwich covariance (sandwich::vcovHC) instead, which is final -- no dispersion applies."""
+        _check_cov_type(type)
         eng, fam, lnk, beta = GLM._load(obj, y, x, offset, m, prior, device)
-        return eng.vcov(beta, fam, lnk)
+        return eng.vcov(beta, fam, lnk) if type == "const" else eng.vcov_robust(beta, fam, lnk, type=type)
+
+    @staticmethod
+    def coeftest(obj: GLMModel, y: Frame, x: Frame, offset: Frame = None, m: Frame = None, prior: Frame = None,
+                 device: int = 0, type: str = "HC3") -> Frame:
+        """Extension: lmtest::coeftest(fit, vcov. = vcovHC(fit, type)) -- name, estimate, robust
+        standard error sqrt(diag V), z statistic and its two-sided normal p-value."""
+        if type not in L.HC_TYPES:
+            raise L.IllegalArgumentException(f"requirement failed: type must be one of {sorted(L.HC_TYPES)}, "
+                                             f"got {type!r}")
+        eng, fam, lnk, beta = GLM._load(obj, y, x, offset, m, prior, device)
+        return _coef_table(obj.xnames, beta, eng.vcov_robust(beta, fam, lnk, type=type), L.load().sglm_pval_normal)
 
     @staticmethod
     def influence(obj: GLMModel, y: Frame, x: Frame, offset: Frame = None, m: Frame = None, prior: Frame = None,

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib as L
 from .frame import Frame
-from .glm import _engine, _require
+from .glm import _check_cov_type, _coef_table, _engine, _require
 
 
 @dataclass
@@ -169,6 +169,31 @@ class LM:
         eng.set_data(x.select(*obj.xnames).to_matrix(), y.to_vector())
         return eng.influence(np.asarray(obj.coefs, dtype=np.float64).reshape(-1), "gaussian", "identity",
                              resid="response", dispersion=float(obj.sigma) ** 2)
+
+    @staticmethod
+    def vcov(obj: LMModel, x: Frame, y: Frame, device: int = 0, type: str = "const") -> np.ndarray:
+        """Extension: R's vcov(fit) = sigma^2 inv(X'X), or with `type` "HC0".."HC3" the sandwich
+        covariance (sandwich::vcovHC; HC0 is White's estimator) at the fitted coefficients."""
+        _check_cov_type(type)
+        _require(x.count() == y.count(), "The two DataFrames must have the same number of rows")
+        eng = _engine(device)
+        eng.set_data(x.select(*obj.xnames).to_matrix(), y.to_vector())
+        beta = np.asarray(obj.coefs, dtype=np.float64).reshape(-1)
+        if type == "const":
+            return float(obj.sigma) ** 2 * eng.vcov(beta, "gaussian", "identity")
+        return eng.vcov_robust(beta, "gaussian", "identity", type=type)
+
+    @staticmethod
+    def coeftest(obj: LMModel, x: Frame, y: Frame, device: int = 0, type: str = "HC3") -> Frame:
+        """Extension: lmtest::coeftest(fit, vcov. = vcovHC(fit, type)) -- name, estimate, robust
+        standard error, t statistic and its two-sided p-value on n - p degrees of freedom."""
+        if type not in L.HC_TYPES:
+            raise L.IllegalArgumentException(f"requirement failed: type must be one of {sorted(L.HC_TYPES)}, "
+                                             f"got {type!r}")
+        V = LM.vcov(obj, x, y, device=device, type=type)
+        dfe = float(int(obj.nrow) - len(obj.xnames))
+        pval_t = L.load().sglm_pval_t
+        return _coef_table(obj.xnames, obj.coefs, V, lambda t: pval_t(t, dfe))
 
     @staticmethod
     def fit_components(x: Frame, y: Frame, device: int = 0) -> PreLM:
