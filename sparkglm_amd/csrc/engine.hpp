@@ -1,0 +1,359 @@
+// engine.hpp -- the HIP engine behind the C ABI: what its host translation units share.
+// Private to engine.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp and ingest.cpp; never included
+// by a .hip file.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+#include <rocblas/rocblas.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <initializer_list>
+#include <memory>
+#include <string>
+#include <thread>
+#include <utility>
+#include <vector>
+
+#include "../../include/sglm.h"
+#include "common.hpp"
+#include "driver.hpp"
+#include "kernels.hpp"
+
+namespace sglm {
+
+inline std::string hip_msg(hipError_t e, const char* what) {
+  return std::string("HIP error in ") + what + ": " + hipGetErrorString(e);
+}
+
+#define HIPCHK(expr)                                  \
+  do {                                                \
+    hipError_t _e = (expr);                           \
+    if (_e != hipSuccess) {                           \
+      sglm::set_error(sglm::hip_msg(_e, #expr));      \
+      return SGLM_EHIP;                               \
+    }                                                 \
+  } while (0)
+
+// Compensated (Neumaier) accumulation of the scalar partials (host side of rowmath.hpp's
+// neumaier_add): the deviance sum decides the iteration count against an absolute 1e-6.
+inline void neumaier_add(double& s, double& c, double x) {
+  const double t = s + x;
+  c += (std::fabs(s) >= std::fabs(x)) ? (s - t) + x : (x - t) + s;
+  s = t;
+}
+
+inline double now_ms() {
+  using namespace std::chrono;
+  return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+// Cross-rank sums of the NS scalars (deviance, Pearson, loglik ingredients, ...) in rank order
+// with compensation.  The all-reduce buffer carries, after the packed result, one block of
+// `count` slots per rank in which only the owner's block is non-zero, so the all-reduce -- in
+// whatever order RCCL or the caller adds -- delivers every rank's scalars exactly (x + 0 = x),
+// and each rank then sums them itself, in rank order, Neumaier-compensated: the fit's deviance
+// trajectory no longer depends on how many ranks the rows are spread over beyond ~1 ulp.  A plain
+// all-reduce of the deviance adds up to G - 1 uncompensated roundings of up to half an ulp each
+// (2.4e-7 at 1e9 rows, beside GLM.scala:452's absolute tol 1e-6).  The partition-order sum of the
+// reference (GLM.scala:404-407) is the order used here; only the rounding is compensated.
+inline void compensated_rank_sum(const double* blocks, int nranks, int64_t count, double* out) {
+  for (int64_t k = 0; k < count; ++k) {
+    double s = 0.0, c = 0.0;
+    for (int r = 0; r < nranks; ++r) neumaier_add(s, c, blocks[(int64_t)r * count + k]);
+    out[k] = s + c;
+  }
+}
+
+// ---- communicators (comm.cpp) ----
+double comm_timeout_ms_env();  // SGLM_COMM_TIMEOUT_S in ms (default 300 s; 0: unbounded)
+std::string rank_str(int rank);
+// The rank a caller-supplied communicator context stands for, when the engine can tell: the
+// in-process communicator's rank contexts (sglm_local_comm_rank); -1 otherwise.
+int known_rank(sglm_allreduce_fn fn, void* ctx);
+
+// Wait, with a deadline, for the streams whose last work is a collective over `comms`.
+int wait_collective(const std::vector<hipStream_t>& sts, std::vector<ncclComm_t*> comms, double timeout_ms, int rank,
+                    const char* what, const std::vector<hipEvent_t>& starts = {});
+
+// Caller-supplied all-reduce callbacks on a communicator thread owned by the handle, waited for
+// with the deadline.
+class CallbackRunner {
+ public:
+  explicit CallbackRunner(int device = -1) : device_(device) {}
+  ~CallbackRunner();
+  CallbackRunner(const CallbackRunner&) = delete;
+  CallbackRunner& operator=(const CallbackRunner&) = delete;
+
+  bool broken() const { return !broken_msg_.empty(); }
+  // a timed-out device-buffer callback may still write its buffer: the owner must not free it
+  bool leaked_device_buffer() const { return leaked_dev_; }
+  void reset() {  // a new communicator
+    broken_msg_.clear();
+    leaked_dev_ = false;
+  }
+  int call(sglm_allreduce_fn fn, void* ctx, double* buf, int64_t count, void* stream, int on_device, double timeout_ms,
+           int rank);
+
+ private:
+  struct State;
+  void start();
+  int device_;
+  std::shared_ptr<State> st_;
+  std::thread th_;
+  std::string broken_msg_;
+  bool leaked_dev_ = false;
+};
+
+struct Comm {
+  int kind = 0;  // 0 none, 1 callback, 2 rccl
+  sglm_allreduce_fn fn = nullptr;
+  void* ctx = nullptr;
+  int on_device = 0;
+  ncclComm_t nccl = nullptr;
+  int nranks = 1;
+  int rank = -1;  // this handle's rank (RCCL, the in-process communicator, sglm_set_comm_rank); -1 unknown
+  double ms = 0.0;
+  double timeout_ms = 300e3;  // SGLM_COMM_TIMEOUT_S when the communicator was set (0: unbounded)
+};
+
+}  // namespace sglm
+
+// One sglm_engine drives one HIP device (or, as a multi-device handle, routes to its shards'
+// engines).  All state first; the member functions are defined in the file named above each group.
+struct sglm_engine : public sglm::Backend {
+  int device = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+  hipEvent_t evc = nullptr;  // end of the pass's device all-reduce (comm time = ev2 -> evc)
+  hipEvent_t evpre = nullptr;  // before a small RCCL all-reduce: where its deadline starts
+  int ncu = 256;
+
+  // ---- resident shard ----
+  int64_t n = 0, p = 0, n_pad = 0, nblocks = 0;
+  double *dX = nullptr, *dy = nullptr, *dm = nullptr, *doff = nullptr, *dprior = nullptr, *deta = nullptr;
+  // procedural shard (sglm_synth_procedural): X regenerated in the wide kernels, not stored
+  sglm::ProcX procx{};
+
+  // ---- pass workspace ----
+  int P16 = 0, grid = 0;
+  int64_t stride = 0;
+  double *dbeta = nullptr, *dpart = nullptr, *dred = nullptr, *dsmall = nullptr;
+  double *hbeta = nullptr, *hred = nullptr;
+  double* hsmall = nullptr;  // pinned [64]: the final statistics' sums (stats)
+  int64_t part_cap = 0, red_cap = 0, dsmall_cap = 0;
+  sglm::Comm comm;
+  std::unique_ptr<sglm::CallbackRunner> cbr;  // caller callbacks with a deadline (CallbackRunner)
+  bool red_on_device = false;  // dred holds the all-reduced result of the last pass
+  bool lp_stats = false;       // the last pass carried the final statistics (PassArgs::stats_in_pass)
+  double stats_const = 0.0;    // the fit's initial-pass S_AUX2: constant part of in-pass Poisson / Gamma statistics
+  int consts_family = -1;      // family whose initial pass produced stats_const on this data (-1: none)
+  // deviance-only passes (Backend::pass_dev): the next enqueue_pass runs the row stage and the
+  // scalar reduction but no Gram -- bitwise the scalars of the full pass.  SGLM_SPECULATE=0 off.
+  bool dev_only = false, allow_spec = true;
+  // narrow path (narrow.hip, p <= 64): barrier-free per-wave pipelines
+  bool narrow = false;
+  int fused_split = 1;  // SGLM_FUSED_SPLIT: 1 K1r from its default column-block count up, 0 never (K1), N >= 2 from P16 = N
+  bool allow_lm_device = true;  // SGLM_LM_DEVICE=0: LM fits take the two host round trips (tests)
+  bool lm_extras_pass = false;  // the next LM Gram pass also sums X'1 and y'y (lm_device, one pass)
+
+  // ---- wide path (wide.hip; wide_path.cpp) ----
+  bool wide = false, force_wide = false;
+  // procedural shards in chunks (setup_proc_chunks): each pass generates C rows of X at a time
+  // into an HBM scratch (the row kernel, while it forms eta) and runs the resident Gram kernels
+  // over it -- X is generated once per pass instead of once per super-tile that reads it
+  int64_t ch_rows = 0;  // rows per chunk (multiple of 32); 0: in-kernel generation (PROC kernels)
+  int nch = 0;
+  double *dxsc = nullptr, *dchunks = nullptr;
+  bool allow_chunks = true;  // SGLM_PROC_CHUNKS=0 disables
+  // SGLM_PROC_OVERLAP: chunks of an overlapped procedural pass (<= 1: one buffer, serial).  Round 2
+  // measured it slower beside both Gram launches (250M x 512 logit: 1257 ms per pass serial, 1420 /
+  // 1480 at 8 / 16 chunks -- the generator's integer + fp64 VALU slowed the Gram by 31-38 %).  Round 5
+  // (VERDICT r4 item 6): gated to the off-diagonal launches (then SGLM_PROC_OV_GATE; the diagonal launch
+  // goes first) and the generating row kernel at raised priority, 8 chunks: 1284.5 -> 1266.9 ms on one
+  // box (ungated 1466.3, gated at normal priority 1285.7).  Round 5 then split the
+  // generator off (proc_gen_kernel, 48 VGPRs) and let it start beside each chunk's diagonal launch,
+  // which goes first; round 6 measured the other launch orders +4.5 % (generator held until the
+  // diagonal launch is done) and +5.5 % (off-diagonal launch first) and retired them.
+  int proc_ov_want = 8;
+  bool proc_ov = false;      // double-buffered scratch, row kernels on st2 (as the resident overlap below)
+  int64_t proc_ov_min = (int64_t)1 << 20;  // SGLM_PROC_OV_MIN: fewest rows per overlapped chunk
+  int64_t proc_scratch_max = 0;  // SGLM_PROC_SCRATCH_MAX (GiB): cap on the procedural chunk scratch (0: none)
+  // resident wide shards, overlapped passes: the rows are cut into nov chunks; the row kernel of
+  // chunk c + 1 runs on a second stream (st2) beside the Gram kernels of chunk c, so only chunk 0's
+  // row stage is exposed.  Each chunk is reduced into dchunks[c]; the chunks are summed in order.
+  int ov_want = 16;                // SGLM_WIDE_OVERLAP: chunks per pass (<= 1: off)
+  int64_t ov_min = (int64_t)1 << 16;  // SGLM_WIDE_OV_MIN: fewest rows per chunk (fewer chunks on small shards)
+  int nov = 0;
+  int64_t ov_rows = 0;             // rows per chunk (multiple of 32; the last chunk may be shorter)
+  int rgrid_ov = 0;                // row-kernel grid of chunks >= 1 (one workgroup per CU)
+  hipStream_t st2 = nullptr;
+  // events of a chunked pass (nch or nov chunks, never both): [4 c .. 4 c + 3] row span and Gram span
+  // of chunk c, [4 * chunks()] the st -> st2 fork
+  std::vector<hipEvent_t> evchunk;
+  double *dw = nullptr, *dwz = nullptr, *dgp = nullptr, *drp = nullptr;
+  int64_t gp_cap = 0, rp_cap = 0, wstride = 0;
+  int npan = 0, nst = 0, nslots = 0, ggrid = 0, rgrid = 0;
+  int ggk[2] = {0, 0};  // persistent grid of the off-diagonal / diagonal Gram kernels
+  sglm::WidePiece* dpieces[2] = {nullptr, nullptr};  // [0] off-diagonal, [1] diagonal super-tiles
+  int* dwgb[2] = {nullptr, nullptr};
+  int* dstr = nullptr;                          // [nst][2] partial slot range per super-tile
+  bool has_sched[2] = {false, false};
+  hipEvent_t evm = nullptr;
+  rocblas_handle blas = nullptr;
+  // wide-path device solve (SGLM_WIDE_SOLVE): 0 Cholesky (potrf / potrs / potri, the default),
+  // 1 LU + explicit inverse (Breeze inv's algorithm: dgetrf + dgetri, utils.scala:103-105)
+  int wide_lu = 0;
+
+  // ---- ingest (sglm_reserve / sglm_set_rows; ingest.cpp): two pinned staging buffers, double-buffered ----
+  static constexpr int64_t STAGE_DOUBLES = (int64_t)8 << 20;  // 64 MiB each
+  double* hstage[2] = {nullptr, nullptr};
+  hipEvent_t evstage[2] = {nullptr, nullptr};
+  int stage_k = 0;
+  int64_t rows_loaded = 0;  // rows covered by the blocks written since the shard was reserved
+  std::vector<std::pair<int64_t, int64_t>> written;  // those blocks' row ranges, disjoint, sorted
+  double load_ms = 0.0;     // host wall time in set_data / set_rows (staging + H2D)
+  int64_t load_bytes = 0;
+
+  // ---- scoring scratch: new rows (sglm_predict_new, sglm_predict_new_se), separate from the resident shard ----
+  double *dxs = nullptr, *dvs = nullptr, *dms = nullptr, *dos = nullptr;
+  int64_t xs_cap = 0, vs_cap = 0;
+
+  // ---- diagnostics (influence.hip; diagnostics.cpp): leverage, residuals, Cook's distance, se.fit ----
+  double *dct = nullptr, *hct = nullptr;          // C~ tiles: device / pinned [MAX_P16 (MAX_P16 + 1) / 2][INFL_TILE]
+  double* dinf[3] = {nullptr, nullptr, nullptr};  // hat, resid, cooks of the resident rows, allocated when first asked for
+  int64_t inf_cap[3] = {0, 0, 0};
+  double* dhpart = nullptr;                       // per-workgroup sums of h, then their sum
+  int64_t hpart_cap = 0;
+  hipEvent_t evi0 = nullptr, evi1 = nullptr;
+  double influence_ms = -1.0;                     // kernel time of the last influence call (-1: none yet)
+  // sandwich covariance (sglm_vcov_robust): the score weights omega of the resident rows [n_pad], and
+  // -- only while that call's meat pass runs -- the vector the pass takes for its prior weights
+  double* domega = nullptr;
+  int64_t omega_cap = 0;
+  const double* meat_w = nullptr;
+  double score_ms = -1.0, meat_ms = -1.0;         // kernel times of the last sglm_vcov_robust call (-1: none yet)
+
+  // ---- group: single-process multi-device handle (sglm_create_multi): the shards' engines; this
+  // handle then only routes and reduces (one process owns all GPUs, as SURVEY 8(b) asks) ----
+  std::vector<sglm_engine*> subs;
+  std::vector<sglm_engine*> self{this};  // shards() of a single-device handle
+  std::vector<int64_t> sub_lo;       // first global row of each shard
+  std::vector<ncclComm_t> gcomms;    // ncclCommInitAll over distinct devices (else host sums)
+  bool group_aborted = false;        // a group all-reduce missed its deadline (wait_collective)
+  int64_t g_n = 0;                   // group: total rows
+
+  // ---- stats ----
+  int64_t passes = 0, dev_passes = 0;
+  double pass_ms = 0.0, reduce_ms = 0.0, last_pass_ms = 0.0, last_reduce_ms = 0.0, row_ms = 0.0, gram_ms = 0.0;
+  // LM fits keep their own last timing (pass_untimed): another pass kind in between must not be booked as LM time
+  double lm_last_pass_ms = -1.0, lm_last_reduce_ms = 0.0;
+  int64_t lm_device_fits = 0;
+  int64_t lm_onepass_fits = 0;  // of those, fits whose statistics came from the Gram pass's sums
+  int last_kernel = SGLM_KERNEL_NONE;  // the kernel of the last pass (enum sglm_pass_kernel) and its name
+  char last_kernel_name[64] = "";
+
+  // ---- accessors ----
+  bool group() const { return !subs.empty(); }
+  // the engines that hold this handle's rows: a group's shards, else the handle itself
+  const std::vector<sglm_engine*>& shards() const { return group() ? subs : self; }
+  int64_t ncols() const override { return group() ? subs[0]->p : p; }
+  bool pass_has_stats() const override { return group() ? subs[0]->lp_stats : lp_stats; }
+  int npart() const override { return group() ? (int)subs.size() : comm.nranks; }
+  bool has_dev_pass() const override { return allow_spec; }
+  bool comm_on_device() const { return comm.kind == 2 || (comm.kind == 1 && comm.on_device); }
+  // scalars summed across ranks through rank blocks (compensated_rank_sum): needs >1 rank and a
+  // known own rank; otherwise the communicator's plain sum
+  bool gather_ranks() const { return comm.kind != 0 && comm.nranks > 1 && comm.rank >= 0 && comm.rank < comm.nranks; }
+  // chunks of a chunked wide pass (resident overlapped, or procedural), 0 if the pass is not chunked
+  int chunks() const { return nov > 0 ? nov : nch; }
+  // chunks whose row kernels run beside the Gram (resident or procedural), 0 if none
+  int ov_chunks() const { return nov > 1 ? nov : (proc_ov ? nch : 0); }
+
+  // ---- engine.cpp: lifetime, workspace, passes ----
+  ~sglm_engine() override;
+  void free_data();
+  void release();
+  int alloc_data(int64_t n_, int64_t p_, bool has_m, bool has_off, bool has_prior, bool proc = false);
+  int ensure_workspace();
+  int ensure_red_len(int64_t len);  // dred / hred / dbeta / hbeta hold at least len doubles
+  int ensure_small(int64_t count);
+  // hipMalloc that reports SGLM_ENOMEM and names the buffer
+  static int dev_alloc(double** ptr, size_t bytes, const char* what);
+  // a grow-only device buffer of doubles: at least `need` afterwards, the old contents not kept
+  static int grow(double*& ptr, int64_t& cap, int64_t need, const char* what);
+  static void dev_free(std::initializer_list<double**> ptrs);  // hipFree and null each
+  int global_sums(double* out2) override;
+  int pass_dev(int mode, const double* beta, double mu0, double ybar, int family, int link, double* packed) override;
+  int pass(int mode, const double* beta, double mu0, double ybar, int family, int link, double* packed) override;
+  void finish_scalars(int mode, int family, double* s);
+  int pass_timing();
+  void pass_untimed();
+  int enqueue_pass(int mode, const double* beta, double mu0, double ybar, int family, int link, bool timed = true);
+  void note_kernel(int family, int link);
+  int group_pass(int mode, const double* beta, double mu0, double ybar, int family, int link, double* packed);
+  int lm_device(double* packed, double* dev_coefs, double* s, bool& done) override;
+  int stats(int mode, const double* beta, double mu0, double ybar, int family, int link, double* s) override;
+
+  // ---- comm.cpp: the communicator ----
+  sglm::CallbackRunner& runner();
+  void leak_comm_buffers();
+  int call_comm(double* buf, int64_t count, int on_device);
+  int allreduce_device(double* dbuf, int64_t count, bool after_pass = false);
+  int allreduce_host(double* hbuf, int64_t count);
+  int allreduce_small(double* h, int64_t count);
+  int stage_rank_block(int r, int nr);
+
+  // ---- wide_path.cpp: schedules, workspace, the wide pass, the device solver ----
+  void free_schedule();
+  bool banded_kind(int S, int64_t nb, int G) const;
+  int build_wide_schedule();
+  int ensure_chunk_events(int nc);
+  int ensure_wide_workspace();
+  int setup_proc_chunks();
+  double* rowpart(int c) const;
+  int launch_grams(sglm::WideGramArgs& g, bool diag_first);
+  int enqueue_wide(int mode, bool has_beta, double mu0, double ybar, int family, int link);
+  int wide_timing(float k1);
+  std::unique_ptr<sglm::SolverIface> make_solver(int64_t pp) override;
+  int blas_handle();
+
+  // ---- ingest.cpp: host rows in, scores of new rows out ----
+  int ensure_staging();
+  int h2d_block(double* dst, int64_t dld, const double* src, int64_t sld, int64_t rows, int64_t cols);
+  int set_rows(int64_t row0, int64_t nr, const double* X, int64_t ldx, const double* yv, const double* mv,
+               const double* ov, const double* pv);
+  int check_loaded() const;
+  int ensure_new_rows(int64_t pp, int64_t chunk);
+  int predict_new(const double* X, int64_t nn, int64_t pp, int64_t ldx, const double* beta, const double* off,
+                  const double* mv, int family, int link, int type, double* out);
+
+  // ---- diagnostics.cpp ----
+  void free_influence();
+  int upload_cov(const double* cov, int64_t pp);
+  int influence_local(const double* beta, const double* cov, int family, int link, int rtype, double disp, double* hat,
+                      double* resid, double* cooks, double* sum_hat);
+  int score_local(const double* beta, const double* cov, int family, int link, int k);
+  int score_sync();
+  int predict_new_se(const double* X, int64_t nn, int64_t pp, int64_t ldx, const double* cov, double disp, double* out);
+};
+
+namespace sglm {
+
+inline int check_handle(sglm_engine* h) {
+  if (!h) {
+    set_error("requirement failed: null engine handle");
+    return SGLM_EINVAL;
+  }
+  return SGLM_OK;
+}
+
+// The handle holds a complete design: every reserved row written (or generated).
+inline int check_ready(sglm_engine* h) {
+  for (sglm_engine* s : h->shards())
+    if (int rc = s->check_loaded()) return rc;
+  return SGLM_OK;
+}
+
+}  // namespace sglm

@@ -320,7 +320,7 @@ __device__ void offdiag_piece(double* lds, const WideGramArgs& a, int I, int J, 
 
 // Persistent Gram kernels (one for the off-diagonal, one for the diagonal super-tiles, so
 // each gets the whole register file): workgroup g runs the pieces [wg_begin[g],
-// wg_begin[g+1]) of the cost-balanced schedule built on the host (engine.cpp).
+// wg_begin[g+1]) of the cost-balanced schedule built on the host (wide_path.cpp).
 template <bool DIAG, bool PROC>
 __global__ void __launch_bounds__(64 * NWAVE, DIAG ? DIAG_WG : 2) wide_gram_kernel(WideGramArgs a) {
   __shared__ double lds[DIAG ? LDS_DIAG : LDS_DOUBLES];
@@ -490,7 +490,7 @@ __global__ void __launch_bounds__(256) wide_rows_kernel(WideRowArgs a) {
   wide_rows_body<FAM, LNK, 4>(a);
 }
 
-// The same row stage for the overlapped chunks (engine.cpp enqueue_pass): one workgroup per CU
+// The same row stage for the overlapped chunks (wide_path.cpp enqueue_wide): one workgroup per CU
 // beside the two persistent Gram workgroups, so at most 96 VGPRs (2 x 208 + 96 = the SIMD's
 // 512) and two rows per thread (no spills at that budget).  Per-row arithmetic and order are the
 // full kernel's, bit for bit.  Non-temporal X loads keep the Gram's rows in the caches.
@@ -513,7 +513,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) w
   wide_rows_body<FAM, LNK, 2, true>(a);
 }
 
-// Procedural chunks >= 1, the generator on its own (engine.cpp enqueue_pass): X rows [r_begin, r_end)
+// Procedural chunks >= 1, the generator on its own (wide_path.cpp enqueue_wide): X rows [r_begin, r_end)
 // into the scratch and X beta into eta_raw, a thread per row, nothing else -- so that it fits in 48
 // VGPRs and two waves per SIMD run beside the two 208-VGPR off-diagonal Gram workgroups (the
 // generating wide_rows_ov_kernel, with the family arithmetic in it, holds 87 VGPRs: one wave).  The

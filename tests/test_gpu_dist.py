@@ -1,7 +1,7 @@
 """Multi-rank GPU paths on one MI355X: rank processes sharing the device with the engine's
 host all-reduce over gloo, the native RCCL communicator, torch's RCCL ("nccl") group through
 the device-buffer callback -- and, at world 2 and 4, the DEVICE-buffer all-reduce path
-(stage_rank_block + the rank blocks of the packed buffer in HBM, engine.cpp) over a gloo group
+(stage_rank_block + the rank blocks of the packed buffer in HBM, comm.cpp) over a gloo group
 of CUDA tensors: the buffers and the staging an RCCL communicator carries across GPUs, exercised
 with several ranks before an 8-GPU node runs them (utils.scala:110-126, GLM.scala:404-407)."""
 import os

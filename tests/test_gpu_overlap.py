@@ -1,4 +1,4 @@
-"""Overlapped wide passes (engine.cpp enqueue_pass, resident X, p > 256): the rows are cut into
+"""Overlapped wide passes (wide_path.cpp enqueue_wide, resident X, p > 256): the rows are cut into
 chunks; the row kernel of chunk c + 1 (eta = X beta + offset, zwCreate: GLM.scala:321-395) runs
 on a second stream beside the Gram kernels of chunk c (partitionComponents / wlsComponents,
 utils.scala:84-126), each chunk is reduced on its own and the chunks are summed in order -- the

@@ -1,4 +1,4 @@
-"""Register budgets the overlapped wide pass relies on (engine.cpp enqueue_pass, wide.hip): the
+"""Register budgets the overlapped wide pass relies on (wide_path.cpp enqueue_wide, wide.hip): the
 two persistent Gram workgroups of a CU and one overlapped row-kernel workgroup must fit one
 SIMD's 512 VGPRs together, or the row kernel's workgroups take Gram slots and the chunk's Gram
 runs in two rounds (measured: logit512r Gram 280 -> 320 ms when a change pushed the off-diagonal
