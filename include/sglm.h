@@ -66,7 +66,8 @@ extern "C" {
                               sglm_stats.lm_onepass_fits.  Added since, without a version change (new
                               symbols only): sglm_vcov, sglm_influence, sglm_predict_new_se,
                               sglm_get_influence_ms, enum sglm_resid_type, sglm_vcov_robust,
-                              sglm_get_sandwich_ms, enum sglm_hc_type; (new values only:) SGLM_SQRT and
+                              sglm_get_sandwich_ms, enum sglm_hc_type, sglm_set_clusters, sglm_vcov_cluster,
+                              sglm_get_cluster_ms, sglm_cluster_plan; (new values only:) SGLM_SQRT and
                               the non-canonical (family, link) pairs of enum sglm_link's table */
 
 enum sglm_status {
@@ -390,6 +391,44 @@ int sglm_vcov_robust(sglm_engine *h, const sglm_glm_opts *opts, const double *be
 /* Kernel times of the last sglm_vcov_robust call: score kernel, meat pass kernel (HIP events; a
  * multi-device handle: its slowest shard; -1 before any call). */
 int sglm_get_sandwich_ms(sglm_engine *h, double *score_ms, double *meat_ms);
+
+/* ---- cluster-robust covariance: sandwich::vcovCL(fit, cluster = ~id), Stata's vce(cluster id) ----
+ * V = a C M C with the bread C of the sandwich above and the meat M = S'S, S [G x p] the cluster sums
+ *   S[g, :] = sum_{i: id_i = g} u_i x_i      over every row of every shard,
+ * u_i the signed score of the sandwich (exactly 0 where the prior weight is 0).  The adjustment a:
+ * hc_type SGLM_HC0 none, SGLM_HC1 (n - 1) / (n - p) -- vcovCL's HC1, not vcovHC's n / (n - p); n the global
+ * row count, rows of weight 0 included -- and with cadjust != 0 a further G / (G - 1).  HC1 with cadjust is
+ * vcovCL's default and Stata's regress, vce(cluster); HC0 with cadjust Stata's glm / ML rule.  HC2 / HC3
+ * (per-cluster leverage blocks) are SGLM_EINVAL.  Scope: that of sglm_vcov_robust.
+ *
+ * sglm_set_clusters declares the cluster of every resident row: dense codes 0 <= ids[i] < G, n_local = the
+ * handle's resident rows (a multi-device handle: all its rows, in row order).  Local, not collective.  A
+ * code without rows is allowed (its row of S is 0; it still counts in G).  ids = NULL clears.  A code out
+ * of range, another n_local, or no data loaded: SGLM_EINVAL.  Any call that replaces the resident data
+ * (sglm_set_data*, sglm_reserve, sglm_synth*) drops the clusters.  The engine cuts the rows into segments
+ * (sglm_cluster_plan) and keeps nseg x p doubles for their sums: rows sorted by cluster, the usual panel
+ * layout, give nseg ~ G + n / tile_rows, fully interleaved ids nseg = n -- SGLM_ENOMEM if that does not fit.
+ *
+ * sglm_vcov_cluster is collective, like sglm_vcov_robust: clusters may span shards and ranks, S is summed
+ * over them through the handle's communicator -- G * p doubles per call (G rounded up to 32), beside the
+ * p (p + 1) / 2 of the bread's pass -- and every rank then forms the same M.  Every rank must have declared
+ * the same G (checked with one small all-reduce; else SGLM_EINVAL on every rank).  Also SGLM_EINVAL: no
+ * clusters set, cadjust with G < 2, a non-finite M or V.  No floating-point atomics: results are run-to-run
+ * bitwise identical, the order of every sum depends on (ids, n, p) only.  The resident data and a later fit
+ * are unchanged.  cov [p*p] col-major, exactly symmetric; meat [p*p] col-major, may be NULL. */
+int sglm_set_clusters(sglm_engine *h, const int32_t *ids, int64_t n_local, int32_t G);
+int sglm_vcov_cluster(sglm_engine *h, const sglm_glm_opts *opts, const double *beta, int hc_type, int cadjust,
+                      double *cov, double *meat);
+/* Kernel times of the last sglm_vcov_cluster call: score kernel, segment sums, combine, the meat's Gram pass
+ * (HIP events; a multi-device handle: its slowest shard; -1 before any call). */
+int sglm_get_cluster_ms(sglm_engine *h, double *score_ms, double *sum_ms, double *combine_ms, double *gram_ms);
+/* The engine's segmentation of n rows with cluster codes ids (no device is touched): a segment is a
+ * maximal run of consecutive rows with one code, additionally cut at every multiple of *tile_rows (a
+ * compile-time constant), so nseg <= runs + ceil(n / tile_rows) and no segment crosses a tile.  seg_start
+ * [nseg + 1] (the last entry is n) and seg_cluster [nseg]; either may be NULL (query *nseg first).  A code
+ * outside [0, G) is SGLM_EINVAL. */
+int sglm_cluster_plan(const int32_t *ids, int64_t n, int32_t G, int64_t *tile_rows, int64_t *nseg,
+                      int64_t *seg_start, int32_t *seg_cluster);
 
 int sglm_get_stats(sglm_engine *h, sglm_stats *out);
 /* The kernel an engine would run a pass of an n x p shard with (enum sglm_pass_kernel, -1 on bad

@@ -37,6 +37,7 @@ EXPORTS = [
     "sglm_local_comm_rank", "sglm_local_allreduce", "sglm_set_comm_rank", "sglm_pass_kernel_for",
     "sglm_vcov", "sglm_influence", "sglm_predict_new_se", "sglm_get_influence_ms",
     "sglm_vcov_robust", "sglm_get_sandwich_ms",
+    "sglm_set_clusters", "sglm_vcov_cluster", "sglm_get_cluster_ms", "sglm_cluster_plan",
 ]
 PREDICT_LINK, PREDICT_RESPONSE = 0, 1
 RESID_TYPES = {"response": 0, "working": 1, "pearson": 2, "deviance": 3}  # enum sglm_resid_type
@@ -184,6 +185,11 @@ def load():
         "sglm_get_influence_ms": ([h, dp], C.c_int),
         "sglm_vcov_robust": ([h, C.POINTER(GlmOpts), dp, C.c_int, dp, dp], C.c_int),
         "sglm_get_sandwich_ms": ([h, dp, dp], C.c_int),
+        "sglm_set_clusters": ([h, C.POINTER(C.c_int32), C.c_int64, C.c_int32], C.c_int),
+        "sglm_vcov_cluster": ([h, C.POINTER(GlmOpts), dp, C.c_int, C.c_int, dp, dp], C.c_int),
+        "sglm_get_cluster_ms": ([h, dp, dp, dp, dp], C.c_int),
+        "sglm_cluster_plan": ([C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int64),
+                               C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("SGLM_LIB") and not hasattr(lib, name):
@@ -204,6 +210,25 @@ def pass_kernel_for(n: int, p: int, family: str = "binomial", link: str = "logit
     if k < 0:
         raise IllegalArgumentException(last_error())
     return PASS_KERNELS[k], buf.value.decode()
+
+
+CLUSTER_TYPES = ("HC0", "HC1")  # the adjustments sglm_vcov_cluster takes (sandwich::vcovCL)
+
+
+def cluster_plan(ids, G: int):
+    """(tile_rows, seg_start [nseg + 1], seg_cluster [nseg]): the engine's segmentation of rows with
+    dense cluster codes `ids` (sglm_cluster_plan; no GPU)."""
+    import numpy as np
+    ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    n = ids.shape[0]
+    lib = load()
+    ip = ids.ctypes.data_as(C.POINTER(C.c_int32)) if n else None
+    tile, nseg = C.c_int64(), C.c_int64()
+    check(lib.sglm_cluster_plan(ip, n, int(G), C.byref(tile), C.byref(nseg), None, None), "sglm_cluster_plan")
+    start, clus = np.zeros(nseg.value + 1, dtype=np.int64), np.zeros(nseg.value, dtype=np.int32)
+    check(lib.sglm_cluster_plan(ip, n, int(G), None, None, start.ctypes.data_as(C.POINTER(C.c_int64)),
+                                clus.ctypes.data_as(C.POINTER(C.c_int32))), "sglm_cluster_plan")
+    return tile.value, start, clus
 
 
 def last_error() -> str:

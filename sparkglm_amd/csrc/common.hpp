@@ -223,6 +223,36 @@ struct InflArgs {
   double* out;
 };
 
+// Cluster sums S[g, :] = sum_{i: id_i = g} u_i x_i (cluster.hip).  A segment is a
+// maximal run of consecutive rows with one id, cut at every multiple of CLUSTER_TILE_ROWS.
+constexpr int CLUSTER_TILE_ROWS = 128;
+struct ClusterArgs {
+  const double* X;           // col-major, leading dimension ld (a multiple of 32, rows >= n zero)
+  int64_t ld;
+  int p;
+  int64_t n;
+  const double* u;           // [ld] signed scores, zero on the rows >= n
+  const int64_t* seg_start;  // [nseg + 2]: first row of each segment, n, and a sentinel past every row
+  const int64_t* tile_seg;   // [ntiles + 1]: first segment of each row tile
+  int64_t ntiles;
+  double* R;                 // [nseg][p] segment sums
+};
+// One level of the combine: chunk k sums the rows in[idx[q]] (idx null: in[q]), q in [chunk_start[k],
+// chunk_start[k + 1]), in that order, into S[g, :] (chunk_dst[k] = g >= 0: the whole of cluster g) or
+// into row -(chunk_dst[k] + 1) of out (one of several chunks of a cluster: the next level's input).
+struct CombineArgs {
+  const double* in;          // rows of p doubles
+  const int64_t* idx;
+  const int64_t* chunk_start;  // [nchunk + 1]
+  const int64_t* chunk_dst;    // [nchunk]
+  int64_t nchunk;
+  int p;
+  double* S;                 // col-major G x p, leading dimension ldS
+  int64_t ldS;
+  double* out;
+};
+constexpr int CLUSTER_CHUNK = 64;  // rows one thread of the combine adds
+
 // Arguments of the final-statistics pass (stats_kernel).
 struct StatsArgs {
   const double* y;

@@ -160,7 +160,7 @@ int sglm_engine::predict_new_se(const double* X, int64_t nn, int64_t pp, int64_t
 
 // inv(X'WX) at beta: the pass of sglm_irls_pass (collective over a communicator) and the engine's
 // solve rule (Cholesky, or the LU inverse below LU_SWITCH_RATIO; SGLM_ESINGULAR as the fit).
-static int vcov_impl(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, double* cov) {
+int sglm::vcov_impl(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, double* cov) {
   const int64_t p = h->ncols();
   std::vector<double> packed((size_t)packed_len(p)), x((size_t)p);
   int rc = h->pass(MODE_IRLS, beta, 0.0, 0.0, opts->family, opts->link, packed.data());
@@ -180,7 +180,7 @@ static int vcov_impl(sglm_engine* h, const sglm_glm_opts* opts, const double* be
 
 // The row kernel covers resident designs on the fused / narrow paths' range only: anything else is
 // refused before any launch.  `what`: the caller's subject and verb ("per-row diagnostics need").
-static int require_fused_or_narrow(const sglm_engine* h, const char* what) {
+int sglm::require_fused_or_narrow(const sglm_engine* h, const char* what) {
   bool refuse = false;
   for (const sglm_engine* s : h->shards()) refuse = refuse || s->procx.on || s->wide;
   if (!refuse) return SGLM_OK;
@@ -188,6 +188,32 @@ static int require_fused_or_narrow(const sglm_engine* h, const char* what) {
             std::to_string(16 * MAX_P16) + " columns on the fused / narrow path (procedural shards, wider "
             "designs and SGLM_FORCE_WIDE are not supported)");
   return SGLM_EINVAL;
+}
+
+// V = f C M C on the host (p <= 256), one triangle of the second product mirrored
+bool sglm::sandwich_product(const std::vector<double>& C, const std::vector<double>& M, int64_t p, double f,
+                            double* cov) {
+  std::vector<double> T((size_t)(p * p));
+  bool finite = true;
+  for (double v : M) finite = finite && std::isfinite(v);
+  for (int64_t j = 0; j < p && finite; ++j)
+    for (int64_t i = 0; i < p; ++i) {
+      double s = 0.0;
+      for (int64_t l = 0; l < p; ++l) s += C[(size_t)(i + l * p)] * M[(size_t)(l + j * p)];
+      T[(size_t)(i + j * p)] = s;
+    }
+  for (int64_t j = 0; j < p && finite; ++j)
+    for (int64_t i = 0; i <= j; ++i) {
+      double s = 0.0, t = 0.0;  // (T C)_ij and (T C)_ji: V = (V + V') / 2
+      for (int64_t l = 0; l < p; ++l) {
+        s += T[(size_t)(i + l * p)] * C[(size_t)(l + j * p)];
+        t += T[(size_t)(j + l * p)] * C[(size_t)(l + i * p)];
+      }
+      const double v = f * (0.5 * (s + t));
+      finite = finite && std::isfinite(v);
+      cov[i + j * p] = cov[j + i * p] = v;
+    }
+  return finite;
 }
 
 static int influence_shards(sglm_engine* h, const double* beta, const double* cov, const sglm_glm_opts* opts, int rtype,
@@ -281,7 +307,7 @@ int sglm_vcov_robust(sglm_engine* h, const sglm_glm_opts* opts, const double* be
   if (int rc = require_fused_or_narrow(h, "the sandwich covariance needs")) return rc;
   const int64_t p = h->ncols();
   const int k = hc_type == SGLM_HC2 ? 1 : (hc_type == SGLM_HC3 ? 2 : 0);
-  std::vector<double> C((size_t)(p * p)), M((size_t)(p * p)), T((size_t)(p * p)), x((size_t)p);
+  std::vector<double> C((size_t)(p * p)), M((size_t)(p * p)), x((size_t)p);
   if (int rc = vcov_impl(h, opts, beta, C.data())) return rc;
   if (int rc = score_shards(h, beta, C.data(), opts, k)) return rc;
   std::vector<double> packed((size_t)packed_len(p)), zero((size_t)p, 0.0);
@@ -295,28 +321,8 @@ int sglm_vcov_robust(sglm_engine* h, const sglm_glm_opts* opts, const double* be
   double nrows = (double)(h->group() ? h->g_n : h->n);  // HC1: every row of every shard, weight 0 included
   if (hc_type == SGLM_HC1 && !h->group())
     if (int rc = h->allreduce_small(&nrows, 1)) return rc;
-  bool finite = true;
-  for (double v : M) finite = finite && std::isfinite(v);
-  // V = C M C on the host (p <= 256), one triangle of the second product mirrored
-  for (int64_t j = 0; j < p && finite; ++j)
-    for (int64_t i = 0; i < p; ++i) {
-      double s = 0.0;
-      for (int64_t l = 0; l < p; ++l) s += C[(size_t)(i + l * p)] * M[(size_t)(l + j * p)];
-      T[(size_t)(i + j * p)] = s;
-    }
   const double f = hc_type == SGLM_HC1 ? nrows / (nrows - (double)p) : 1.0;
-  for (int64_t j = 0; j < p && finite; ++j)
-    for (int64_t i = 0; i <= j; ++i) {
-      double s = 0.0, t = 0.0;  // (T C)_ij and (T C)_ji: V = (V + V') / 2
-      for (int64_t l = 0; l < p; ++l) {
-        s += T[(size_t)(i + l * p)] * C[(size_t)(l + j * p)];
-        t += T[(size_t)(j + l * p)] * C[(size_t)(l + i * p)];
-      }
-      const double v = f * (0.5 * (s + t));
-      finite = finite && std::isfinite(v);
-      cov[i + j * p] = cov[j + i * p] = v;
-    }
-  if (!finite) {
+  if (!sandwich_product(C, M, p, f, cov)) {
     set_error("requirement failed: the sandwich covariance is not finite (a row with leverage 1 under HC2 / HC3, "
               "or a row whose mean leaves the family's range at beta)");
     return SGLM_EINVAL;

@@ -15,6 +15,7 @@
 //   wide_path.cpp    wide designs (p > 256): schedules, the wide pass (enqueue_wide), the device solver
 //   ingest.cpp       sglm_reserve / set_rows / set_data* / synth* / get_data / predict*
 //   diagnostics.cpp  sglm_vcov / influence / vcov_robust / predict_new_se
+//   vcov_cluster.cpp sglm_set_clusters / vcov_cluster / cluster_plan
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -106,6 +107,7 @@ void sglm_engine::free_data() {
   proc_ov = false;
   nov = 0;
   ov_rows = 0;
+  free_clusters(false);  // cluster ids belong to the rows they were declared for
 }
 
 void sglm_engine::release() {
@@ -115,6 +117,7 @@ void sglm_engine::release() {
   xs_cap = vs_cap = 0;
   dsmall_cap = 0;
   free_influence();
+  free_clusters(true);
   for (int k = 0; k < 2; ++k) {
     if (hstage[k]) (void)hipHostFree(hstage[k]);
     if (evstage[k]) (void)hipEventDestroy(evstage[k]);

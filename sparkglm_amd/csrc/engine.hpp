@@ -1,5 +1,5 @@
 // engine.hpp -- the HIP engine behind the C ABI: what its host translation units share.
-// Private to engine.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp and ingest.cpp; never included
+// Private to engine.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp and ingest.cpp; never included
 // by a .hip file.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -235,6 +235,28 @@ struct sglm_engine : public sglm::Backend {
   const double* meat_w = nullptr;
   double score_ms = -1.0, meat_ms = -1.0;         // kernel times of the last sglm_vcov_robust call (-1: none yet)
 
+  // ---- cluster sums (cluster.hip; vcov_cluster.cpp): sglm_set_clusters / sglm_vcov_cluster ----
+  int32_t cl_G = 0;                               // clusters declared for the resident rows (0: none set)
+  int64_t cl_nseg = 0, cl_ntiles = 0;
+  // one allocation: seg_start [nseg + 2] | tile_seg [ntiles + 1] | cl_seg [nseg] | per combine level
+  // chunk_start [nchunk + 1], chunk_dst [nchunk]
+  int64_t* dclidx = nullptr;
+  double* dR = nullptr;                           // segment sums [nseg][p]
+  // the combine's levels (common.hpp CombineArgs): offsets into dclidx; rows of dP the level reads
+  // (level 0 reads R through cl_seg) and writes
+  struct CombineLevel {
+    int64_t nchunk, start_off, dst_off, in_row, out_row;
+  };
+  std::vector<CombineLevel> cl_levels;
+  double* dP = nullptr;                           // partial sums of the clusters of more than one chunk
+  bool cl_S_stale = true;                         // S may hold sums of other ids: zero it before the combine
+  // an engine on the same device whose design is S [G x p] (the combine kernel writes it there): its
+  // tuned LM Gram pass forms the meat S'S.  Kept from call to call while G and p stay.
+  sglm_engine* cl_inner = nullptr;
+  hipEvent_t evcl[4] = {nullptr, nullptr, nullptr, nullptr};
+  // kernel times of the last sglm_vcov_cluster call: score, segment sums, combine, Gram (-1: none yet)
+  double cl_ms[4] = {-1.0, -1.0, -1.0, -1.0};
+
   // ---- group: single-process multi-device handle (sglm_create_multi): the shards' engines; this
   // handle then only routes and reduces (one process owns all GPUs, as SURVEY 8(b) asks) ----
   std::vector<sglm_engine*> subs;
@@ -337,6 +359,14 @@ struct sglm_engine : public sglm::Backend {
   int score_local(const double* beta, const double* cov, int family, int link, int k);
   int score_sync();
   int predict_new_se(const double* X, int64_t nn, int64_t pp, int64_t ldx, const double* cov, double disp, double* out);
+
+  // ---- vcov_cluster.cpp ----
+  void free_clusters(bool inner_too);
+  int set_clusters_local(const int32_t* ids, int64_t nl, int32_t G);
+  int uscore_local(const double* beta, int family, int link);
+  int cluster_sums_local();
+  int cluster_sync();
+  int64_t cluster_len() const { return cl_inner->n_pad * p; }  // doubles of S, padding included
 };
 
 namespace sglm {
@@ -348,6 +378,14 @@ inline int check_handle(sglm_engine* h) {
   }
   return SGLM_OK;
 }
+
+// ---- diagnostics.cpp: what the covariance estimators share ----
+// inv(X'WX) at beta (collective over a communicator), the bread of both sandwich estimators
+int vcov_impl(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, double* cov);
+// SGLM_EINVAL unless every shard is a resident design on the fused / narrow path
+int require_fused_or_narrow(const sglm_engine* h, const char* what);
+// cov = f (C M C + (C M C)') / 2, exactly symmetric (col-major p x p, on the host); false: M or cov is not finite
+bool sandwich_product(const std::vector<double>& C, const std::vector<double>& M, int64_t p, double f, double* cov);
 
 // The handle holds a complete design: every reserved row written (or generated).
 inline int check_ready(sglm_engine* h) {

@@ -27,6 +27,7 @@
 // score_kernel is the same body writing one vector, the sandwich covariance's score weights
 //   omega_i = u_i^2 / (1 - h_i)^k,  u_i = w_i (y_i - mu_i) g'(mu_i),  h_i = w_i q_i
 // (k = 0: no MFMA product), which the engine then feeds to a Gram pass as prior weights.
+// uscore_kernel stores u_i itself, the factor of the cluster sums of cluster.hip.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -55,9 +56,10 @@ __device__ __forceinline__ double group_sum(double v) {  // over the four lane g
   return v;
 }
 
-// what the kernel does with a row: the diagnostics at beta, sqrt(phi q) alone, or the sandwich
-// estimator's score weight omega = u^2 / (1 - h)^k
-enum InflMode : int { INFL_ROWS = 0, INFL_QFORM = 1, INFL_SCORE = 2 };
+// what the kernel does with a row: the diagnostics at beta, sqrt(phi q) alone, the sandwich
+// estimator's score weight omega = u^2 / (1 - h)^k, or the signed score u itself,
+// the factor of the cluster sums (cluster.hip)
+enum InflMode : int { INFL_ROWS = 0, INFL_QFORM = 1, INFL_SCORE = 2, INFL_USCORE = 3 };
 
 template <int P16, int MODE>
 __device__ __forceinline__ void influence_body(const InflArgs& a) {
@@ -184,12 +186,16 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
         continue;
       }
       const double e = eta[r] + (a.off ? a.off[ri] : 0.0);
-      if constexpr (MODE == INFL_SCORE) {
+      if constexpr (MODE == INFL_SCORE || MODE == INFL_USCORE) {
         // u = w (y - mu) g'(mu): the working weight times the working residual; a row of prior weight
         // 0 contributes exactly 0 whatever its mu
         const double pw = a.prior ? a.prior[ri] : 1.0;
         const InflRow w = influence_row(a.family, a.link, RESID_WORKING, e, a.y[ri], a.m ? a.m[ri] : 1.0, pw);
         const double u = w.w * w.resid;
+        if constexpr (MODE == INFL_USCORE) {
+          a.out[ri] = pw == 0.0 ? 0.0 : u;
+          continue;
+        }
         double om = u * u;
         if (a.hc_k > 0) {
           const double d = 1.0 - w.w * q[r];
@@ -236,6 +242,10 @@ __global__ void __launch_bounds__(INFL_NT, 2) qform_kernel(InflArgs a) {
 template <int P16>
 __global__ void __launch_bounds__(INFL_NT, 2) score_kernel(InflArgs a) {
   influence_body<P16, INFL_SCORE>(a);
+}
+template <int P16>
+__global__ void __launch_bounds__(INFL_NT, 2) uscore_kernel(InflArgs a) {
+  influence_body<P16, INFL_USCORE>(a);
 }
 
 __global__ void __launch_bounds__(256) influence_sum_kernel(const double* __restrict__ part, int nparts,
@@ -307,6 +317,14 @@ hipError_t launch_influence(int P16, const InflArgs& a, int grid, hipStream_t st
 hipError_t launch_score(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
 #define K(N) \
   case N: hipExtLaunchKernelGGL(score_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
+  INFL_CASES(K)
+#undef K
+  return hipGetLastError();
+}
+
+hipError_t launch_uscore(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+#define K(N) \
+  case N: hipExtLaunchKernelGGL(uscore_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
   INFL_CASES(K)
 #undef K
   return hipGetLastError();

@@ -68,6 +68,20 @@ hipError_t launch_qform(int P16, const InflArgs& a, int grid, hipStream_t st);
 hipError_t launch_score(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
                         hipEvent_t e1 = nullptr);
 hipError_t launch_influence_sum(const double* part, int nparts, double* out, hipStream_t st);  // fixed order
+// the signed scores u_i = w_i (y_i - mu_i) g'(mu_i) of the rows < n into a.out (need_q = 0: no MFMA product)
+hipError_t launch_uscore(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
+                         hipEvent_t e1 = nullptr);
+
+// cluster sums (cluster.hip): the cluster-robust covariance's grouped scores
+// segments of the n rows under `ids` (cluster_segments: maximal runs of one id, cut at every multiple
+// of CLUSTER_TILE_ROWS): seg_start [nseg + 1], seg_cluster [nseg], either may be null; returns nseg,
+// or -1 at an id outside [0, G)
+int64_t cluster_segments(const int32_t* ids, int64_t n, int32_t G, int64_t* seg_start, int32_t* seg_cluster);
+int cluster_sum_grid(int ncu, int64_t n, int p);
+hipError_t launch_cluster_sum(const ClusterArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
+                              hipEvent_t e1 = nullptr);
+hipError_t launch_cluster_combine(const CombineArgs& a, int ncu, hipStream_t st, hipEvent_t e0 = nullptr,
+                                  hipEvent_t e1 = nullptr);
 
 // wide path (wide.hip)
 int wide_panels(int p);

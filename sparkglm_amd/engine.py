@@ -386,6 +386,56 @@ class Engine:
         L.check(self._lib.sglm_get_sandwich_ms(self._h, C.byref(a), C.byref(b)), "sglm_get_sandwich_ms")
         return a.value, b.value
 
+    # ---- cluster-robust covariance ----
+    def set_clusters(self, ids, G=None):
+        """The cluster of every resident row (sglm_set_clusters).  With `G=None` the labels -- any
+        integer or string dtype -- are factorised (np.unique); with `G` given, `ids` are dense codes in
+        [0, G): the form the ranks of a communicator need, so that codes are global.  `ids=None`
+        clears.  A call that replaces the data (set_data, reserve, synth, ...) drops the clusters."""
+        if ids is None:
+            L.check(self._lib.sglm_set_clusters(self._h, None, 0, 0), "sglm_set_clusters")
+            return self
+        ids = np.asarray(ids).reshape(-1)
+        if G is None:
+            labels, ids = np.unique(ids, return_inverse=True)
+            G = len(labels)
+        elif ids.dtype.kind not in "iu":
+            raise L.IllegalArgumentException("requirement failed: with G given, ids are integer codes in [0, G)")
+        elif ids.size and (ids.min() < 0 or ids.max() >= G):  # before the cast to int32 can wrap a code
+            raise L.IllegalArgumentException(f"requirement failed: every cluster id in [0, G = {G})")
+        codes = np.ascontiguousarray(ids, dtype=np.int32)
+        L.check(self._lib.sglm_set_clusters(self._h, codes.ctypes.data_as(C.POINTER(C.c_int32)), codes.shape[0],
+                                            int(G)), "sglm_set_clusters")
+        return self
+
+    def vcov_cluster(self, beta, family="binomial", link="logit", type="HC1", cadjust=True, return_meat=False):
+        """Cluster-robust covariance a C M C at beta (p x p; sandwich::vcovCL): the bread C = vcov(beta),
+        the meat M = S'S of the cluster sums S[g] = sum_{i in g} u_i x_i (set_clusters first).  `type`
+        "HC0" | "HC1" ((n - 1) / (n - p)); `cadjust` a further G / (G - 1).  The defaults are vcovCL's
+        and Stata's regress, vce(cluster); "HC0" with cadjust is Stata's glm rule.  With `return_meat`
+        the pair (V, M)."""
+        if type not in L.CLUSTER_TYPES:
+            raise L.IllegalArgumentException(f"requirement failed: with clusters, type must be one of "
+                                             f"{list(L.CLUSTER_TYPES)}, got {type!r}")
+        o = glm_opts(family, link)
+        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+        if b.shape[0] != self.p:
+            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
+                                             f"beta {b.shape[0]} rows")
+        cov = np.zeros((self.p, self.p), order="F")
+        meat = np.zeros((self.p, self.p), order="F") if return_meat else None
+        L.check(self._lib.sglm_vcov_cluster(self._h, C.byref(o), L.ptr(b), L.HC_TYPES[type], int(bool(cadjust)),
+                                            cov.ctypes.data_as(L.dp),
+                                            None if meat is None else meat.ctypes.data_as(L.dp)), "sglm_vcov_cluster")
+        return (cov, meat) if return_meat else cov
+
+    def cluster_ms(self):
+        """Kernel times (score, segment sums, combine, the meat's Gram pass) of the last vcov_cluster()
+        call (HIP events)."""
+        t = [C.c_double() for _ in range(4)]
+        L.check(self._lib.sglm_get_cluster_ms(self._h, *[C.byref(v) for v in t]), "sglm_get_cluster_ms")
+        return tuple(v.value for v in t)
+
     def influence_ms(self) -> float:
         """Kernel time of the last influence() call (HIP events)."""
         ms = C.c_double()

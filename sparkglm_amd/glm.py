@@ -206,6 +206,20 @@ def _check_cov_type(type):
                                          f"{['const'] + sorted(L.HC_TYPES)}, got {type!r}")
 
 
+def _check_cluster_type(type):
+    if type not in L.CLUSTER_TYPES:
+        raise L.IllegalArgumentException(f"requirement failed: with cluster, type must be one of "
+                                         f"{list(L.CLUSTER_TYPES)} (HC2 / HC3 need per-cluster leverage blocks), "
+                                         f"got {type!r}")
+
+
+def _set_clusters(eng, cluster: Frame, n: int):
+    """The one column of `cluster` (labels of any integer or string type) as the engine's clusters."""
+    _require(len(cluster.columns) == 1, "The 'cluster' DataFrame must have only one column")
+    _require(cluster.count() == n, "The two DataFrames must have the same number of rows")
+    eng.set_clusters(cluster[cluster.columns[0]])
+
+
 def _coef_table(names, beta, V, pval) -> Frame:
     """The coeftest columns from a covariance: se = sqrt(diag V), stat = estimate / se, pval(stat)."""
     est = np.asarray(beta, dtype=np.float64).reshape(-1)
@@ -302,10 +316,27 @@ class GLM:
         return eng.vcov(beta, fam, lnk) if type == "const" else eng.vcov_robust(beta, fam, lnk, type=type)
 
     @staticmethod
+    def vcov_cluster(obj: GLMModel, y: Frame, x: Frame, cluster: Frame, offset: Frame = None, m: Frame = None,
+                     prior: Frame = None, device: int = 0, type: str = "HC1", cadjust: bool = True) -> np.ndarray:
+        """Extension: the cluster-robust covariance sandwich::vcovCL(fit, cluster = ~id, type, cadjust)
+        at the fitted coefficients; `cluster` holds one column of labels, one per row.  `type` "HC0" or
+        "HC1"; the defaults are vcovCL's (and Stata's regress, vce(cluster)).  Final, as the sandwich."""
+        _check_cluster_type(type)
+        eng, fam, lnk, beta = GLM._load(obj, y, x, offset, m, prior, device)
+        _set_clusters(eng, cluster, y.count())
+        return eng.vcov_cluster(beta, fam, lnk, type=type, cadjust=cadjust)
+
+    @staticmethod
     def coeftest(obj: GLMModel, y: Frame, x: Frame, offset: Frame = None, m: Frame = None, prior: Frame = None,
-                 device: int = 0, type: str = "HC3") -> Frame:
+                 device: int = 0, type: str = "HC3", cluster: Frame = None, cadjust: bool = True) -> Frame:
         """Extension: lmtest::coeftest(fit, vcov. = vcovHC(fit, type)) -- name, estimate, robust
-        standard error sqrt(diag V), z statistic and its two-sided normal p-value."""
+        standard error sqrt(diag V), z statistic and its two-sided normal p-value.  With `cluster` (one
+        column of labels) the covariance is vcovCL(fit, cluster, type, cadjust) and `type` must be "HC0"
+        or "HC1"."""
+        if cluster is not None:
+            V = GLM.vcov_cluster(obj, y, x, cluster, offset, m, prior, device, type, cadjust)
+            beta = np.asarray(obj.coefs, dtype=np.float64).reshape(-1)
+            return _coef_table(obj.xnames, beta, V, L.load().sglm_pval_normal)
         if type not in L.HC_TYPES:
             raise L.IllegalArgumentException(f"requirement failed: type must be one of {sorted(L.HC_TYPES)}, "
                                              f"got {type!r}")

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib as L
 from .frame import Frame
-from .glm import _check_cov_type, _coef_table, _engine, _require
+from .glm import _check_cluster_type, _check_cov_type, _coef_table, _engine, _require, _set_clusters
 
 
 @dataclass
@@ -184,13 +184,33 @@ class LM:
         return eng.vcov_robust(beta, "gaussian", "identity", type=type)
 
     @staticmethod
-    def coeftest(obj: LMModel, x: Frame, y: Frame, device: int = 0, type: str = "HC3") -> Frame:
+    def vcov_cluster(obj: LMModel, x: Frame, y: Frame, cluster: Frame, device: int = 0, type: str = "HC1",
+                     cadjust: bool = True) -> np.ndarray:
+        """Extension: the cluster-robust covariance sandwich::vcovCL(fit, cluster = ~id, type, cadjust)
+        at the fitted coefficients; `cluster` holds one column of labels, one per row.  `type` "HC0" or
+        "HC1"; the defaults are vcovCL's and Stata's regress, vce(cluster)."""
+        _check_cluster_type(type)
+        _require(x.count() == y.count(), "The two DataFrames must have the same number of rows")
+        eng = _engine(device)
+        eng.set_data(x.select(*obj.xnames).to_matrix(), y.to_vector())
+        _set_clusters(eng, cluster, y.count())
+        beta = np.asarray(obj.coefs, dtype=np.float64).reshape(-1)
+        return eng.vcov_cluster(beta, "gaussian", "identity", type=type, cadjust=cadjust)
+
+    @staticmethod
+    def coeftest(obj: LMModel, x: Frame, y: Frame, device: int = 0, type: str = "HC3", cluster: Frame = None,
+                 cadjust: bool = True) -> Frame:
         """Extension: lmtest::coeftest(fit, vcov. = vcovHC(fit, type)) -- name, estimate, robust
-        standard error, t statistic and its two-sided p-value on n - p degrees of freedom."""
-        if type not in L.HC_TYPES:
+        standard error, t statistic and its two-sided p-value on n - p degrees of freedom.  With
+        `cluster` (one column of labels) the covariance is vcovCL(fit, cluster, type, cadjust) and
+        `type` must be "HC0" or "HC1"; the statistic and its p-value rule stay."""
+        if cluster is not None:
+            V = LM.vcov_cluster(obj, x, y, cluster, device=device, type=type, cadjust=cadjust)
+        elif type not in L.HC_TYPES:
             raise L.IllegalArgumentException(f"requirement failed: type must be one of {sorted(L.HC_TYPES)}, "
                                              f"got {type!r}")
-        V = LM.vcov(obj, x, y, device=device, type=type)
+        else:
+            V = LM.vcov(obj, x, y, device=device, type=type)
         dfe = float(int(obj.nrow) - len(obj.xnames))
         pval_t = L.load().sglm_pval_t
         return _coef_table(obj.xnames, obj.coefs, V, lambda t: pval_t(t, dfe))
