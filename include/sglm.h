@@ -67,8 +67,11 @@ extern "C" {
                               symbols only): sglm_vcov, sglm_influence, sglm_predict_new_se,
                               sglm_get_influence_ms, enum sglm_resid_type, sglm_vcov_robust,
                               sglm_get_sandwich_ms, enum sglm_hc_type, sglm_set_clusters, sglm_vcov_cluster,
-                              sglm_get_cluster_ms, sglm_cluster_plan; (new values only:) SGLM_SQRT and
-                              the non-canonical (family, link) pairs of enum sglm_link's table */
+                              sglm_get_cluster_ms, sglm_cluster_plan, sglm_set_theta, sglm_get_theta,
+                              sglm_get_theta_ms, sglm_nb_theta_terms, sglm_theta_ml, sglm_fit_glm_start, sglm_fit_glm_nb
+                              (with sglm_nb_opts / sglm_nb_result); (new values only:) SGLM_SQRT and
+                              the non-canonical (family, link) pairs of enum sglm_link's table,
+                              SGLM_NEGBIN and its three pairs */
 
 enum sglm_status {
   SGLM_OK = 0,
@@ -81,12 +84,16 @@ enum sglm_status {
 
 /* Families: the reference fits only binomial (GLM.scala:486-590); the rest follow R's
  * family objects on the reference's IRLS skeleton. */
-enum sglm_family { SGLM_BINOMIAL = 0, SGLM_GAUSSIAN = 1, SGLM_POISSON = 2, SGLM_GAMMA = 3 };
+enum sglm_family { SGLM_BINOMIAL = 0, SGLM_GAUSSIAN = 1, SGLM_POISSON = 2, SGLM_GAMMA = 3, SGLM_NEGBIN = 4 };
 /* The (family, link) pairs, R's three links per family; any other pair is SGLM_EINVAL:
  *   binomial  logit, probit, cloglog
  *   gaussian  identity, log, inverse
  *   poisson   log, identity, sqrt
  *   gamma     inverse, identity, log
+ *   negbin    log, sqrt, identity      (MASS::negative.binomial(theta): V = mu + mu^2 / theta)
+ * The negative binomial's theta is not in sglm_glm_opts: it lives on the handle (sglm_set_theta, or estimated
+ * by sglm_fit_glm_nb).  Every call that takes SGLM_NEGBIN on a handle whose theta was never set is
+ * SGLM_EINVAL.  None of its links is canonical: its rows follow the poisson rows' validity rule below.
  * With a non-canonical link of gaussian / poisson / gamma the mean can leave the family's range during
  * the iterations (R's validmu / valideta: poisson and gamma need mu finite and > 0, sqrt eta > 0; gaussian
  * eta finite, inverse eta != 0).  There is no step-halving: such a fit returns SGLM_EINVAL ("no valid set
@@ -95,7 +102,7 @@ enum sglm_family { SGLM_BINOMIAL = 0, SGLM_GAUSSIAN = 1, SGLM_POISSON = 2, SGLM_
 enum sglm_link {
   SGLM_LOGIT = 0, SGLM_PROBIT = 1, SGLM_CLOGLOG = 2, /* binomial (GLM.scala:190-251) */
   SGLM_IDENTITY = 3, SGLM_LOG = 4, SGLM_INVERSE = 5,  /* gaussian / poisson / gamma */
-  SGLM_SQRT = 6                                       /* poisson */
+  SGLM_SQRT = 6                                       /* poisson, negbin */
 };
 
 /* How mu is formed on the first iteration. */
@@ -307,6 +314,60 @@ int sglm_set_comm_rccl(sglm_engine *h, int nranks, int rank, const void *unique_
 /* ---- fits ---------------------------------------------------------------------- */
 int sglm_fit_glm(sglm_engine *h, const sglm_glm_opts *opts, sglm_preglm *out);
 int sglm_fit_lm(sglm_engine *h, sglm_prelm *out);
+/* sglm_fit_glm warm-started (R's start=): the initial constant-mu pass is replaced by a pass at beta_start
+ * [p].  dev_trace[0] is the deviance at beta_start; the loop and its stop rule |delta deviance| <= tol are
+ * sglm_fit_glm's; iter counts solves; null_deviance comes from one initial-mode pass at mean(y).  Every
+ * family. */
+int sglm_fit_glm_start(sglm_engine *h, const sglm_glm_opts *opts, const double *beta_start, sglm_preglm *out);
+
+/* ---- negative binomial --------------------------------------------------------- */
+/* theta of SGLM_NEGBIN on this handle (a group handle: on all its shards).  theta <= 0 or non-finite is
+ * SGLM_EINVAL.  sglm_get_theta returns 0 while none was set.  Ranks of a communicator each set their own
+ * handle (sglm_fit_glm_nb leaves the identical value on every rank). */
+int sglm_set_theta(sglm_engine *h, double theta);
+int sglm_get_theta(sglm_engine *h, double *theta);
+/* theta_terms_kernel launches on this handle since it was created and their summed kernel time (HIP events; a
+ * multi-device handle: its slowest shard). */
+int sglm_get_theta_ms(sglm_engine *h, int64_t *launches, double *kernel_ms);
+/* The theta score, information and log-likelihood at beta [p] and theta, with mu = unlink(X beta + offset), w
+ * the prior weight: out[5] = {
+ *   sum w [psi(theta+y) - psi(theta) + log theta + 1 - log(theta+mu) - (y+theta)/(mu+theta)],
+ *   sum w [-psi'(theta+y) + psi'(theta) - 1/theta + 2/(mu+theta) - (y+theta)/(mu+theta)^2],
+ *   sum w dnbinom(y, theta, mu, log), sum w (y/mu - 1)^2, sum w }.
+ * opts: the link (family ignored).  It first forms eta at beta with one deviance-only pass (no Gram), then
+ * runs one streaming kernel over y, eta and the prior weights.  COLLECTIVE over a communicator; every rank
+ * gets bitwise the same sums (rank blocks, compensated, as the pass scalars). */
+int sglm_nb_theta_terms(sglm_engine *h, const sglm_glm_opts *opts, const double *beta, double theta, double *out5);
+/* MASS::theta.ml at beta: t0 = sum w / sum w (y/mu - 1)^2; it = 0; del = 1;
+ *   while (++it < limit && |del| > eps) { t0 = |t0|; del = score(t0) / info(t0); t0 += del; }
+ * *theta = t0 (0 where t0 < 0), *se = sqrt(1 / info) of the last step, *iters = it, *warn: bit 0 "iteration
+ * limit reached" (it == limit), bit 1 "estimate truncated at zero".  limit <= 0: 25; eps <= 0: 2^-13
+ * (.Machine$double.eps^0.25).  Each Newton step is one kernel launch and one all-reduce of five scalars.
+ * The handle's theta is not changed.  COLLECTIVE. */
+int sglm_theta_ml(sglm_engine *h, const sglm_glm_opts *opts, const double *beta, int limit, double eps,
+                  double *theta, double *se, int *iters, int *warn);
+typedef struct {
+  int maxit;         /* outer alternations; 0: 25 */
+  double epsilon;    /* outer stop |Lm0 - Lm| / d1 + |del| <= epsilon; 0: 1e-8 */
+  int theta_limit;   /* sglm_theta_ml's limit; 0: 25 */
+  double theta_eps;  /* sglm_theta_ml's eps; 0: 2^-13 */
+} sglm_nb_opts;
+typedef struct {
+  double theta, se_theta, twologlik;
+  int outer_iter;    /* inner negative binomial fits run */
+  int theta_warn;    /* the last sglm_theta_ml's warn bits */
+  int converged;     /* 0: maxit ended the alternation */
+} sglm_nb_result;
+/* MASS::glm.nb: a Poisson fit (opts->link, opts->init_mode, opts->tol), theta by sglm_theta_ml, then
+ * alternately a negative binomial fit at theta warm-started from the last coefficients (sglm_fit_glm_start)
+ * and theta by sglm_theta_ml at its coefficients, until |Lm0 - Lm| / d1 + |theta_old - theta| <= epsilon
+ * (Lm = twice the log-likelihood, d1 = sqrt(2 max(1, n - p))).  opts->family is ignored.  `out` is the last
+ * inner fit; its null_deviance is recomputed at the final theta and its loglik is twologlik / 2.  The final
+ * theta stays set on the handle, so sglm_vcov*, sglm_influence and sglm_predict_* with SGLM_NEGBIN follow
+ * without another call.  A failure of an inner fit is returned as that fit's status.  nb_opts may be NULL
+ * (all defaults).  COLLECTIVE. */
+int sglm_fit_glm_nb(sglm_engine *h, const sglm_glm_opts *opts, const sglm_nb_opts *nb_opts, sglm_preglm *out,
+                    sglm_nb_result *nb);
 
 /* One IRLS pass at beta (beta == NULL: the initial constant-eta pass at mu0),
  * all-reduced over the communicator.  Outputs (any may be NULL): gram [p*p] col-major
@@ -451,7 +512,8 @@ typedef struct {
   int (*pass)(void *ctx, int mode, const double *beta, double mu0, double ybar, double *packed);
 } sglm_backend;
 
-/* fn: as sglm_set_comm's (the communicator thread unless SGLM_COMM_TIMEOUT_S=0). */
+/* fn: as sglm_set_comm's (the communicator thread unless SGLM_COMM_TIMEOUT_S=0).  SGLM_NEGBIN is
+ * SGLM_EINVAL here: the pass callback carries no theta. */
 int sglm_fit_glm_external(const sglm_backend *be, sglm_allreduce_fn fn, void *comm_ctx,
                           const sglm_glm_opts *opts, sglm_preglm *out);
 int sglm_fit_lm_external(const sglm_backend *be, sglm_allreduce_fn fn, void *comm_ctx,

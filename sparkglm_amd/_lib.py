@@ -14,12 +14,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGLM_LIB") or os.path.join(HERE, "lib", "libsglm_hip.so")
 
 SGLM_OK, SGLM_EINVAL, SGLM_ESINGULAR, SGLM_EHIP, SGLM_ECOMM, SGLM_ENOMEM = range(6)
-FAMILIES = {"binomial": 0, "gaussian": 1, "poisson": 2, "gamma": 3}
+FAMILIES = {"binomial": 0, "gaussian": 1, "poisson": 2, "gamma": 3, "negbin": 4}
 LINKS = {"logit": 0, "probit": 1, "cloglog": 2, "identity": 3, "log": 4, "inverse": 5, "sqrt": 6}
 CANONICAL_LINK = {"gaussian": "identity", "poisson": "log", "gamma": "inverse"}
 # the links of each extension family (R's family objects; include/sglm.h enum sglm_link), canonical first
 FAMILY_LINKS = {"gaussian": ("identity", "log", "inverse"), "poisson": ("log", "identity", "sqrt"),
                 "gamma": ("inverse", "identity", "log")}
+NEGBIN_LINKS = ("log", "sqrt", "identity")  # MASS::negative.binomial's; theta lives on the engine handle
 INIT_SINGLE, INIT_MULTIPLE = 0, 1
 NS = 8
 S_DEV, S_PEARSON, S_LL, S_BAD, S_AUX0, S_AUX1, S_AUX2, S_SUMW = range(8)
@@ -38,6 +39,8 @@ EXPORTS = [
     "sglm_vcov", "sglm_influence", "sglm_predict_new_se", "sglm_get_influence_ms",
     "sglm_vcov_robust", "sglm_get_sandwich_ms",
     "sglm_set_clusters", "sglm_vcov_cluster", "sglm_get_cluster_ms", "sglm_cluster_plan",
+    "sglm_set_theta", "sglm_get_theta", "sglm_get_theta_ms", "sglm_nb_theta_terms", "sglm_theta_ml", "sglm_fit_glm_start",
+    "sglm_fit_glm_nb",
 ]
 PREDICT_LINK, PREDICT_RESPONSE = 0, 1
 RESID_TYPES = {"response": 0, "working": 1, "pearson": 2, "deviance": 3}  # enum sglm_resid_type
@@ -55,6 +58,15 @@ class PreGLM(C.Structure):
     _fields_ = [("coefs", dp), ("std_err", dp), ("deviance", C.c_double), ("null_deviance", C.c_double),
                 ("pearson", C.c_double), ("loglik", C.c_double), ("iter", C.c_int), ("nrow", C.c_double),
                 ("npart", C.c_int), ("dev_trace", dp), ("max_trace", C.c_int)]
+
+
+class NbOpts(C.Structure):
+    _fields_ = [("maxit", C.c_int), ("epsilon", C.c_double), ("theta_limit", C.c_int), ("theta_eps", C.c_double)]
+
+
+class NbResult(C.Structure):
+    _fields_ = [("theta", C.c_double), ("se_theta", C.c_double), ("twologlik", C.c_double),
+                ("outer_iter", C.c_int), ("theta_warn", C.c_int), ("converged", C.c_int)]
 
 
 class PreLM(C.Structure):
@@ -188,6 +200,15 @@ def load():
         "sglm_set_clusters": ([h, C.POINTER(C.c_int32), C.c_int64, C.c_int32], C.c_int),
         "sglm_vcov_cluster": ([h, C.POINTER(GlmOpts), dp, C.c_int, C.c_int, dp, dp], C.c_int),
         "sglm_get_cluster_ms": ([h, dp, dp, dp, dp], C.c_int),
+        "sglm_set_theta": ([h, C.c_double], C.c_int),
+        "sglm_get_theta": ([h, dp], C.c_int),
+        "sglm_get_theta_ms": ([h, C.POINTER(C.c_int64), dp], C.c_int),
+        "sglm_nb_theta_terms": ([h, C.POINTER(GlmOpts), dp, C.c_double, dp], C.c_int),
+        "sglm_theta_ml": ([h, C.POINTER(GlmOpts), dp, C.c_int, C.c_double, dp, dp, C.POINTER(C.c_int),
+                           C.POINTER(C.c_int)], C.c_int),
+        "sglm_fit_glm_start": ([h, C.POINTER(GlmOpts), dp, C.POINTER(PreGLM)], C.c_int),
+        "sglm_fit_glm_nb": ([h, C.POINTER(GlmOpts), C.POINTER(NbOpts), C.POINTER(PreGLM), C.POINTER(NbResult)],
+                            C.c_int),
         "sglm_cluster_plan": ([C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int64),
                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
     }

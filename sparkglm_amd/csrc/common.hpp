@@ -19,7 +19,7 @@ enum PassMode : int {
   MODE_LM_RESID = 4     // no Gram: SSE/SSR/SST at beta (LM.scala:160-188)
 };
 
-enum Family : int { FAM_BINOMIAL = 0, FAM_GAUSSIAN = 1, FAM_POISSON = 2, FAM_GAMMA = 3 };
+enum Family : int { FAM_BINOMIAL = 0, FAM_GAUSSIAN = 1, FAM_POISSON = 2, FAM_GAMMA = 3, FAM_NEGBIN = 4 };
 enum Link : int {
   LNK_LOGIT = 0, LNK_PROBIT = 1, LNK_CLOGLOG = 2, LNK_IDENTITY = 3, LNK_LOG = 4, LNK_INVERSE = 5, LNK_SQRT = 6
 };
@@ -27,16 +27,19 @@ enum Link : int {
 // run time (PassArgs::link ...) and take the out-of-line reference row functions for every row.
 constexpr int LNK_RT = -1;
 
-// The (family, link) pairs of the engine (R's family objects: three links per family).
+// The (family, link) pairs of the engine (R's family objects: three links per family; the negative
+// binomial's are MASS::negative.binomial's).
 constexpr bool family_link_pair(int fam, int lnk) {
   return (fam == FAM_BINOMIAL && (lnk == LNK_LOGIT || lnk == LNK_PROBIT || lnk == LNK_CLOGLOG)) ||
          (fam == FAM_GAUSSIAN && (lnk == LNK_IDENTITY || lnk == LNK_LOG || lnk == LNK_INVERSE)) ||
          (fam == FAM_POISSON && (lnk == LNK_LOG || lnk == LNK_IDENTITY || lnk == LNK_SQRT)) ||
-         (fam == FAM_GAMMA && (lnk == LNK_INVERSE || lnk == LNK_IDENTITY || lnk == LNK_LOG));
+         (fam == FAM_GAMMA && (lnk == LNK_INVERSE || lnk == LNK_IDENTITY || lnk == LNK_LOG)) ||
+         (fam == FAM_NEGBIN && (lnk == LNK_LOG || lnk == LNK_SQRT || lnk == LNK_IDENTITY));
 }
 // The non-canonical pairs of the extension families: the only ones whose mu = unlink(eta) can leave the
 // family's range (R's validmu / valideta), which the row functions report as a NaN unit deviance
-// (rowmath.hpp link_row_valid) and the drivers as SGLM_EINVAL.
+// (rowmath.hpp link_row_valid) and the drivers as SGLM_EINVAL.  None of the negative binomial's links is
+// its canonical one (log(mu / (mu + theta))), so all three of its pairs are in this set.
 constexpr bool noncanonical_pair(int fam, int lnk) {
   return family_link_pair(fam, lnk) && fam != FAM_BINOMIAL &&
          !((fam == FAM_GAUSSIAN && lnk == LNK_IDENTITY) || (fam == FAM_POISSON && lnk == LNK_LOG) ||
@@ -45,7 +48,7 @@ constexpr bool noncanonical_pair(int fam, int lnk) {
 
 // The one dispatch of a run-time (family, link) onto the kernels' compile-time <FAM, LNK> instantiations
 // (every launcher goes through it): a dedicated instantiation for the binomial links, the three canonical
-// pairs and gamma / log; the other pairs run their family's LNK_RT instantiation.  f(Fam, Lnk) receives
+// pairs, gamma / log and negative binomial / log; the other pairs run their family's LNK_RT instantiation.  f(Fam, Lnk) receives
 // the pair as std::integral_constant-like tags; false: the pair has no instantiation (the launcher returns
 // hipErrorInvalidValue -- it never runs another link's kernel).
 template <int V>
@@ -65,16 +68,19 @@ inline bool dispatch_family_link(int fam, int lnk, F&& f) {
   } else if (fam == FAM_POISSON) {
     if (lnk == LNK_LOG) f(IntTag<FAM_POISSON>{}, IntTag<LNK_LOG>{});
     else f(IntTag<FAM_POISSON>{}, IntTag<LNK_RT>{});
-  } else {
+  } else if (fam == FAM_GAMMA) {
     if (lnk == LNK_INVERSE) f(IntTag<FAM_GAMMA>{}, IntTag<LNK_INVERSE>{});
     else if (lnk == LNK_LOG) f(IntTag<FAM_GAMMA>{}, IntTag<LNK_LOG>{});
     else f(IntTag<FAM_GAMMA>{}, IntTag<LNK_RT>{});
+  } else {
+    if (lnk == LNK_LOG) f(IntTag<FAM_NEGBIN>{}, IntTag<LNK_LOG>{});
+    else f(IntTag<FAM_NEGBIN>{}, IntTag<LNK_RT>{});
   }
   return true;
 }
 // the link slot of the instantiation dispatch_family_link picks (LNK_RT or the link itself)
 constexpr int dispatched_link(int fam, int lnk) {
-  return (noncanonical_pair(fam, lnk) && !(fam == FAM_GAMMA && lnk == LNK_LOG)) ? LNK_RT : lnk;
+  return (noncanonical_pair(fam, lnk) && !((fam == FAM_GAMMA || fam == FAM_NEGBIN) && lnk == LNK_LOG)) ? LNK_RT : lnk;
 }
 
 // Which families carry their final statistics in the narrow pass (PassArgs::stats_in_pass;
@@ -120,6 +126,7 @@ struct PassArgs {
   int no_gram;          // deviance-only pass (glm_drive's speculative last pass): row stage, no Gram
   int fused_split;      // split-role kernel K1r (irls_pass_r_kernel) from P16 >= threshold: 1 default, 0 never, N: P16 >= N
   int lm_extras;        // narrow LM Gram pass of the one-round-trip LM.fit: X'1 after the scalars, y'y in S_PEARSON
+  double theta;         // FAM_NEGBIN: the dispersion parameter (sglm_set_theta); last, so every other field keeps its offset
 };
 
 // ---- wide-design path (p > 16*MAX_P16): row kernel + panel-pair Gram kernel ----
@@ -156,6 +163,7 @@ struct WideRowArgs {
   double* xs_out;       // procedural chunks: the generated X rows stored here (column-major,
   int64_t xs_ld;        //   leading dimension xs_ld, local row = row - r_begin), else null
   const double* eta_in; // procedural chunks after proc_gen_kernel: X beta of rows < n (MODE_IRLS), else null
+  double theta;         // FAM_NEGBIN: the dispersion parameter (last: the other fields keep their offsets)
 };
 
 // Procedural chunks: the lean generator (wide.hip proc_gen_kernel) -- X rows [r_begin, r_end) into
@@ -221,6 +229,9 @@ struct InflArgs {
   double* hpart;        // [grid] per-workgroup sums of h (null: not wanted)
   // qform_kernel: out[i] = sqrt(max(0, dispersion * q_i)); score_kernel: out[i] = omega_i
   double* out;
+  // FAM_NEGBIN: the dispersion parameter.  hc_k took the block's only 4-byte gap and a double needs 8, so
+  // theta goes last: every other field keeps its offset.
+  double theta;
 };
 
 // Cluster sums S[g, :] = sum_{i: id_i = g} u_i x_i (cluster.hip).  A segment is a
@@ -269,8 +280,21 @@ struct StatsArgs {
   double* partials;     // [grid][NS]
   const double* ybar_dev;  // non-null: ybar read from the device (the LM device round trip, lm_chol_kernel)
   int beta_by_value;    // p <= STATS_BETA_MAX: beta travels in the kernel arguments (no H2D copy)
+  double theta;         // FAM_NEGBIN: the dispersion parameter (before bv, which stays the last field)
   double bv[32];        //   beta_by_value: beta[0..p)
 };
 constexpr int STATS_BETA_MAX = 32;
+
+// The negative binomial's theta terms (theta.hip theta_terms_kernel; sglm_nb_theta_terms' out[5] in this order).
+enum ThetaTerm : int { T_SCORE = 0, T_INFO = 1, T_LL = 2, T_MOM = 3, T_SUMW = 4, THETA_NT = 5 };
+struct ThetaArgs {
+  const double* y;
+  const double* eta;    // eta of the last pass (the buffer stats_kernel reads)
+  const double* prior;  // may be null
+  int64_t n;            // rows; rows >= n are never read
+  int link;             // LNK_LOG, LNK_SQRT or LNK_IDENTITY
+  double theta;
+  double* partials;     // [grid][NS]: THETA_NT sums, zeros in the other slots (reduce_stats_kernel's layout)
+};
 
 }  // namespace sglm

@@ -48,6 +48,7 @@ static InflArgs resident_args(const sglm_engine& e, int family, int link) {
   a.prior = e.dprior;
   a.family = family;
   a.link = link;
+  a.theta = e.theta;
   return a;
 }
 

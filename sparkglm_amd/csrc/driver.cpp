@@ -34,7 +34,7 @@ int family_link_valid(int family, int link) { return family_link_pair(family, li
 // such a row with a NaN unit deviance (rowmath.hpp link_row_valid), so a non-finite deviance means that
 // no valid set of coefficients was reached -- R stops there too, and like the reference this driver has
 // no step-halving.  The canonical pairs keep their behaviour on non-finite deviances.
-static const char* const kFamilyName[] = {"binomial", "gaussian", "poisson", "gamma"};
+static const char* const kFamilyName[] = {"binomial", "gaussian", "poisson", "gamma", "negative binomial"};
 static int range_error(int family, int iter) {
   char buf[160];
   std::snprintf(buf, sizeof buf, "requirement failed: no valid set of coefficients: %s left the %s range at iteration %d",
@@ -106,7 +106,9 @@ static double family_loglik(int family, const double* s, double dev, double nrow
   return s[S_LL];
 }
 
-int glm_drive(Backend& be, const sglm_glm_opts& o, sglm_preglm* out) {
+// beta_start (sglm_fit_glm_start, R's start=): the loop starts from a pass at beta_start instead of the
+// initial constant-mu pass, which then serves the null deviance alone.
+int glm_drive(Backend& be, const sglm_glm_opts& o, sglm_preglm* out, const double* beta_start) {
   if (!family_link_valid(o.family, o.link)) {
     set_error("requirement failed: unsupported family/link combination");
     return SGLM_EINVAL;
@@ -134,6 +136,13 @@ int glm_drive(Backend& be, const sglm_glm_opts& o, sglm_preglm* out) {
   double dev = fac * packed[tri_count(p) + p + S_DEV];
   if (check_range && !std::isfinite(dev)) return range_error(o.family, 0);
   const double null_dev = dev;  // GLM.scala:272 / 444
+  if (beta_start) {
+    std::memcpy(beta.data(), beta_start, sizeof(double) * (size_t)p);
+    rc = be.pass(MODE_IRLS, beta.data(), ymean, 0.0, o.family, o.link, packed.data());
+    if (rc) return rc;
+    dev = fac * packed[tri_count(p) + p + S_DEV];
+    if (check_range && !std::isfinite(dev)) return range_error(o.family, 0);
+  }
   double deltad = 1.0, d_prev = 0.0;  // d_prev: |deltad| of the iteration before (speculation)
   int iter = 0;
   if (out->dev_trace && out->max_trace > 0) out->dev_trace[0] = dev;
@@ -186,10 +195,11 @@ int glm_drive(Backend& be, const sglm_glm_opts& o, sglm_preglm* out) {
     }
   }
 
-  if (iter > 0 && be.pass_has_stats()) {  // the last pass computed them at the final mu
+  const bool at_beta = iter > 0 || beta_start;  // the last pass was an IRLS pass at beta
+  if (at_beta && be.pass_has_stats()) {  // the last pass computed them at the final mu
     std::memcpy(s.data(), packed.data() + tri_count(p) + p, sizeof(double) * NS);
   } else {
-    rc = be.stats(iter > 0 ? MODE_IRLS : init_mode, beta.data(), ymean, 0.0, o.family, o.link, s.data());
+    rc = be.stats(at_beta ? MODE_IRLS : init_mode, beta.data(), ymean, 0.0, o.family, o.link, s.data());
     if (rc) return rc;
   }
   if (s[S_BAD] > 0) {

@@ -89,7 +89,7 @@ class Backend {
   int solve_path = -1;  // enum sglm_solve_path of the last solve
 };
 
-int glm_drive(Backend& be, const sglm_glm_opts& o, sglm_preglm* out);
+int glm_drive(Backend& be, const sglm_glm_opts& o, sglm_preglm* out, const double* beta_start = nullptr);
 int lm_drive(Backend& be, sglm_prelm* out);
 // Bench / test helper: `iters` IRLS iterations (pass at beta, then solve) from beta.
 int irls_iterate(Backend& be, const sglm_glm_opts& o, double* beta, int iters, double* last_dev);

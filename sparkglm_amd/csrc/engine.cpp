@@ -31,9 +31,9 @@ using namespace sglm;
 // its passes with it; sglm_pass_kernel_for exposes it for a CPU test of the mapping).
 static int pass_kernel_choice(int64_t n_pad, int P16, bool narrow, bool wide, bool proc, int fused_split, int family,
                               int link, char* name, size_t len) {
-  static const char* fam[] = {"binomial", "gaussian", "poisson", "gamma"};
+  static const char* fam[] = {"binomial", "gaussian", "poisson", "gamma", "negbin"};
   static const char* lnk[] = {"logit", "probit", "cloglog", "identity", "log", "inverse", "sqrt"};
-  const char* f = (family >= 0 && family < 4) ? fam[family] : "?";
+  const char* f = (family >= 0 && family < 5) ? fam[family] : "?";
   // the link slot of the instantiation the launchers' dispatch picks (common.hpp dispatch_family_link):
   // the pairs without a dedicated one run their family's run-time-link instantiation
   const int il = dispatched_link(family, link);
@@ -145,6 +145,9 @@ void sglm_engine::release() {
   if (ev2) (void)hipEventDestroy(ev2);
   if (evpre) (void)hipEventDestroy(evpre);
   if (evc) (void)hipEventDestroy(evc);
+  if (evt0) (void)hipEventDestroy(evt0);
+  if (evt1) (void)hipEventDestroy(evt1);
+  evt0 = evt1 = nullptr;
   if (st) (void)hipStreamDestroy(st);
   ev0 = ev1 = ev2 = evc = evpre = nullptr;
   st = nullptr;
@@ -277,6 +280,7 @@ int sglm_engine::pass_dev(int mode, const double* beta, double mu0, double ybar,
 }
 
 int sglm_engine::pass(int mode, const double* beta, double mu0, double ybar, int family, int link, double* packed) {
+  if (int rc = theta_check(family)) return rc;
   if (group()) return group_pass(mode, beta, mu0, ybar, family, link, packed);
   const int64_t plen = packed_len(p), sc = tri_count(p) + p;
   const int R = gather_ranks() ? comm.nranks : 0;  // rank blocks of the scalars (compensated_rank_sum)
@@ -383,6 +387,7 @@ int sglm_engine::enqueue_pass(int mode, const double* beta, double mu0, double y
   a.ybar = ybar;
   a.partials = dpart;
   a.stride = stride;
+  a.theta = theta;
   // Final statistics in the narrow pass, no eta store (rowmath.hpp stats_in_pass_family):
   // binomial / logit (m = 1) in every IRLS pass -- measured faster than the lean variant, the
   // statistics hide under the stream (DESIGN 4 K1') -- and Poisson / Gamma in the deviance-only
@@ -392,7 +397,7 @@ int sglm_engine::enqueue_pass(int mode, const double* beta, double mu0, double y
   // (Poisson / Gamma: only after this data's initial pass has summed the statistics' constants.)
   a.stats_in_pass = (narrow && mode == MODE_IRLS && stats_in_pass_family(family, link) &&
                      !(family == FAM_BINOMIAL && dm) &&
-                     (family == FAM_BINOMIAL || (dev_only && consts_family == family))) ? 1 : 0;
+                     (family == FAM_BINOMIAL || (dev_only && consts_family == family)) && !want_eta) ? 1 : 0;
   if (meat_w) {
     // the sandwich's meat X' diag(omega) X (sglm_vcov_robust): a gaussian / identity pass at beta = 0
     // whose prior weights are omega; nothing of the shard's own vectors but y, no eta store, and the
@@ -525,12 +530,6 @@ int sglm_engine::group_pass(int mode, const double* beta, double mu0, double yba
   return SGLM_OK;
 }
 
-// blocks (= partials) of the statistics pass; the LM device round trip and the host path alike
-// (LM 1M x 20: 2048 blocks measured equal, 4096 +5 %: profiles/r04_lm_stats_blocks.txt)
-static int stats_blocks(int64_t rows) {
-  return (int)std::min<int64_t>(4096, std::max<int64_t>(1024, rows / 131072));
-}
-
 // LM.fit in one round trip (driver.hpp Backend::lm_device): a resident narrow shard with no
 // communicator -- the Gram pass, which also sums X'1 and y'y (narrow LMX), then lm_chol_kernel:
 // the host Cholesky, bitwise, on the device, and the residual statistics of LM.scala:160-188 from
@@ -587,6 +586,7 @@ int sglm_engine::lm_device(double* packed, double* dev_coefs, double* s, bool& d
 }
 
 int sglm_engine::stats(int mode, const double* beta, double mu0, double ybar, int family, int link, double* s) {
+  if (int rc = theta_check(family)) return rc;
   if (group()) {  // shard order, compensated (compensated_rank_sum)
     std::vector<double> blocks((size_t)NS * subs.size());
     for (size_t d = 0; d < subs.size(); ++d)
@@ -622,6 +622,7 @@ int sglm_engine::stats(int mode, const double* beta, double mu0, double ybar, in
   a.mode = mode;
   a.mu0 = mu0;
   a.ybar = ybar;
+  a.theta = theta;
   a.partials = dpart;
   // one wave per SIMD leaves the per-row chain latency-bound on large shards; small ones
   // (LM 1M x 20) keep 1024 partials; they are summed on the device (reduce_stats_kernel,
@@ -981,6 +982,11 @@ int sglm_fit_glm_external(const sglm_backend* be, sglm_allreduce_fn fn, void* co
                           sglm_preglm* out) {
   if (!be || !be->pass || !be->local_sums || be->p <= 0 || !opts || !out || !out->coefs || !out->std_err) {
     set_error("requirement failed: backend callbacks, p >= 1, opts, out");
+    return SGLM_EINVAL;
+  }
+  if (opts->family == FAM_NEGBIN) {  // the pass callback has no theta to take
+    set_error("requirement failed: the negative binomial family is not available over an external backend "
+              "(sglm_backend.pass carries no theta)");
     return SGLM_EINVAL;
   }
   ExternalBackend eb(be, fn, comm_ctx);

@@ -1,11 +1,12 @@
 // engine.hpp -- the HIP engine behind the C ABI: what its host translation units share.
-// Private to engine.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp and ingest.cpp; never included
+// Private to engine.cpp, negbin.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp and ingest.cpp; never included
 // by a .hip file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <rocblas/rocblas.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -64,6 +65,13 @@ inline void compensated_rank_sum(const double* blocks, int nranks, int64_t count
     for (int r = 0; r < nranks; ++r) neumaier_add(s, c, blocks[(int64_t)r * count + k]);
     out[k] = s + c;
   }
+}
+
+// blocks (= partials of NS doubles) of the statistics pass and of the theta kernel; the LM device round trip and the
+// host path alike.  At most 4096: ensure_workspace sizes the partials buffer for 4096 * NS doubles at least.
+// (LM 1M x 20: 2048 blocks measured equal, 4096 +5 %: profiles/r04_lm_stats_blocks.txt)
+inline int stats_blocks(int64_t rows) {
+  return (int)std::min<int64_t>(4096, std::max<int64_t>(1024, rows / 131072));
 }
 
 // ---- communicators (comm.cpp) ----
@@ -157,6 +165,14 @@ struct sglm_engine : public sglm::Backend {
   int fused_split = 1;  // SGLM_FUSED_SPLIT: 1 K1r from its default column-block count up, 0 never (K1), N >= 2 from P16 = N
   bool allow_lm_device = true;  // SGLM_LM_DEVICE=0: LM fits take the two host round trips (tests)
   bool lm_extras_pass = false;  // the next LM Gram pass also sums X'1 and y'y (lm_device, one pass)
+  // negative binomial (negbin.cpp): theta of FAM_NEGBIN passes (0: never set; a group handle and its shards
+  // hold the same value), and -- while sglm_fit_glm_nb's Poisson fit runs -- every IRLS pass stores eta (no
+  // in-pass statistics), so that the theta kernel finds the fit's eta
+  double theta = 0.0;
+  bool want_eta = false;
+  int64_t theta_launches = 0;  // theta_terms_kernel launches, and their kernel time (HIP events)
+  double theta_ms = 0.0;
+  hipEvent_t evt0 = nullptr, evt1 = nullptr;
 
   // ---- wide path (wide.hip; wide_path.cpp) ----
   bool wide = false, force_wide = false;
@@ -317,6 +333,13 @@ struct sglm_engine : public sglm::Backend {
   int group_pass(int mode, const double* beta, double mu0, double ybar, int family, int link, double* packed);
   int lm_device(double* packed, double* dev_coefs, double* s, bool& done) override;
   int stats(int mode, const double* beta, double mu0, double ybar, int family, int link, double* s) override;
+
+  // ---- negbin.cpp: theta on the handle, the theta terms ----
+  int theta_check(int family) const;  // SGLM_EINVAL: a FAM_NEGBIN call on a handle without theta
+  // {score, info, loglik (if asked), sum w (y/mu - 1)^2, sum w} at theta over the eta of the last pass,
+  // all-reduced (shards in order / rank blocks, compensated)
+  int theta_terms(int link, double th, bool loglik, double* out5);
+  int theta_terms_local(int link, double th, bool loglik, double* s);
 
   // ---- comm.cpp: the communicator ----
   sglm::CallbackRunner& runner();

@@ -321,7 +321,7 @@ __device__ __forceinline__ void row_stage(double* lds, int buf, int wb, const Pa
       // (P16 = 16: the row arithmetic of K1r's row_stage_r, so that K1 and K1r are bitwise
       // interchangeable -- tests/test_gpu_fused_split.py)
       else pass_row(FAM, LNK, a.mode, eta, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux,
-                    P16 == 16, false, nullptr, a.link);
+                    P16 == 16, false, nullptr, a.link, a.theta);
     }
     lds[G::OFF_W + wb * 2 * RB + r] = w;
     lds[G::OFF_W + wb * 2 * RB + RB + r] = wz;
@@ -792,7 +792,7 @@ __device__ __forceinline__ void row_stage_r(double* lds, int buf, const PassArgs
       if (FAM == FAM_BINOMIAL && init_fast_row(FAM, a.mode, a.m != nullptr) && y >= 0.0 && y <= 1.0)
         pass_row_init(lds + R::OFF_INIT, y, off, pw, w, wz, s_dev, s_aux);
       else pass_row(FAM, LNK, a.mode, eta, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
-                    false, nullptr, a.link);
+                    false, nullptr, a.link, a.theta);
     }
     lds[R::OFF_W + buf * 2 * RB + r] = w;
     lds[R::OFF_W + buf * 2 * RB + RB + r] = wz;

@@ -190,7 +190,8 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
         // u = w (y - mu) g'(mu): the working weight times the working residual; a row of prior weight
         // 0 contributes exactly 0 whatever its mu
         const double pw = a.prior ? a.prior[ri] : 1.0;
-        const InflRow w = influence_row(a.family, a.link, RESID_WORKING, e, a.y[ri], a.m ? a.m[ri] : 1.0, pw);
+        const InflRow w = influence_row(a.family, a.link, RESID_WORKING, e, a.y[ri], a.m ? a.m[ri] : 1.0, pw,
+                                        a.theta);
         const double u = w.w * w.resid;
         if constexpr (MODE == INFL_USCORE) {
           a.out[ri] = pw == 0.0 ? 0.0 : u;
@@ -205,7 +206,7 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
         continue;
       }
       const InflRow w = influence_row(a.family, a.link, a.resid_type, e, a.y[ri], a.m ? a.m[ri] : 1.0,
-                                      a.prior ? a.prior[ri] : 1.0);
+                                      a.prior ? a.prior[ri] : 1.0, a.theta);
       const double h = w.w * q[r];
       if (a.resid) a.resid[ri] = w.resid;
       if (a.hat) a.hat[ri] = h;

@@ -196,7 +196,11 @@ __global__ void __launch_bounds__(256) stats_kernel(StatsArgs a) {
     } else if (a.eta) {
       eta = a.eta[i];
     }
-    if constexpr (link_by_link(FAM, LNK)) {  // the non-canonical pairs: mu by the link
+    if constexpr (FAM == FAM_NEGBIN) {  // variance, deviance and log-density at the handle's theta
+      const RowAcc r = stats_row_ref_nb(link_of<LNK>(a.link), a.mode, eta, a.y[i], pw, a.mu0, a.theta);
+#pragma unroll
+      for (int k = 0; k < NS; ++k) acc.s[k] += r.s[k];
+    } else if constexpr (link_by_link(FAM, LNK)) {  // the non-canonical pairs: mu by the link
       const RowAcc r = stats_row_ref_x(FAM, link_of<LNK>(a.link), a.mode, eta, a.y[i], pw, a.mu0);
 #pragma unroll
       for (int k = 0; k < NS; ++k) acc.s[k] += r.s[k];

@@ -83,6 +83,10 @@ hipError_t launch_cluster_sum(const ClusterArgs& a, int grid, hipStream_t st, hi
 hipError_t launch_cluster_combine(const CombineArgs& a, int ncu, hipStream_t st, hipEvent_t e0 = nullptr,
                                   hipEvent_t e1 = nullptr);
 
+// theta terms of the negative binomial (theta.hip): [grid][NS] partials for launch_reduce_stats; loglik: T_LL too
+hipError_t launch_theta_terms(const ThetaArgs& a, int grid, bool loglik, hipStream_t st, hipEvent_t e0 = nullptr,
+                              hipEvent_t e1 = nullptr);
+
 // wide path (wide.hip)
 int wide_panels(int p);
 int64_t wide_stride();

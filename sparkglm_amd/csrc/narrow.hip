@@ -208,7 +208,9 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
   // IRLS passes' y log y (poisson_ylogy_table, pass_row ylogy)
   constexpr bool PTAB = !IRLS && FAM == FAM_POISSON && (G::LDS + 2 * POIS_TAB + 8) * 8 <= 160 * 1024;
   // (the y log y table serves the log link's fast path only; the LNK_RT rows take pass_row_ref)
-  constexpr bool YTAB = IRLS && FAM == FAM_POISSON && LNK == LNK_LOG && (G::LDS + POIS_TAB) * 8 <= 160 * 1024;
+  // (negative binomial / log: the same table serves its fast path's y log y)
+  constexpr bool YTAB = IRLS && (FAM == FAM_POISSON || FAM == FAM_NEGBIN) && LNK == LNK_LOG &&
+                        (G::LDS + POIS_TAB) * 8 <= 160 * 1024;
   static_assert(FAM != FAM_POISSON || PTAB || YTAB || (IRLS && LNK != LNK_LOG),
                 "the Poisson tables fit every narrow variant's LDS");
   __shared__ double lds[G::LDS + (PTAB ? 2 * POIS_TAB + 8 : (YTAB ? POIS_TAB : 0))];
@@ -414,7 +416,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
             pass_row_stats<FAM>(et, y, off, pw, w, wz, s_dev, s_aux, s_pear, s_ll, s_bad, true, ylogy);
           else if (!(PTAB && poisson_init_row(pconst, ptab, y, off, pw, w, wz, s_dev, s_aux, s_ll))) {
             pass_row(FAM, LNK, mode, et, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
-                     !IRLS, ylogy, a.link);
+                     !IRLS, ylogy, a.link, a.theta);
             if constexpr (LMX) s_pear += y * y;
             if constexpr (INIT_CONST)
               if (mode != MODE_LM_GRAM) s_ll += init_stats_const<FAM>(y, pw);
@@ -475,7 +477,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
             pass_row_stats<FAM>(eta, yv, ov, pv, w, wz, s_dev, s_aux, s_pear, s_ll, s_bad, true, ylogy);
           else if (!(PTAB && poisson_init_row(pconst, ptab, yv, ov, pv, w, wz, s_dev, s_aux, s_ll))) {
             pass_row(FAM, LNK, mode, eta, yv, mv, ov, pv, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
-                     !IRLS, ylogy, a.link);
+                     !IRLS, ylogy, a.link, a.theta);
             if constexpr (LMX) s_pear += yv * yv;
             if constexpr (INIT_CONST)
               if (mode != MODE_LM_GRAM) s_ll += init_stats_const<FAM>(yv, pv);
@@ -535,7 +537,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
           pass_row_stats<FAM>(eta, y, off, pw, w, wz, s_dev, s_aux, s_pear, s_ll, s_bad, true, ylogy);
         else if (!(PTAB && poisson_init_row(pconst, ptab, y, off, pw, w, wz, s_dev, s_aux, s_ll))) {
           pass_row(FAM, LNK, mode, eta, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
-                   !IRLS, ylogy, a.link);
+                   !IRLS, ylogy, a.link, a.theta);
           if constexpr (LMX) s_pear += y * y;
           if constexpr (INIT_CONST)
             if (mode != MODE_LM_GRAM) s_ll += init_stats_const<FAM>(y, pw);
@@ -616,7 +618,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
           pass_row_stats<FAM>(et, y, off, pw, w, wz, s_dev, s_aux, s_pear, s_ll, s_bad, true, ylogy);
         else if (!(PTAB && poisson_init_row(pconst, ptab, y, off, pw, w, wz, s_dev, s_aux, s_ll))) {
           pass_row(FAM, LNK, mode, et, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
-                   !IRLS, ylogy, a.link);
+                   !IRLS, ylogy, a.link, a.theta);
           if constexpr (LMX) s_pear += y * y;
           if constexpr (INIT_CONST)
             if (mode != MODE_LM_GRAM) s_ll += init_stats_const<FAM>(y, pw);

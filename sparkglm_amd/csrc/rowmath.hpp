@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "polygamma.hpp"
 
 namespace sglm {
 
@@ -269,6 +270,39 @@ __device__ __noinline__ RowWZ pass_row_ref_x(int fam, int lnk, int mode, double 
   return r;
 }
 
+// ---- negative binomial with a fixed theta (MASS::negative.binomial(theta)) ----
+// V = mu + mu^2 / theta; unit deviance y log(max(y, 1) / mu) - (y + theta) log((y + theta) / (mu + theta)) (family
+// factor 2); the log-density of R's dnbinom(y, theta, mu = mu).  New functions beside the four families': those
+// (variance_fn, unit_dev, pass_row_ref_x ...) stay as they are, so that their instantiations' code does not move.
+__device__ __forceinline__ double nb_variance(double mu, double theta) { return mu + (mu * mu) / theta; }
+__device__ __forceinline__ double nb_unit_dev(double y, double mu, double pw, double theta) {
+  return pw * ((y * log(fmax(y, 1.0) / mu)) - ((y + theta) * log((y + theta) / (mu + theta))));
+}
+__device__ __forceinline__ double nb_loglik_row(double y, double mu, double theta) {
+  return ((((lgamma(theta + y) - lgamma(theta)) - lgamma(y + 1.0)) + theta * log(theta)) +
+          y * log(mu + (y == 0.0 ? 1.0 : 0.0))) - (theta + y) * log(theta + mu);
+}
+// pass_row_ref_x's operation order with the negative binomial variance and deviance; the row's validity is the
+// poisson rows' rule (link_row_valid: mu finite and > 0, sqrt needs eta > 0), carried as a NaN unit deviance.
+__device__ __noinline__ RowWZ pass_row_ref_nb(int lnk, int mode, double eta, double y, double off, double pw,
+                                              double mu0, double theta) {
+  double mu;
+  if (mode == MODE_IRLS) {
+    mu = unlink_fn_x(lnk, eta);
+  } else {
+    eta = link_fn_x(lnk, mu0);
+    mu = (mode == MODE_INIT_SINGLE) ? mu0 : unlink_fn_x(lnk, eta);
+  }
+  const double g = lprime_fn_x(lnk, mu);
+  const double v = nb_variance(mu, theta);
+  RowWZ r;
+  r.w = pw * (1.0 / (v * (g * g)));
+  const double z = (eta + ((y + (-1.0 * mu)) * g)) + (-1.0 * off);
+  r.wz = r.w * z;
+  r.dev = link_row_valid(FAM_NEGBIN, lnk, eta, mu) ? nb_unit_dev(y, mode == MODE_IRLS ? mu : mu0, pw, theta) : NAN;
+  return r;
+}
+
 // The initial pass of a binomial fit without m (GLM.scala:263-272, 429-444): mu = mu0
 // (fitSingle) or unlink(link(mu0)) (fitMultiple) is the same for every row, so link, lPrime and
 // the variance are invariants of the pass; per row only z and the deviance remain.
@@ -324,7 +358,8 @@ __device__ __forceinline__ void pass_row_init(const double* c, double y, double 
 __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta, double y, double m, double off,
                                          double pw, double mu0, double ybar, bool has_m, double& w, double& wz,
                                          double& s_dev, double& s_aux, bool small_exp = false,
-                                         bool init_fast = false, const double* ylogy = nullptr, int rt_link = 0) {
+                                         bool init_fast = false, const double* ylogy = nullptr, int rt_link = 0,
+                                         double theta = 0.0) {
   (void)ybar;
   if (fam == FAM_BINOMIAL && lnk == LNK_LOGIT && mode == MODE_IRLS && !has_m && fabs(eta) < 8.0 && y >= 0.0 &&
       y <= 1.0) {
@@ -393,6 +428,31 @@ __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta,
     s_aux += pw;
     return;
   }
+  if (fam == FAM_NEGBIN && lnk == LNK_LOG && mode == MODE_IRLS && fabs(eta) < 300.0 && y >= 0.0 && y < 1e150 &&
+      theta > 1e-150 && theta < 1e150) {
+    // Negative binomial / log (MASS::negative.binomial(theta)): mu = exp(eta), g' = 1/mu, V = mu + mu^2/theta, so
+    // with r = 1/(mu + theta) and t = theta r
+    //   w = 1/(V g'^2) = mu theta/(mu + theta) = mu t,  w*z = mu t (eta - off) + (y - mu) t,
+    //   dev row = y log(max(y, 1)/mu) - (y + theta) log((y + theta)/(mu + theta))
+    //           = (y log y - y eta) - (y + theta) log((y + theta) r)
+    // -- one exp, one reciprocal and one log (y log y from the narrow kernel's table of counts, or a second
+    // log).  The range checks keep mu + theta in (1e-150, 2e150), t in (5e-281, 1] and (y + theta) r in
+    // (5e-301, 2e300): normal operands for rcp_pos / log_pos; they imply the row's validity (mu finite, > 0).
+    // Other rows take pass_row_ref_nb.
+    const double mu = small_exp ? exp_small(eta) : exp(eta);
+    const double r = rcp_pos(mu + theta);
+    const double t = theta * r;
+    const double wt = mu * t;
+    w = pw * wt;
+    wz = pw * (wt * (eta - off) + (y - mu) * t);
+    double d0;
+    if (ylogy && y < (double)POIS_TAB && y == floor(y)) d0 = ylogy[(int)y] - y * eta;
+    else d0 = y > 0.0 ? y * (log_pos(y) - eta) : 0.0;
+    const double yt = y + theta;
+    s_dev += pw * (d0 - yt * log_pos(yt * r));
+    s_aux += pw;
+    return;
+  }
   if (mode == MODE_LM_GRAM) {
     w = 1.0;
     wz = y;
@@ -409,7 +469,8 @@ __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta,
     return;
   }
   // (LNK_RT instantiations: every row takes the reference functions at the arguments' link)
-  const RowWZ r = link_by_link(fam, lnk) ? pass_row_ref_x(fam, lnk == LNK_RT ? rt_link : lnk, mode, eta, y, m, off, pw, mu0)
+  const RowWZ r = fam == FAM_NEGBIN ? pass_row_ref_nb(lnk == LNK_RT ? rt_link : lnk, mode, eta, y, off, pw, mu0, theta)
+                  : link_by_link(fam, lnk) ? pass_row_ref_x(fam, lnk == LNK_RT ? rt_link : lnk, mode, eta, y, m, off, pw, mu0)
                                          : pass_row_ref(fam, lnk, mode, eta, y, m, off, pw, mu0);
   w = r.w;
   wz = r.wz;
@@ -487,6 +548,22 @@ __device__ __noinline__ RowAcc stats_row_ref_x(int fam, int lnk, int mode, doubl
     acc.s[S_AUX0] += pw * (y / mu);
     acc.s[S_AUX1] += pw * log(mu);
   }
+  return acc;
+}
+
+// stats_row_ref_x for the negative binomial: S_LL is the whole log-likelihood sum pw dnbinom(y, theta, mu, log).
+__device__ __noinline__ RowAcc stats_row_ref_nb(int lnk, int mode, double eta, double y, double pw, double mu0,
+                                                double theta) {
+  RowAcc acc;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) acc.s[k] = 0.0;
+  const double mu = (mode == MODE_IRLS) ? unlink_fn_x(lnk, eta) : mu0;
+  const double v = nb_variance(mu, theta);
+  const double r = y + (-1.0 * mu);
+  acc.s[S_DEV] += nb_unit_dev(y, mu, pw, theta);
+  acc.s[S_PEARSON] += pw * (r * r) / v;
+  acc.s[S_SUMW] += pw;
+  acc.s[S_LL] += pw * nb_loglik_row(y, mu, theta);
   return acc;
 }
 
@@ -701,11 +778,12 @@ enum ResidType : int { RESID_RESPONSE = 0, RESID_WORKING = 1, RESID_PEARSON = 2,
 struct InflRow {
   double w, rp, resid;
 };
-__device__ __noinline__ InflRow influence_row(int fam, int lnk, int rtype, double eta, double y, double m, double pw) {
+__device__ __noinline__ InflRow influence_row(int fam, int lnk, int rtype, double eta, double y, double m, double pw,
+                                              double theta) {
   const bool x = noncanonical_pair(fam, lnk);  // the links selected by link (link_fn_x ...)
   const double mu = x ? unlink_fn_x(lnk, eta) : unlink_fn(fam, lnk, eta, m);
   const double g = x ? lprime_fn_x(lnk, mu) : lprime_fn(fam, lnk, mu, m);
-  const double v = variance_fn(fam, mu, m);
+  const double v = fam == FAM_NEGBIN ? nb_variance(mu, theta) : variance_fn(fam, mu, m);
   const double e = y + (-1.0 * mu);
   InflRow r;
   r.w = pw * (1.0 / (v * (g * g)));
@@ -717,7 +795,8 @@ __device__ __noinline__ InflRow influence_row(int fam, int lnk, int rtype, doubl
   } else if (rtype == RESID_PEARSON) {
     r.resid = r.rp;
   } else {
-    const double d = (fam == FAM_GAUSSIAN ? 1.0 : 2.0) * unit_dev(fam, y, mu, m, pw);
+    const double d = fam == FAM_NEGBIN ? 2.0 * nb_unit_dev(y, mu, pw, theta)
+                                       : (fam == FAM_GAUSSIAN ? 1.0 : 2.0) * unit_dev(fam, y, mu, m, pw);
     const double s = sqrt(fmax(d, 0.0));
     r.resid = e > 0.0 ? s : (e < 0.0 ? -s : 0.0);
   }

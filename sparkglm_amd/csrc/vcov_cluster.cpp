@@ -144,6 +144,7 @@ int sglm_engine::uscore_local(const double* beta, int family, int link) {
   a.prior = dprior;
   a.family = family;
   a.link = link;
+  a.theta = theta;
   a.need_q = 0;
   a.out = domega;
   if (n_pad > n) HIPCHK(hipMemsetAsync(domega + n, 0, sizeof(double) * (size_t)(n_pad - n), st));

@@ -458,7 +458,7 @@ __device__ __forceinline__ void wide_rows_body(const WideRowArgs& a) {
           if (a.eta_out) a.eta_out[row] = et;
         }
         pass_row(FAM, LNK, a.mode, et, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w[r], wz[r], s_dev, s_aux, false,
-                 false, nullptr, a.link);
+                 false, nullptr, a.link, a.theta);
       }
     }
 #pragma unroll
@@ -509,6 +509,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) w
 // the same budget (tests/test_links.py).
 template <int FAM, int LNK>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) wide_rows_link_ov_kernel(WideRowArgs a) {
+  if (a.xs_out) __builtin_amdgcn_s_setprio(1);
+  wide_rows_body<FAM, LNK, 2, true>(a);
+}
+
+// The negative binomial's overlapped row stage (<negbin, log> with the inline rows, <negbin, runtime>), under a
+// name of its own for the reason above: the instantiations of wide_rows_ov_kernel and wide_rows_link_ov_kernel
+// are counted and bounded per feature (tests/test_residency.py, tests/test_links.py), and so are these
+// (tests/test_negbin_api.py: two, at most 96 VGPRs, no scratch).
+template <int FAM, int LNK>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) wide_rows_nb_ov_kernel(WideRowArgs a) {
   if (a.xs_out) __builtin_amdgcn_s_setprio(1);
   wide_rows_body<FAM, LNK, 2, true>(a);
 }
@@ -687,17 +697,22 @@ int64_t wide_stride() { return (int64_t)PT * PT * 256 + PANEL; }
 SGLM_ROW_LAUNCH(wide_rows_kernel)
 SGLM_ROW_LAUNCH(wide_rows_ov_kernel)
 SGLM_ROW_LAUNCH(wide_rows_link_ov_kernel)
+SGLM_ROW_LAUNCH(wide_rows_nb_ov_kernel)
 #undef SGLM_ROW_LAUNCH
 
-// KX: the kernel of the non-canonical pairs (rowmath.hpp link_by_link)
-template <template <int, int> class K, template <int, int> class KX>
+// KX: the kernel of the non-canonical pairs (rowmath.hpp link_by_link); KN: of the negative binomial's
+template <template <int, int> class K, template <int, int> class KX, template <int, int> class KN>
 static hipError_t launch_rows_fl(int fam, int lnk, dim3 g, dim3 b, hipStream_t st, const WideRowArgs& a) {
   const bool ok = dispatch_family_link(fam, lnk, [&](auto F, auto L) {
     constexpr int f = decltype(F)::value, l = decltype(L)::value;
     // (gamma / log too: its inline fast path put the overlapped kernel 16 bytes into scratch at the 96
     // VGPR budget, and the row stage is a few per cent of a wide pass -- both wide kernels run every
     // non-canonical pair through the family's LNK_RT instantiation, so they stay bitwise alike)
-    if constexpr (l == LNK_RT || noncanonical_pair(f, l)) KX<f, LNK_RT>::go(g, b, st, a);
+    // (negative binomial: log runs its inline row stage in both kernels -- the overlapped one holds 96 VGPRs and
+    // no scratch with it, within the budget, so unlike gamma / log it need not fall back --, sqrt and identity the
+    // run-time-link rows; either way the two kernels run the same rows and stay bitwise alike)
+    if constexpr (f == FAM_NEGBIN) KN<f, l>::go(g, b, st, a);
+    else if constexpr (l == LNK_RT || noncanonical_pair(f, l)) KX<f, LNK_RT>::go(g, b, st, a);
     else K<f, l>::go(g, b, st, a);
   });
   return ok ? hipGetLastError() : hipErrorInvalidValue;
@@ -707,8 +722,9 @@ hipError_t launch_wide_rows(const WideRowArgs& a, int grid, hipStream_t st, bool
   const dim3 g(grid), b(256);
   const int fam = (a.mode == MODE_LM_GRAM) ? FAM_GAUSSIAN : a.family;
   const int lnk = (a.mode == MODE_LM_GRAM) ? LNK_IDENTITY : a.link;
-  return ov ? launch_rows_fl<wide_rows_ov_kernel_t, wide_rows_link_ov_kernel_t>(fam, lnk, g, b, st, a)
-            : launch_rows_fl<wide_rows_kernel_t, wide_rows_kernel_t>(fam, lnk, g, b, st, a);
+  return ov ? launch_rows_fl<wide_rows_ov_kernel_t, wide_rows_link_ov_kernel_t, wide_rows_nb_ov_kernel_t>(fam, lnk, g, b,
+                                                                                                          st, a)
+            : launch_rows_fl<wide_rows_kernel_t, wide_rows_kernel_t, wide_rows_kernel_t>(fam, lnk, g, b, st, a);
 }
 
 hipError_t launch_proc_gen(const ProcGenArgs& a, int grid, hipStream_t st) {

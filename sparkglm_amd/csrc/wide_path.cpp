@@ -262,6 +262,7 @@ int sglm_engine::enqueue_wide(int mode, bool has_beta, double mu0, double ybar, 
   r.mode = mode;
   r.mu0 = mu0;
   r.ybar = ybar;
+  r.theta = theta;
   r.w = dw;
   r.wz = dwz;
   r.eta_out = (mode == MODE_IRLS) ? deta : nullptr;

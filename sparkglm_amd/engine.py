@@ -29,6 +29,27 @@ class FitGLM:
 
 
 @dataclass
+class FitNB:
+    """sglm_fit_glm_nb: the last inner negative binomial fit and the estimated theta (MASS::glm.nb)."""
+    fit: FitGLM
+    theta: float
+    se_theta: float
+    twologlik: float
+    outer_iter: int
+    theta_warn: int   # bit 0: theta.ml's iteration limit reached, bit 1: estimate truncated at zero
+    converged: bool
+
+
+@dataclass
+class ThetaML:
+    """sglm_theta_ml (MASS::theta.ml)."""
+    theta: float
+    se: float
+    iters: int
+    warn: int
+
+
+@dataclass
 class FitLM:
     """PreLM (LM.scala:10-14) plus LM.fit's stdErr and sigma (LM.scala:260-263)."""
     coefs: np.ndarray
@@ -229,14 +250,76 @@ class Engine:
 
     # ---- fits ----
     def fit_glm(self, family="binomial", link="logit", tol=1e-6, verbose=False, max_iter=0, init="single",
-                npart=0, max_trace=512) -> FitGLM:
+                npart=0, max_trace=512, start=None) -> FitGLM:
+        """`start` (R's start=): coefficients the iterations begin at (sglm_fit_glm_start); dev_trace[0] is
+        then the deviance at `start`.  family "negbin" fits at the handle's theta (set_theta)."""
         o = glm_opts(family, link, tol, verbose, max_iter, init, npart)
         coefs, se = np.zeros(self.p), np.zeros(self.p)
         trace = np.full(max_trace, np.nan)
         pre = L.PreGLM(L.ptr(coefs), L.ptr(se), 0, 0, 0, 0, 0, 0, 0, L.ptr(trace), max_trace)
-        L.check(self._lib.sglm_fit_glm(self._h, C.byref(o), C.byref(pre)), "sglm_fit_glm")
+        if start is None:
+            L.check(self._lib.sglm_fit_glm(self._h, C.byref(o), C.byref(pre)), "sglm_fit_glm")
+        else:
+            b = self._beta(start)
+            L.check(self._lib.sglm_fit_glm_start(self._h, C.byref(o), L.ptr(b), C.byref(pre)), "sglm_fit_glm_start")
         return FitGLM(coefs, se, pre.deviance, pre.null_deviance, pre.pearson, pre.loglik, pre.iter, pre.nrow,
                       pre.npart, trace[: pre.iter + 1].copy())
+
+    def _beta(self, beta):
+        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+        if b.shape[0] != self.p:
+            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
+                                             f"beta {b.shape[0]} rows")
+        return b
+
+    # ---- negative binomial ----
+    def set_theta(self, theta: float):
+        """theta of the "negbin" family on this handle (sglm_set_theta): V = mu + mu^2 / theta."""
+        L.check(self._lib.sglm_set_theta(self._h, float(theta)), "sglm_set_theta")
+        return self
+
+    def get_theta(self) -> float:
+        t = C.c_double()
+        L.check(self._lib.sglm_get_theta(self._h, C.byref(t)), "sglm_get_theta")
+        return t.value
+
+    def theta_ms(self):
+        """(launches, summed kernel ms) of the theta kernel on this handle (HIP events)."""
+        k, ms = C.c_int64(), C.c_double()
+        L.check(self._lib.sglm_get_theta_ms(self._h, C.byref(k), C.byref(ms)), "sglm_get_theta_ms")
+        return k.value, ms.value
+
+    def theta_terms(self, beta, theta: float, link="log") -> np.ndarray:
+        """[score, info, loglik, sum w (y/mu - 1)^2, sum w] of the negative binomial's theta at beta."""
+        o = glm_opts("negbin", link)
+        out = np.zeros(5)
+        L.check(self._lib.sglm_nb_theta_terms(self._h, C.byref(o), L.ptr(self._beta(beta)), float(theta), L.ptr(out)),
+                "sglm_nb_theta_terms")
+        return out
+
+    def theta_ml(self, beta, link="log", limit=0, eps=0.0) -> ThetaML:
+        """MASS::theta.ml at beta (limit 0: 25, eps 0: 2^-13)."""
+        o = glm_opts("negbin", link)
+        th, se, it, warn = C.c_double(), C.c_double(), C.c_int(), C.c_int()
+        L.check(self._lib.sglm_theta_ml(self._h, C.byref(o), L.ptr(self._beta(beta)), int(limit), float(eps),
+                                        C.byref(th), C.byref(se), C.byref(it), C.byref(warn)), "sglm_theta_ml")
+        return ThetaML(th.value, se.value, it.value, warn.value)
+
+    def fit_glm_nb(self, link="log", tol=1e-6, init="single", npart=0, maxit=0, epsilon=0.0, theta_limit=0,
+                   theta_eps=0.0, max_iter=0, max_trace=512) -> FitNB:
+        """MASS::glm.nb (sglm_fit_glm_nb): theta by maximum likelihood, alternating with negative binomial
+        fits; theta stays set on the handle.  Zeros take the defaults 25 / 1e-8 / 25 / 2^-13."""
+        o = glm_opts("negbin", link, tol, False, max_iter, init, npart)
+        nbo = L.NbOpts(int(maxit), float(epsilon), int(theta_limit), float(theta_eps))
+        coefs, se = np.zeros(self.p), np.zeros(self.p)
+        trace = np.full(max_trace, np.nan)
+        pre = L.PreGLM(L.ptr(coefs), L.ptr(se), 0, 0, 0, 0, 0, 0, 0, L.ptr(trace), max_trace)
+        res = L.NbResult()
+        L.check(self._lib.sglm_fit_glm_nb(self._h, C.byref(o), C.byref(nbo), C.byref(pre), C.byref(res)),
+                "sglm_fit_glm_nb")
+        f = FitGLM(coefs, se, pre.deviance, pre.null_deviance, pre.pearson, pre.loglik, pre.iter, pre.nrow,
+                   pre.npart, trace[: pre.iter + 1].copy())
+        return FitNB(f, res.theta, res.se_theta, res.twologlik, res.outer_iter, res.theta_warn, bool(res.converged))
 
     def fit_lm(self) -> FitLM:
         p = self.p

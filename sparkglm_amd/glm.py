@@ -22,10 +22,16 @@ leaves the family's range raises IllegalArgumentException (no step-halving).  Th
 is R's logLik; `aic` stays createObj's -2 loglik + 2p (GLM.scala:70), which counts the
 coefficients only -- R's AIC(glm) for gaussian and Gamma adds 2 for the dispersion parameter,
 so it is 2 higher than `aic` here for those two families.
+`GLM.fit_nb` fits the negative binomial (links log / sqrt / identity): with `theta` given it is R's
+glm(family = MASS::negative.binomial(theta)), without it MASS::glm.nb, which estimates theta by maximum
+likelihood; the model then carries `theta`, `theta_se` and `twologlik`, its dispersion is 1, and its `aic`
+counts theta as a parameter when it was estimated (as logLik.negbin does).  `GLM.fit`'s family strings are
+unchanged: "negbin" there is an unrecognised family and fits binomial, as the reference does.
 """
 from __future__ import annotations
 
 import ctypes as C
+import re
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -85,6 +91,11 @@ class GLMModel:
     iter: int
     nrow: float
     npart: int
+    # GLM.fit_nb only: the negative binomial's theta (given or estimated), and for MASS::glm.nb fits its
+    # standard error and twice the log-likelihood
+    theta: Optional[float] = None
+    theta_se: Optional[float] = None
+    twologlik: Optional[float] = None
 
     def predict(self, newData: Frame, type: str = "response", offset: Optional[Frame] = None,
                 m: Optional[Frame] = None, device: int = 0, cov=None, dispersion: Optional[float] = None) -> Frame:
@@ -100,7 +111,7 @@ class GLMModel:
         (_dispersion).  Without `cov` the result is unchanged."""
         _require(len(set(self.xnames) - set(newData.columns)) == 0,
                  "Not all predictors in the estimation data are in the data to be predicted")
-        fam, lnk = _engine_family_link(self.family, self.link)
+        fam, lnk = _model_family_link(self)
         newX = newData.select(*self.xnames).to_matrix()
         beta = np.asarray(self.coefs, dtype=np.float64).reshape(-1)
         off = None if offset is None else offset.to_vector()
@@ -119,8 +130,8 @@ class GLMModel:
 
 def _dispersion(obj) -> float:
     """R's summary.glm rule: 1 for binomial and poisson, the Pearson estimate for gaussian and gamma."""
-    fam, _ = _engine_family_link(obj.family, obj.link)
-    return 1.0 if fam in ("binomial", "poisson") else float(obj.pDispersion)
+    fam, _ = _model_family_link(obj)
+    return 1.0 if fam in ("binomial", "poisson", "negbin") else float(obj.pDispersion)
 
 
 def _dmu_deta(link: str, eta, m=1.0):
@@ -154,6 +165,30 @@ def _engine_family_link(family: str, link: str):
     if link == "probit":
         return "binomial", "probit"
     return "binomial", "cloglog"
+
+
+def _model_family_link(obj):
+    """The engine's (family, link) of a fitted model: GLM.fit_nb's models are "negbin" (they carry theta);
+    every other model goes through GLM.fit's string dispatch."""
+    if getattr(obj, "theta", None) is not None and obj.family.lower() == "negbin":
+        _require(obj.link in L.NEGBIN_LINKS, f"family negbin supports only the {', '.join(L.NEGBIN_LINKS)} links")
+        return "negbin", obj.link
+    return _engine_family_link(obj.family, obj.link)
+
+
+def _nb_summary(text: str, obj, lib) -> str:
+    """GLM.summary's text for a GLM.fit_nb model: the AIC line carries obj.aic (which counts theta when it was
+    estimated) and a Theta block follows it.  The two anchors are sglm_glm_summary's own lines; if that layout
+    ever changes this raises instead of printing a summary without them."""
+    aic = "AIC: " + L.java_double_str(lib.sglm_sig_digits(float(obj.aic), 5))
+    th = "Theta: " + L.java_double_str(lib.sglm_sig_digits(float(obj.theta), 6))
+    if obj.theta_se is not None:
+        th += "\nStd. Err.: " + L.java_double_str(lib.sglm_sig_digits(float(obj.theta_se), 6))
+        th += "\n2 x log-likelihood: " + L.java_double_str(lib.sglm_sig_digits(float(obj.twologlik), 6))
+    text, k = re.subn(r"^AIC: .*$", lambda _: aic + "\n" + th, text, count=1, flags=re.M)
+    if k != 1:
+        raise RuntimeError("sglm_glm_summary printed no 'AIC: ' line to carry the negative binomial's AIC and theta")
+    return text
 
 
 def _check_inputs(y: Frame, x: Frame):
@@ -297,10 +332,45 @@ class GLM:
         return GLM.createObj(x, y, pre, family, link)
 
     @staticmethod
+    def fit_nb(y: Frame, x: Frame, link: str = "log", theta: Optional[float] = None, offset: Frame = None,
+               prior: Frame = None, tol: float = 1e-6, maxit: int = 0, epsilon: float = 0.0, theta_limit: int = 0,
+               theta_eps: float = 0.0, device: int = 0) -> GLMModel:
+        """Extension: the negative binomial family, V = mu + mu^2 / theta, links "log" (default), "sqrt",
+        "identity".  With `theta` it is R's glm(..., family = MASS::negative.binomial(theta)); with
+        theta=None it is MASS::glm.nb: theta by maximum likelihood, alternating with the fit (`maxit`,
+        `epsilon`: glm.control's of the alternation; `theta_limit`, `theta_eps`: theta.ml's; zeros take
+        R's defaults 25 / 1e-8 / 25 / 2^-13).  The model carries `theta`, and for glm.nb `theta_se` and
+        `twologlik`; vcov, vcov_cluster, coeftest, influence and predict work on it."""
+        _check_inputs(y, x)
+        _require(link in L.NEGBIN_LINKS, f"family negbin supports only the {', '.join(L.NEGBIN_LINKS)} links")
+        npart = x.rdd.partitions.size()
+        for extra in (offset, prior):
+            if extra is not None:
+                _require(extra.count() == y.count(), "The two DataFrames must have the same number of rows")
+        eng = _engine(device)
+        eng.set_data(x.to_matrix(), y.to_vector(), None, None if offset is None else offset.to_vector(),
+                     None if prior is None else prior.to_vector())
+        init = "single" if npart == 1 else "multiple"
+        if theta is not None:
+            eng.set_theta(theta)
+            f, th, se, tll = eng.fit_glm("negbin", link, tol=tol, init=init, npart=npart), float(theta), None, None
+        else:
+            r = eng.fit_glm_nb(link, tol=tol, init=init, npart=npart, maxit=maxit, epsilon=epsilon,
+                               theta_limit=theta_limit, theta_eps=theta_eps)
+            f, th, se, tll = r.fit, r.theta, r.se_theta, r.twologlik
+        obj = GLM.createObj(x, y, _to_pre(f), "negbin", link)
+        obj.theta, obj.theta_se, obj.twologlik = th, se, tll
+        if theta is None:
+            obj.aic += 2.0  # theta was estimated: one more parameter (logLik.negbin's df)
+        return obj
+
+    @staticmethod
     def _load(obj: GLMModel, y: Frame, x: Frame, offset, m, prior, device):
         _check_inputs(y, x)
-        fam, lnk = _engine_family_link(obj.family, obj.link)
+        fam, lnk = _model_family_link(obj)
         eng = _engine(device)
+        if fam == "negbin":
+            eng.set_theta(obj.theta)
         eng.set_data(x.select(*obj.xnames).to_matrix(), y.to_vector(), None if m is None else m.to_vector(),
                      None if offset is None else offset.to_vector(), None if prior is None else prior.to_vector())
         return eng, fam, lnk, np.asarray(obj.coefs, dtype=np.float64).reshape(-1)
@@ -368,7 +438,10 @@ class GLM:
         buf = C.create_string_buffer(int(need))
         lib.sglm_glm_summary(C.byref(s), len(obj.xnames), names, obj.yname.encode(), obj.family.encode(),
                              obj.link.encode(), buf, need)
-        return buf.value.decode()
+        text = buf.value.decode()
+        if getattr(obj, "theta", None) is not None:  # GLM.fit_nb: theta, and the AIC that counts it when estimated
+            text = _nb_summary(text, obj, lib)
+        return text
 
     @staticmethod
     def summary(obj: GLMModel) -> None:

@@ -1,4 +1,4 @@
-"""Per-kernel gfx950 disassembly of the built device objects (build/obj/{kernels,fused_odd,narrow,wide}.o;
+"""Per-kernel gfx950 disassembly of the built device objects (build/obj/{kernels,fused_odd,narrow,wide,influence,theta}.o;
 ISA_OBJDIR selects a variant build's objects).
 
     python tools/isa_dump.py OUTDIR            # one OUTDIR/<kernel>.s per kernel symbol
@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-OBJECTS = ("kernels", "fused_odd", "narrow", "wide", "influence")
+OBJECTS = ("kernels", "fused_odd", "narrow", "wide", "influence", "theta")
 
 
 def _code_objects(run):
@@ -92,19 +92,83 @@ def _write(outdir, sym, lines):
         fh.write("\n".join(lines) + "\n")
 
 
+def _normalise(text: str):
+    """A symbol's instructions without what only its place in the code object decides: the padding after its
+    end (s_nop / s_code_end) and the PC-relative offsets of its calls and constant addresses (the two adds
+    after an s_getpc_b64)."""
+    lines = text.splitlines()
+    while lines and re.match(r"(s_nop 0|s_code_end|\.\.\.|v_illegal.*)$", lines[-1]):
+        lines.pop()
+    out, pc = [], 0
+    for ln in lines:
+        if ln.startswith("s_getpc_b64"):
+            pc = 2
+        elif pc and re.match(r"s_addc?_u32 s\d+, s\d+, 0x[0-9a-f]+$", ln):
+            ln = re.sub(r"0x[0-9a-f]+$", "PCREL", ln)
+            pc -= 1
+        out.append(ln)
+    return out
+
+
+def _kernarg_only(la, lb):
+    """The (old, new) literal pairs if the only differences are offsets into the kernel-argument segment (a struct
+    that grew at its end moves the hidden arguments behind it), else None.  Such a difference is a scalar load
+    whose offset literal changed, or an `s_add_u32 sN, sM, literal` that forms the address of such an argument:
+    the add counts only if its literal pair is one a scalar load of the same symbol shows or moves by the same
+    amount as one, or if it adds to / from the low register of a pair the symbol's scalar loads use as their
+    base (the segment pointer) -- a changed scalar constant of any other kind is an instruction difference."""
+    if len(la) != len(lb):
+        return None
+    load = re.compile(r"(s_load_dword(?:x\d+)? \S+ s\[\d+:\d+\], )(0x[0-9a-f]+)$")
+    add = re.compile(r"(s_add_u32 s(\d+), s(\d+), )(0x[0-9a-f]+)$")
+    bases = {m.group(1) for ln in la for m in [re.match(r"s_load_dword(?:x\d+)? \S+ s\[(\d+):\d+\]", ln)] if m}
+    loads, adds = set(), set()
+    for x, y in zip(la, lb):
+        if x == y:
+            continue
+        mx, my = load.match(x), load.match(y)
+        if mx and my and mx.group(1) == my.group(1):
+            loads.add((int(mx.group(2), 16), int(my.group(2), 16)))
+            continue
+        mx, my = add.match(x), add.match(y)
+        if mx and my and mx.group(1) == my.group(1):
+            adds.add((int(mx.group(4), 16), int(my.group(4), 16), mx.group(2) in bases or mx.group(3) in bases))
+            continue
+        return None
+    deltas = {n - o for o, n in loads}
+    if any(not base and (o, n) not in loads and (n - o) not in deltas for o, n, base in adds):
+        return None
+    return sorted(loads | {(o, n) for o, n, _ in adds})
+
+
 def diff(a: str, b: str) -> int:
+    """Symbols whose instructions differ.  Layout-only differences (padding, PC-relative offsets) are not
+    differences; differences in kernel-argument offsets alone are listed apart with the offsets that moved;
+    symbols present in one build only are listed and counted."""
     fa, fb = set(os.listdir(a)), set(os.listdir(b))
-    bad = 0
+    bad = karg = 0
+    moved = {}
     for f in sorted(fa | fb):
         if f not in fa or f not in fb:
             print(f"only in {'B' if f not in fa else 'A'}: {f}")
-            bad += 1
             continue
-        if open(os.path.join(a, f)).read() != open(os.path.join(b, f)).read():
-            print(f"differs: {f}")
-            bad += 1
-    print(f"{len(fa & fb)} common kernels, {bad} differences")
-    return bad
+        la, lb = _normalise(open(os.path.join(a, f)).read()), _normalise(open(os.path.join(b, f)).read())
+        if la == lb:
+            continue
+        pairs = _kernarg_only(la, lb)
+        if pairs is not None:
+            txt = ", ".join(f"{o:#x}->{n:#x}" for o, n in pairs)
+            print(f"kernel-argument offsets only ({txt}): {f}")
+            moved[txt] = moved.get(txt, 0) + 1
+            karg += 1
+            continue
+        print(f"differs: {f}")
+        bad += 1
+    for txt, k in sorted(moved.items()):
+        print(f"  offsets {txt}: {k} symbols")
+    print(f"{len(fa & fb)} common symbols, {len(fa - fb)} only in A, {len(fb - fa)} only in B, {karg} with "
+          f"kernel-argument offsets moved, {bad} with other differences")
+    return bad + len(fa - fb)
 
 
 if __name__ == "__main__":
