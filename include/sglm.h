@@ -69,7 +69,8 @@ extern "C" {
                               sglm_get_sandwich_ms, enum sglm_hc_type, sglm_set_clusters, sglm_vcov_cluster,
                               sglm_get_cluster_ms, sglm_cluster_plan, sglm_set_theta, sglm_get_theta,
                               sglm_get_theta_ms, sglm_nb_theta_terms, sglm_theta_ml, sglm_fit_glm_start, sglm_fit_glm_nb
-                              (with sglm_nb_opts / sglm_nb_result); (new values only:) SGLM_SQRT and
+                              (with sglm_nb_opts / sglm_nb_result), sglm_fit_glm_fe (with sglm_fe_info),
+                              sglm_fe_pass, sglm_vcov_fe, sglm_get_fe_ms; (new values only:) SGLM_SQRT and
                               the non-canonical (family, link) pairs of enum sglm_link's table,
                               SGLM_NEGBIN and its three pairs */
 
@@ -490,6 +491,56 @@ int sglm_get_cluster_ms(sglm_engine *h, double *score_ms, double *sum_ms, double
  * outside [0, G) is SGLM_EINVAL. */
 int sglm_cluster_plan(const int32_t *ids, int64_t n, int32_t G, int64_t *tile_rows, int64_t *nseg,
                       int64_t *seg_start, int32_t *seg_cluster);
+
+/* ---- one-way fixed effects: the factor of sglm_set_clusters absorbed (fixest::feglm / fepois, Stata's
+ * xtpoisson, fe / areg, alpaca::feglm) ----
+ * The model eta_i = x_i' beta + alpha_{g(i)} + offset_i with one coefficient alpha_g per cluster, fitted by
+ * the concentrated ("within") IRLS: at (beta, alpha) one ordinary pass with the effective offset
+ * o*_i = offset_i + alpha_{g(i)} gives X'WX, X'Wz and the deviance; the group sums W_g = sum w_i,
+ * t_g = sum w_i z_i, s_g = sum w_i x_i over every row of every shard and rank give
+ *   A = X'WX - sum_g s_g s_g' / W_g,   b = X'Wz - sum_g s_g t_g / W_g,
+ *   beta+ = inv(A) b (the fit's solve rule),   alpha_g+ = alpha_g + (t_g - s_g' beta+) / W_g.
+ * By Frisch-Waugh-Lovell every iterate is that of sglm_fit_glm on [X | D], D the G dummy columns: start
+ * (the initial-mode pass, alpha = 0), stop rule, dev_trace, iter, null_deviance, pearson and loglik are
+ * sglm_fit_glm's; std_err = sqrt(diag(inv(A))), the beta block of the dummy fit's unscaled covariance.
+ * X holds no intercept and no column that is constant within every group: such a column leaves a diagonal
+ * element of A below 1e-10 of X'WX's and is SGLM_ESINGULAR.  Groups with W_g = 0 (no row, or only rows of
+ * prior weight 0) contribute nothing, their alpha is NaN, and they do not count in G_eff;
+ * df_residual = n - p - G_eff.  A group whose rows of positive prior weight all have y = 0 (poisson, negative
+ * binomial, binomial) or all y = m (binomial) has no finite alpha: sglm_fit_glm_fe checks this on the device
+ * before its first pass and returns SGLM_EINVAL naming how many such groups there are and the first.
+ *
+ * Scope: sglm_vcov_cluster's -- resident designs with p <= 256 on the fused / narrow path, else SGLM_EINVAL
+ * before any launch; collective in the same way (group handles, RCCL, caller all-reduces), with one extra
+ * all-reduce of G (p + 2) doubles (G rounded up to 32) per iteration beside the pass's; every rank ends
+ * with bitwise the same beta and alpha.  No floating-point atomics: every order of summation depends on
+ * (ids, n, p) only.  The resident data, the offset among them, and later calls of every other entry point
+ * are unchanged.  SGLM_NEGBIN fits at the handle's theta (sglm_set_theta). */
+typedef struct {
+  int32_t G_eff;      /* groups with W_g > 0 at the solution */
+  double df_residual; /* n - p - G_eff, n the global row count */
+  double weights_ms, sum_ms, combine_ms, gram_ms; /* as sglm_get_fe_ms, of the last iteration */
+} sglm_fe_info;
+/* alpha [G] out; info may be NULL. */
+int sglm_fit_glm_fe(sglm_engine *h, const sglm_glm_opts *opts, sglm_preglm *out, double *alpha, sglm_fe_info *info);
+/* The test-level step at any (beta, alpha): A [p*p] col-major, b [p], group [G*(p+2)] = s [G x p] col-major |
+ * t [G] | W [G], scalars [8] (the pass's); any output may be NULL.  beta == NULL selects opts' initial mode at
+ * mu0 = mean(y) (alpha may then be NULL: zeros).  No uninformative-group check, no absorbed-column check. */
+int sglm_fe_pass(sglm_engine *h, const sglm_glm_opts *opts, const double *beta, const double *alpha, double *A,
+                 double *b, double *group, double *scalars);
+/* The covariance of beta at (beta, alpha).  cluster == 0: inv(A), the unscaled model-based covariance
+ * (hc_type and cadjust are not read).  cluster != 0: V = a inv(A) M inv(A), clustered on the absorbed factor:
+ * M = S'S, S_g = sum_{i in g} u_i x_i - U_g s_g / W_g with U_g = sum_{i in g} u_i (the second term vanishes
+ * only at an exact solution) and u the signed score of sglm_vcov_cluster; a as sglm_vcov_cluster's with the
+ * regressor count p replaced by p + G_eff: SGLM_HC0 none, SGLM_HC1 (n - 1) / (n - p - G_eff), cadjust a further
+ * G / (G - 1); SGLM_HC2 / SGLM_HC3 are SGLM_EINVAL.  With this a, V is the beta block of sandwich::vcovCL on
+ * the dummy fit.  An alpha that is NaN (a group without weight) is read as 0.  cov, meat [p*p] col-major;
+ * meat may be NULL. */
+int sglm_vcov_fe(sglm_engine *h, const sglm_glm_opts *opts, const double *beta, const double *alpha, int cluster,
+                 int hc_type, int cadjust, double *cov, double *meat);
+/* Kernel times of the last fixed-effects step: the weights kernel, segment sums, combine, the Gram pass over
+ * the group sums (HIP events; a multi-device handle: its slowest shard; -1 before any call). */
+int sglm_get_fe_ms(sglm_engine *h, double *weights_ms, double *sum_ms, double *combine_ms, double *gram_ms);
 
 int sglm_get_stats(sglm_engine *h, sglm_stats *out);
 /* The kernel an engine would run a pass of an n x p shard with (enum sglm_pass_kernel, -1 on bad

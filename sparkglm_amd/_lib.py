@@ -41,6 +41,7 @@ EXPORTS = [
     "sglm_set_clusters", "sglm_vcov_cluster", "sglm_get_cluster_ms", "sglm_cluster_plan",
     "sglm_set_theta", "sglm_get_theta", "sglm_get_theta_ms", "sglm_nb_theta_terms", "sglm_theta_ml", "sglm_fit_glm_start",
     "sglm_fit_glm_nb",
+    "sglm_fit_glm_fe", "sglm_fe_pass", "sglm_vcov_fe", "sglm_get_fe_ms",
 ]
 PREDICT_LINK, PREDICT_RESPONSE = 0, 1
 RESID_TYPES = {"response": 0, "working": 1, "pearson": 2, "deviance": 3}  # enum sglm_resid_type
@@ -67,6 +68,11 @@ class NbOpts(C.Structure):
 class NbResult(C.Structure):
     _fields_ = [("theta", C.c_double), ("se_theta", C.c_double), ("twologlik", C.c_double),
                 ("outer_iter", C.c_int), ("theta_warn", C.c_int), ("converged", C.c_int)]
+
+
+class FeInfo(C.Structure):
+    _fields_ = [("G_eff", C.c_int32), ("df_residual", C.c_double), ("weights_ms", C.c_double),
+                ("sum_ms", C.c_double), ("combine_ms", C.c_double), ("gram_ms", C.c_double)]
 
 
 class PreLM(C.Structure):
@@ -209,6 +215,10 @@ def load():
         "sglm_fit_glm_start": ([h, C.POINTER(GlmOpts), dp, C.POINTER(PreGLM)], C.c_int),
         "sglm_fit_glm_nb": ([h, C.POINTER(GlmOpts), C.POINTER(NbOpts), C.POINTER(PreGLM), C.POINTER(NbResult)],
                             C.c_int),
+        "sglm_fit_glm_fe": ([h, C.POINTER(GlmOpts), C.POINTER(PreGLM), dp, C.POINTER(FeInfo)], C.c_int),
+        "sglm_fe_pass": ([h, C.POINTER(GlmOpts), dp, dp, dp, dp, dp, dp], C.c_int),
+        "sglm_vcov_fe": ([h, C.POINTER(GlmOpts), dp, dp, C.c_int, C.c_int, C.c_int, dp, dp], C.c_int),
+        "sglm_get_fe_ms": ([h, dp, dp, dp, dp], C.c_int),
         "sglm_cluster_plan": ([C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int64),
                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
     }

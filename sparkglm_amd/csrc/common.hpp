@@ -264,6 +264,56 @@ struct CombineArgs {
 };
 constexpr int CLUSTER_CHUNK = 64;  // rows one thread of the combine adds
 
+// Fixed-effects (within) IRLS over the cluster factor (fe.hip; fe.cpp).
+// fe_weights_kernel: one streaming read of the row vectors (never X), one value per row into `w` and two
+// sums per segment into Q [nseg][2], by kind:
+//   FE_WZ     w_i (the working weight) | sum w z, sum w     at eta (mode MODE_IRLS) or at mu0 (the init modes)
+//   FE_SCORE  u_i (the signed score)   | sum u,   0
+//   FE_CHECK  nothing                  | sum y,   sum (m - y)  (binomial; else the row count) over the rows of
+//                                        positive prior weight: the uninformative-group check
+enum FeKind : int { FE_WZ = 0, FE_SCORE = 1, FE_CHECK = 2 };
+struct FeArgs {
+  const double* y;
+  const double* eta;         // eta of the last pass (offset included); not read in the init modes
+  const double* m;           // may be null
+  const double* off;         // the effective offset o* = o + alpha_g (FE_WZ)
+  const double* prior;       // may be null
+  int64_t n, ld;             // rows; w is written up to ld (zeros past n)
+  int family, link, mode, kind;
+  double mu0, theta;
+  const int64_t* seg_start;  // the segments of sglm_set_clusters (ClusterArgs)
+  const int64_t* tile_seg;
+  int64_t ntiles;
+  double* w;                 // [ld]; null: not stored (FE_CHECK)
+  double* Q;                 // [nseg][2]
+};
+// fe_offset_kernel: out_i = off_i + alpha[cluster of row i] per segment, zeros on the rows in [n, ld)
+struct FeOffsetArgs {
+  const double* off;         // may be null
+  const double* alpha;       // [G]
+  const int64_t* seg_start;
+  const int64_t* tile_seg;
+  const int64_t* seg_cluster;  // [nseg]
+  int64_t ntiles, n, ld;
+  double* out;               // [ld]
+};
+// The group sums as one buffer (one all-reduce): S [ld x p] col-major | t [ld] | W [ld], ld = G rounded up to 32.
+// fe_alpha_kernel: alpha_g += (t_g - s_g' beta) / W_g where W_g > 0.
+// fe_scale_kernel: the design X [ld x p] and response y [ld] of the Gram pass over the groups --
+//   meat = 0: x_g = s_g / sqrt(W_g), y_g = t_g / sqrt(W_g)        (X'X = sum s s' / W, X'y = sum s t / W)
+//   meat = 1: x_g = S_g - U_g s_g / W_g, y_g = 0; S | U from `grp`, s | W from `grp_w`
+// rows with W_g = 0 (or not > 0): exact zeros.
+struct FeGroupArgs {
+  const double* grp;
+  const double* grp_w;
+  int64_t G, ld;
+  int p, meat;
+  const double* beta;        // device [p] (fe_alpha_kernel)
+  double* alpha;             // [G]
+  double* X;
+  double* y;
+};
+
 // Arguments of the final-statistics pass (stats_kernel).
 struct StatsArgs {
   const double* y;

@@ -408,6 +408,8 @@ int sglm_engine::enqueue_pass(int mode, const double* beta, double mu0, double y
     lp_stats = a.stats_in_pass != 0;
     note_kernel(mode == MODE_LM_GRAM ? FAM_GAUSSIAN : family, mode == MODE_LM_GRAM ? LNK_IDENTITY : link);
   }
+  // the fixed-effects fits' effective offset o* = o + alpha_g (fe.cpp): the shard's own offset is never written
+  if (off_override && !meat_w) a.off = off_override;
   a.eta_out = (mode == MODE_IRLS && !a.stats_in_pass && !meat_w) ? deta : nullptr;
   a.no_gram = dev_only ? 1 : 0;
   a.fused_split = fused_split;

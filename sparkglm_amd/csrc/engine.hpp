@@ -1,5 +1,5 @@
 // engine.hpp -- the HIP engine behind the C ABI: what its host translation units share.
-// Private to engine.cpp, negbin.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp and ingest.cpp; never included
+// Private to engine.cpp, negbin.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp, fe.cpp and ingest.cpp; never included
 // by a .hip file.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -273,6 +273,20 @@ struct sglm_engine : public sglm::Backend {
   // kernel times of the last sglm_vcov_cluster call: score, segment sums, combine, Gram (-1: none yet)
   double cl_ms[4] = {-1.0, -1.0, -1.0, -1.0};
 
+  // ---- fixed effects over the cluster factor (fe.hip; fe.cpp): sglm_fit_glm_fe / sglm_fe_pass / sglm_vcov_fe ----
+  int64_t cl_prow = 0;                            // rows of dP (the combine's scratch)
+  int64_t cl_segcl_off = 0;                       // offset in dclidx of seg_cluster [nseg] (as int64)
+  const double* off_override = nullptr;           // while set, the pass reads its offset here (o* = o + alpha_g)
+  double *dfo = nullptr, *dalpha = nullptr;       // o* [n_pad]; alpha [G]
+  double *dfq = nullptr, *dfqp = nullptr;         // per-segment scalar sums [nseg][2]; their combine scratch [cl_prow][2]
+  // the group sums S | t | W (common.hpp FeGroupArgs), summed over shards and ranks in place; dfg2: the
+  // w-weighted sums kept while sglm_vcov_fe forms the u-weighted ones
+  double *dfg = nullptr, *dfg2 = nullptr;
+  bool fe_stale = true;                           // dfg may hold other shards' sums: zero it before the combine
+  hipEvent_t evf[2] = {nullptr, nullptr};
+  // kernel times of the last FE step: weights, segment sums, combine, Gram over the group sums (-1: none yet)
+  double fe_ms[4] = {-1.0, -1.0, -1.0, -1.0};
+
   // ---- group: single-process multi-device handle (sglm_create_multi): the shards' engines; this
   // handle then only routes and reduces (one process owns all GPUs, as SURVEY 8(b) asks) ----
   std::vector<sglm_engine*> subs;
@@ -387,9 +401,19 @@ struct sglm_engine : public sglm::Backend {
   void free_clusters(bool inner_too);
   int set_clusters_local(const int32_t* ids, int64_t nl, int32_t G);
   int uscore_local(const double* beta, int family, int link);
+  int ensure_cl_inner();  // the internal engine whose design is [G x p]
   int cluster_sums_local();
   int cluster_sync();
   int64_t cluster_len() const { return cl_inner->n_pad * p; }  // doubles of S, padding included
+
+  // ---- fe.cpp ----
+  void free_fe();
+  int fe_prepare();
+  int64_t fe_len() const { return cl_inner->n_pad * (p + 2); }  // doubles of S | t | W, padding included
+  int fe_set_alpha(const double* alpha);  // null: zeros
+  int fe_offset_local();
+  int fe_sums_local(int kind, int mode, int family, int link, double mu0);
+  int fe_sync();
 };
 
 namespace sglm {
@@ -401,6 +425,14 @@ inline int check_handle(sglm_engine* h) {
   }
   return SGLM_OK;
 }
+
+// ---- vcov_cluster.cpp: what the fixed-effects fits share with the cluster-robust covariance ----
+// The number of clusters every shard (and every rank: one small all-reduce) declared; SGLM_EINVAL
+// on every rank when they differ or none are set.
+int cluster_count(sglm_engine* h, int32_t* G);
+// The cluster sums S (fe: the group sums S | t | W, sglm_engine::dfg) summed in place over the handle's
+// shards or ranks; every rank (a group: shard 0) ends with bitwise the same sums.
+int sum_cluster_scores(sglm_engine* h, bool fe = false);
 
 // ---- diagnostics.cpp: what the covariance estimators share ----
 // inv(X'WX) at beta (collective over a communicator), the bread of both sandwich estimators

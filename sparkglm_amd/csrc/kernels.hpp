@@ -83,6 +83,14 @@ hipError_t launch_cluster_sum(const ClusterArgs& a, int grid, hipStream_t st, hi
 hipError_t launch_cluster_combine(const CombineArgs& a, int ncu, hipStream_t st, hipEvent_t e0 = nullptr,
                                   hipEvent_t e1 = nullptr);
 
+// fixed-effects IRLS (fe.hip): per-row weights / scores and their per-segment sums, the effective offset,
+// the fixed-effect update and the scaling of the group sums for the Gram pass over them
+int fe_grid(int ncu, int64_t ntiles);
+hipError_t launch_fe_weights(const FeArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+hipError_t launch_fe_offset(const FeOffsetArgs& a, int grid, hipStream_t st);
+hipError_t launch_fe_alpha(const FeGroupArgs& a, hipStream_t st);
+hipError_t launch_fe_scale(const FeGroupArgs& a, hipStream_t st);
+
 // theta terms of the negative binomial (theta.hip): [grid][NS] partials for launch_reduce_stats; loglik: T_LL too
 hipError_t launch_theta_terms(const ThetaArgs& a, int grid, bool loglik, hipStream_t st, hipEvent_t e0 = nullptr,
                               hipEvent_t e1 = nullptr);

@@ -14,6 +14,7 @@ void sglm_engine::free_clusters(bool inner_too) {
   if (dclidx) (void)hipFree(dclidx);
   dclidx = nullptr;
   dev_free({&dR, &dP});
+  free_fe();
   cl_levels.clear();
   cl_G = 0;
   cl_nseg = cl_ntiles = 0;
@@ -43,7 +44,7 @@ int sglm_engine::set_clusters_local(const int32_t* ids, int64_t nl, int32_t G) {
     return SGLM_EINVAL;
   }
   const int64_t ntiles = (n + CLUSTER_TILE_ROWS - 1) / CLUSTER_TILE_ROWS;
-  // seg_start [nseg + 2] | tile_seg [ntiles + 1] | cl_seg [nseg] | the levels' chunk_start, chunk_dst
+  // seg_start [nseg + 2] | tile_seg [ntiles + 1] | cl_seg [nseg] | the levels' chunk_start, chunk_dst | seg_cluster [nseg]
   std::vector<int64_t> idx((size_t)(nseg + 2 + ntiles + 1 + nseg));
   std::vector<int32_t> seg_cluster((size_t)nseg);
   std::vector<int64_t> cl_ptr((size_t)G + 1, 0);
@@ -100,6 +101,9 @@ int sglm_engine::set_clusters_local(const int32_t* ids, int64_t nl, int32_t G) {
     prow += out;
     cur.swap(next);
   }
+  cl_segcl_off = (int64_t)idx.size();  // seg_cluster [nseg]: the fixed-effects offset kernel's (fe.hip)
+  idx.insert(idx.end(), seg_cluster.begin(), seg_cluster.end());
+  cl_prow = prow;
   hipError_t e = hipMalloc(&dclidx, sizeof(int64_t) * idx.size());
   if (e == hipSuccess) e = hipMalloc(&dR, sizeof(double) * (size_t)std::max<int64_t>(nseg * p, 1));
   if (e == hipSuccess && prow > 0) e = hipMalloc(&dP, sizeof(double) * (size_t)(prow * p));
@@ -152,9 +156,8 @@ int sglm_engine::uscore_local(const double* beta, int family, int link) {
   return SGLM_OK;
 }
 
-// Segment sums of u x, then the cluster sums S into the internal engine's design: enqueued on the
-// stream after uscore_local
-int sglm_engine::cluster_sums_local() {
+// The internal engine on this device whose design is the G x p matrix of cluster sums
+int sglm_engine::ensure_cl_inner() {
   HIPCHK(hipSetDevice(device));
   if (!cl_inner)
     if (int rc = sglm_create_device(device, &cl_inner)) return rc;
@@ -164,6 +167,13 @@ int sglm_engine::cluster_sums_local() {
     cl_inner->written.assign(1, std::make_pair((int64_t)0, (int64_t)cl_G));
     HIPCHK(hipStreamSynchronize(cl_inner->st));  // its zero fill, before this stream writes S there
   }
+  return SGLM_OK;
+}
+
+// Segment sums of u x, then the cluster sums S into the internal engine's design: enqueued on the
+// stream after uscore_local
+int sglm_engine::cluster_sums_local() {
+  if (int rc = ensure_cl_inner()) return rc;
   // The combine rewrites the rows of the clusters that have a segment on this shard and no others.  The
   // rest must be zero: S is cleared after new ids, and after every call whose cross-shard sum was
   // written into it (sglm_vcov_cluster marks it) -- a lone shard's S keeps its zero rows from call to call.
@@ -220,17 +230,18 @@ int sglm_engine::cluster_sync() {
 // S summed over the handle's shards or ranks, a plain sum that leaves every rank (a group: shard 0)
 // with bitwise the same S: the group's RCCL all-reduce or its host sum in shard order, the engine's
 // RCCL communicator, or the caller's all-reduce on device or host buffers.
-static int sum_cluster_scores(sglm_engine* h) {
+int sglm::sum_cluster_scores(sglm_engine* h, bool fe) {
   const std::vector<sglm_engine*>& shards = h->shards();
   sglm_engine* s0 = shards[0];
-  const int64_t len = s0->cluster_len();
+  const int64_t len = fe ? s0->fe_len() : s0->cluster_len();
+  auto buf = [fe](sglm_engine* s) { return fe ? s->dfg : s->cl_inner->dX; };
   if (h->group()) {
     const int D = (int)shards.size();
     if (!h->gcomms.empty()) {
       ncclResult_t r = ncclGroupStart();
       for (int d = 0; d < D && r == ncclSuccess; ++d)
-        r = ncclAllReduce(shards[d]->cl_inner->dX, shards[d]->cl_inner->dX, (size_t)len, ncclFloat64, ncclSum,
-                          h->gcomms[d], shards[d]->st);
+        r = ncclAllReduce(buf(shards[d]), buf(shards[d]), (size_t)len, ncclFloat64, ncclSum, h->gcomms[d],
+                          shards[d]->st);
       const ncclResult_t r2 = ncclGroupEnd();
       if (r != ncclSuccess || r2 != ncclSuccess) {
         set_error(std::string("RCCL ncclAllReduce (group, cluster sums): ") +
@@ -253,27 +264,54 @@ static int sum_cluster_scores(sglm_engine* h) {
     std::vector<double> sum((size_t)len), part((size_t)len);
     for (int d = 0; d < D; ++d) {
       HIPCHK(hipSetDevice(shards[d]->device));
-      HIPCHK(hipMemcpy(d == 0 ? sum.data() : part.data(), shards[d]->cl_inner->dX, sizeof(double) * len,
+      HIPCHK(hipMemcpy(d == 0 ? sum.data() : part.data(), buf(shards[d]), sizeof(double) * len,
                        hipMemcpyDeviceToHost));
       if (d > 0)
         for (int64_t k = 0; k < len; ++k) sum[(size_t)k] += part[(size_t)k];
     }
     HIPCHK(hipSetDevice(s0->device));
-    HIPCHK(hipMemcpy(s0->cl_inner->dX, sum.data(), sizeof(double) * len, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(buf(s0), sum.data(), sizeof(double) * len, hipMemcpyHostToDevice));
     h->comm.ms += now_ms() - t0;
     return SGLM_OK;
   }
   if (h->comm.kind == 0) return SGLM_OK;
   HIPCHK(hipSetDevice(h->device));
   if (h->comm_on_device()) {
-    if (int rc = h->allreduce_device(h->cl_inner->dX, len)) return rc;
+    if (int rc = h->allreduce_device(buf(h), len)) return rc;
     HIPCHK(hipStreamSynchronize(h->st));
     return SGLM_OK;
   }
   std::vector<double> host((size_t)len);
-  HIPCHK(hipMemcpy(host.data(), h->cl_inner->dX, sizeof(double) * len, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(host.data(), buf(h), sizeof(double) * len, hipMemcpyDeviceToHost));
   if (int rc = h->allreduce_host(host.data(), len)) return rc;
-  HIPCHK(hipMemcpy(h->cl_inner->dX, host.data(), sizeof(double) * len, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(buf(h), host.data(), sizeof(double) * len, hipMemcpyHostToDevice));
+  return SGLM_OK;
+}
+
+// Every shard of the handle declared the same number of clusters, and so did every rank of its
+// communicator (one small all-reduce: collective), or every rank fails.
+int sglm::cluster_count(sglm_engine* h, int32_t* Gout) {
+  const std::vector<sglm_engine*>& shards = h->shards();
+  int32_t G = shards[0]->cl_G;
+  for (const sglm_engine* s : shards) G = s->cl_G == G ? G : 0;
+  if (!h->group() && h->comm.kind != 0) {
+    // every rank declared the same G, or every rank fails: G = 65536 a + b, and the values a_r are all
+    // equal iff R sum a_r^2 = (sum a_r)^2 (every term exact in fp64); a rank without clusters joins with 0
+    const double a = (double)(G >> 16), b = (double)(G & 0xffff);
+    double v[5] = {1.0, a, a * a, b, b * b};
+    if (int rc = h->allreduce_small(v, 5)) return rc;
+    if (v[0] * v[2] != v[1] * v[1] || v[0] * v[4] != v[3] * v[3]) {
+      set_error("requirement failed: every rank of the communicator declares the same number of clusters G "
+                "(sglm_set_clusters; this rank: " + std::to_string(G) + ")");
+      return SGLM_EINVAL;
+    }
+  }
+  if (G < 1) {
+    set_error("requirement failed: cluster ids of the resident rows (sglm_set_clusters; a call that replaces the "
+              "data drops them)");
+    return SGLM_EINVAL;
+  }
+  *Gout = G;
   return SGLM_OK;
 }
 
@@ -337,30 +375,13 @@ int sglm_vcov_cluster(sglm_engine* h, const sglm_glm_opts* opts, const double* b
     set_error("the multi-device handle's RCCL group was aborted by an earlier failure; create a new handle");
     return SGLM_ECOMM;
   }
-  const std::vector<sglm_engine*>& shards = h->shards();
-  int32_t G = shards[0]->cl_G;
-  for (const sglm_engine* s : shards) G = s->cl_G == G ? G : 0;
-  if (!h->group() && h->comm.kind != 0) {
-    // every rank declared the same G, or every rank fails: G = 65536 a + b, and the values a_r are all
-    // equal iff R sum a_r^2 = (sum a_r)^2 (every term exact in fp64); a rank without clusters joins with 0
-    const double a = (double)(G >> 16), b = (double)(G & 0xffff);
-    double v[5] = {1.0, a, a * a, b, b * b};
-    if (int rc = h->allreduce_small(v, 5)) return rc;
-    if (v[0] * v[2] != v[1] * v[1] || v[0] * v[4] != v[3] * v[3]) {
-      set_error("requirement failed: every rank of the communicator declares the same number of clusters G "
-                "(sglm_set_clusters; this rank: " + std::to_string(G) + ")");
-      return SGLM_EINVAL;
-    }
-  }
-  if (G < 1) {
-    set_error("requirement failed: cluster ids of the resident rows (sglm_set_clusters; a call that replaces the "
-              "data drops them)");
-    return SGLM_EINVAL;
-  }
+  int32_t G = 0;
+  if (int rc = cluster_count(h, &G)) return rc;
   if (cadjust && G < 2) {
     set_error("requirement failed: cadjust (the factor G / (G - 1)) needs G >= 2 clusters");
     return SGLM_EINVAL;
   }
+  const std::vector<sglm_engine*>& shards = h->shards();
   const int64_t p = h->ncols();
   std::vector<double> C((size_t)(p * p)), M((size_t)(p * p)), x((size_t)p);
   if (int rc = vcov_impl(h, opts, beta, C.data())) return rc;

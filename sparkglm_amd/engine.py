@@ -41,6 +41,16 @@ class FitNB:
 
 
 @dataclass
+class FitFE:
+    """sglm_fit_glm_fe: the fit of beta (as sglm_fit_glm's), the fixed effects alpha [G] (NaN: a group without
+    weight), the number of groups with weight and df_residual = n - p - G_eff."""
+    fit: FitGLM
+    alpha: np.ndarray
+    G_eff: int
+    df_residual: float
+
+
+@dataclass
 class ThetaML:
     """sglm_theta_ml (MASS::theta.ml)."""
     theta: float
@@ -477,6 +487,7 @@ class Engine:
         clears.  A call that replaces the data (set_data, reserve, synth, ...) drops the clusters."""
         if ids is None:
             L.check(self._lib.sglm_set_clusters(self._h, None, 0, 0), "sglm_set_clusters")
+            self._nclusters = 0
             return self
         ids = np.asarray(ids).reshape(-1)
         if G is None:
@@ -489,6 +500,7 @@ class Engine:
         codes = np.ascontiguousarray(ids, dtype=np.int32)
         L.check(self._lib.sglm_set_clusters(self._h, codes.ctypes.data_as(C.POINTER(C.c_int32)), codes.shape[0],
                                             int(G)), "sglm_set_clusters")
+        self._nclusters = int(G)  # the length of the fixed-effects calls' alpha
         return self
 
     def vcov_cluster(self, beta, family="binomial", link="logit", type="HC1", cadjust=True, return_meat=False):
@@ -517,6 +529,74 @@ class Engine:
         call (HIP events)."""
         t = [C.c_double() for _ in range(4)]
         L.check(self._lib.sglm_get_cluster_ms(self._h, *[C.byref(v) for v in t]), "sglm_get_cluster_ms")
+        return tuple(v.value for v in t)
+
+    # ---- one-way fixed effects over the factor of set_clusters ----
+    def fit_glm_fe(self, family="poisson", link="log", tol=1e-6, verbose=False, max_iter=0, init="single",
+                   npart=0, max_trace=512) -> FitFE:
+        """The GLM with one fixed effect per cluster of set_clusters, absorbed (sglm_fit_glm_fe;
+        fixest::feglm): every iterate is that of fit_glm on [X | dummies].  X holds no intercept."""
+        o = glm_opts(family, link, tol, verbose, max_iter, init, npart)
+        coefs, se = np.zeros(self.p), np.zeros(self.p)
+        trace = np.full(max_trace, np.nan)
+        pre = L.PreGLM(L.ptr(coefs), L.ptr(se), 0, 0, 0, 0, 0, 0, 0, L.ptr(trace), max_trace)
+        alpha = np.zeros(max(self._G(), 1))
+        info = L.FeInfo()
+        L.check(self._lib.sglm_fit_glm_fe(self._h, C.byref(o), C.byref(pre), L.ptr(alpha), C.byref(info)),
+                "sglm_fit_glm_fe")
+        f = FitGLM(coefs, se, pre.deviance, pre.null_deviance, pre.pearson, pre.loglik, pre.iter, pre.nrow,
+                   pre.npart, trace[: pre.iter + 1].copy())
+        return FitFE(f, alpha[: self._G()], info.G_eff, info.df_residual)
+
+    def _G(self) -> int:
+        return int(getattr(self, "_nclusters", 0))
+
+    def _alpha(self, alpha):
+        a = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+        if a.shape[0] != self._G():
+            raise L.IllegalArgumentException(f"requirement failed: alpha has {a.shape[0]} entries for "
+                                             f"{self._G()} clusters (set_clusters)")
+        return a
+
+    def fe_pass(self, beta=None, alpha=None, family="poisson", link="log", init="single", sums=True):
+        """One fixed-effects step at (beta, alpha) (sglm_fe_pass): A, b, the group sums s [G x p], t [G],
+        W [G] and the pass's scalars.  beta=None: the initial mode at mean(y) (alpha=None: zeros).
+        sums=False: (A, b, scalars) only -- the G (p + 2) group sums are not copied to the host."""
+        o = glm_opts(family, link, init=init)
+        p, G = self.p, self._G()
+        A, b, s = np.zeros((p, p), order="F"), np.zeros(p), np.zeros(L.NS)
+        grp = np.zeros(max(G, 1) * (p + 2)) if sums else None
+        bb = None if beta is None else self._beta(beta)
+        aa = None if alpha is None else self._alpha(alpha)
+        L.check(self._lib.sglm_fe_pass(self._h, C.byref(o), L.ptr(bb), L.ptr(aa), A.ctypes.data_as(L.dp), L.ptr(b),
+                                       L.ptr(grp), L.ptr(s)), "sglm_fe_pass")
+        if not sums:
+            return A, b, s
+        S = grp[: G * p].reshape((G, p), order="F")
+        return A, b, S, grp[G * p: G * (p + 1)].copy(), grp[G * (p + 1): G * (p + 2)].copy(), s
+
+    def vcov_fe(self, beta, alpha, family="poisson", link="log", cluster=True, type="HC1", cadjust=True,
+                return_meat=False):
+        """The covariance of beta at (beta, alpha) of a fixed-effects fit (sglm_vcov_fe): inv(A) with
+        cluster=False, else clustered on the absorbed factor -- the beta block of sandwich::vcovCL on the
+        dummy fit (`type` "HC0" | "HC1" with p + G_eff regressors, `cadjust`)."""
+        if cluster and type not in L.CLUSTER_TYPES:
+            raise L.IllegalArgumentException(f"requirement failed: with clusters, type must be one of "
+                                             f"{list(L.CLUSTER_TYPES)}, got {type!r}")
+        o = glm_opts(family, link)
+        b, a = self._beta(beta), self._alpha(alpha)
+        cov = np.zeros((self.p, self.p), order="F")
+        meat = np.zeros((self.p, self.p), order="F") if return_meat else None
+        L.check(self._lib.sglm_vcov_fe(self._h, C.byref(o), L.ptr(b), L.ptr(a), int(bool(cluster)),
+                                       L.HC_TYPES.get(type, 0), int(bool(cadjust)), cov.ctypes.data_as(L.dp),
+                                       None if meat is None else meat.ctypes.data_as(L.dp)), "sglm_vcov_fe")
+        return (cov, meat) if return_meat else cov
+
+    def fe_ms(self):
+        """Kernel times (weights, segment sums, combine, the Gram pass over the group sums) of the last
+        fixed-effects step (HIP events)."""
+        t = [C.c_double() for _ in range(4)]
+        L.check(self._lib.sglm_get_fe_ms(self._h, *[C.byref(v) for v in t]), "sglm_get_fe_ms")
         return tuple(v.value for v in t)
 
     def influence_ms(self) -> float:

@@ -96,9 +96,15 @@ class GLMModel:
     theta: Optional[float] = None
     theta_se: Optional[float] = None
     twologlik: Optional[float] = None
+    # GLM.fit_fe only: the absorbed factor's effects (label -> alpha; NaN: a group without weight), the groups
+    # and rows dropped as uninformative (all y = 0, or all y = m)
+    fixef: Optional[dict] = None
+    fe_dropped_groups: int = 0
+    fe_dropped_rows: int = 0
 
     def predict(self, newData: Frame, type: str = "response", offset: Optional[Frame] = None,
-                m: Optional[Frame] = None, device: int = 0, cov=None, dispersion: Optional[float] = None) -> Frame:
+                m: Optional[Frame] = None, device: int = 0, cov=None, dispersion: Optional[float] = None,
+                fe: Optional[Frame] = None) -> Frame:
         """Extension (the reference has no GLM predict): (index, value) rows of the
         linear predictor newX * coefs (+ offset) on the "link" scale, or of mu = unlink(eta, m)
         on the "response" scale (m = binomial trials, default 1) -- R's predict.glm(type=).
@@ -108,7 +114,10 @@ class GLMModel:
         With `cov` (the unscaled covariance of GLM.vcov) the frame gains an `se` column, R's
         se.fit: sqrt(dispersion * x' cov x) on the link scale (sglm_predict_new_se), times
         |dmu/deta| on the response scale (the delta method).  `dispersion` defaults to R's rule
-        (_dispersion).  Without `cov` the result is unchanged."""
+        (_dispersion).  Without `cov` the result is unchanged.
+
+        A GLM.fit_fe model takes `fe`, one column with each new row's label of the absorbed factor: the
+        label's alpha is added to the offset, and a label the fit has not seen predicts NaN."""
         _require(len(set(self.xnames) - set(newData.columns)) == 0,
                  "Not all predictors in the estimation data are in the data to be predicted")
         fam, lnk = _model_family_link(self)
@@ -116,6 +125,13 @@ class GLMModel:
         beta = np.asarray(self.coefs, dtype=np.float64).reshape(-1)
         off = None if offset is None else offset.to_vector()
         mv = None if m is None else m.to_vector()
+        if self.fixef is not None:
+            _require(fe is not None and len(fe.columns) == 1, "a fixed-effects model predicts with fe, one column "
+                     "of labels")
+            _require(fe.count() == newData.count(), "The two DataFrames must have the same number of rows")
+            off = fe_offsets(self.fixef, fe[fe.columns[0]], off)
+        else:
+            _require(fe is None, "fe belongs to a GLM.fit_fe model")
         vals = _engine(device).predict_new(newX, beta, fam, lnk, type, off, mv)
         cols = {"index": np.arange(len(vals), dtype=np.int64), "value": vals}
         if cov is not None:
@@ -264,6 +280,41 @@ def _coef_table(names, beta, V, pval) -> Frame:
                   "pvalue": np.array([pval(float(t)) for t in stat])})
 
 
+# ---- one-way fixed effects (GLM.fit_fe): the array logic, no device ----
+def fe_codes(labels):
+    """(unique labels, dense codes) of a factor of any dtype (np.unique)."""
+    uniq, codes = np.unique(np.asarray(labels).reshape(-1), return_inverse=True)
+    return uniq, codes.reshape(-1).astype(np.int64)
+
+
+def fe_drop_intercept(X, names):
+    """X without its intercept columns (every entry exactly 1): the fixed effects absorb the intercept."""
+    X = np.asarray(X, dtype=np.float64)
+    keep = [j for j in range(X.shape[1]) if not (X.shape[0] > 0 and np.all(X[:, j] == 1.0))]
+    return np.asfortranarray(X[:, keep]), [names[j] for j in keep]
+
+
+def fe_uninformative(codes, G, y, family, m=None, prior=None):
+    """Mask [G] of the groups without a finite fixed effect: the rows of positive prior weight all have
+    y = 0 (poisson, negbin, binomial) or all y = m (binomial).  A group with no such row is not one."""
+    if family not in ("binomial", "poisson", "negbin"):
+        return np.zeros(G, dtype=bool)
+    y = np.asarray(y, dtype=np.float64)
+    pos = np.ones(len(y), dtype=bool) if prior is None else np.asarray(prior) > 0
+    a = np.bincount(codes[pos], weights=y[pos], minlength=G)
+    other = (np.ones(len(y)) if m is None else np.asarray(m, dtype=np.float64)) - y if family == "binomial" \
+        else np.ones(len(y))
+    b = np.bincount(codes[pos], weights=other[pos], minlength=G)
+    return (a == 0) != (b == 0)
+
+
+def fe_offsets(fixef, labels, offset=None):
+    """offset + alpha[label] per row; NaN where the label is not among the fitted effects."""
+    labels = np.asarray(labels).reshape(-1)
+    a = np.array([fixef.get(l.item() if hasattr(l, "item") else l, np.nan) for l in labels], dtype=np.float64)
+    return a if offset is None else a + np.asarray(offset, dtype=np.float64)
+
+
 class GLM:
     """Namespace mirroring `object GLM` (GLM.scala:55-1026)."""
 
@@ -365,6 +416,90 @@ class GLM:
         return obj
 
     @staticmethod
+    def _fe_data(y, x, fe, family, link, offset, m, prior, drop_uninformative, quiet=False):
+        """The arrays of a fixed-effects fit: the intercept removed, the labels coded, uninformative groups
+        dropped.  Returns (X, names, y, m, offset, prior, labels, codes, dropped groups, dropped rows)."""
+        _check_inputs(y, x)
+        _require(len(fe.columns) == 1, "The 'fe' DataFrame must have only one column")
+        n = y.count()
+        for extra in (fe, offset, m, prior):
+            if extra is not None:
+                _require(extra.count() == n, "The two DataFrames must have the same number of rows")
+        fam = family.lower()
+        if fam == "negbin":
+            _require(link in L.NEGBIN_LINKS, f"family negbin supports only the {', '.join(L.NEGBIN_LINKS)} links")
+            lnk = link
+        else:
+            fam, lnk = _engine_family_link(family, link)
+        X, names = fe_drop_intercept(x.to_matrix(), x.columns)
+        _require(len(names) >= 1, "x holds no column beside the intercept, which the fixed effects absorb")
+        vec = lambda f: None if f is None else f.to_vector()
+        yv, mv, ov, pv = y.to_vector(), vec(m), vec(offset), vec(prior)
+        labels, codes = fe_codes(fe[fe.columns[0]])
+        bad = fe_uninformative(codes, len(labels), yv, fam, mv, pv)
+        ngroups = nrows = 0
+        if bad.any() and drop_uninformative:
+            keep = ~bad[codes]
+            ngroups, nrows = int(bad.sum()), int((~keep).sum())
+            if not quiet:
+                print(f"NOTE: {ngroups} fixed effect(s) ({nrows} rows) removed because of only 0"
+                      f"{' (or only m)' if fam == 'binomial' else ''} outcomes.")
+            X, yv = np.asfortranarray(X[keep]), yv[keep]
+            mv, ov, pv = (None if v is None else v[keep] for v in (mv, ov, pv))
+            labels, codes = fe_codes(labels[codes[keep]])
+        return fam, lnk, X, names, yv, mv, ov, pv, labels, codes, ngroups, nrows
+
+    @staticmethod
+    def fit_fe(y: Frame, x: Frame, fe: Frame, family: str = "poisson", link: str = "log", offset: Frame = None,
+               m: Frame = None, prior: Frame = None, drop_uninformative: bool = True, tol: float = 1e-6,
+               verbose: bool = False, theta: Optional[float] = None, device: int = 0) -> GLMModel:
+        """Extension: the GLM with one fixed effect per level of `fe` (one column of labels of any dtype),
+        absorbed rather than expanded into dummy columns (fixest::feglm / fepois, Stata's xtpoisson, fe):
+        coefficients, standard errors, deviances and iterations are those of GLM.fit on [x | dummies of fe].
+        An intercept column of `x` is removed (the effects absorb it); a column that is constant within
+        every level raises MatrixSingularException.  Groups whose outcomes are all 0 (binomial: or all m)
+        have no finite effect: they are dropped with a note, as fixest does (drop_uninformative=False: the
+        engine refuses the fit).  The model carries `fixef` (label -> alpha), dfResidual = n - p - G_eff and
+        the counts of dropped groups and rows; family "negbin" fits at the given `theta`.  For binomial
+        models with few rows per level the estimates carry the incidental-parameters bias of every
+        dummy-variable fit (the engine applies no correction)."""
+        fam, lnk, X, names, yv, mv, ov, pv, labels, codes, ngroups, nrows = GLM._fe_data(
+            y, x, fe, family, link, offset, m, prior, drop_uninformative)
+        eng = _engine(device)
+        if fam == "negbin":
+            _require(theta is not None, "family negbin needs theta (GLM.fit_nb estimates it without fixed effects)")
+            eng.set_theta(theta)
+        eng.set_data(X, yv, mv, ov, pv)
+        eng.set_clusters(codes, len(labels))
+        npart = x.rdd.partitions.size()
+        r = eng.fit_glm_fe(fam, lnk, tol=tol, verbose=verbose, init="single" if npart == 1 else "multiple",
+                           npart=npart)
+        obj = GLM.createObj(x.select(*names), y, _to_pre(r.fit), "negbin" if fam == "negbin" else family, link)
+        p = len(names)
+        obj.dfResidual, obj.dfNull = float(r.df_residual), float(r.fit.nrow - 1.0)
+        obj.pDispersion = obj.pearson / obj.dfResidual
+        obj.aic = -2.0 * obj.loglik + 2.0 * (p + r.G_eff)  # createObj's rule with the effects counted
+        obj.theta = None if fam != "negbin" else float(theta)
+        obj.fixef = {(l.item() if hasattr(l, "item") else l): float(a) for l, a in zip(labels, r.alpha)}
+        obj.fe_dropped_groups, obj.fe_dropped_rows = ngroups, nrows
+        return obj
+
+    @staticmethod
+    def _load_fe(obj: GLMModel, y, x, fe, offset, m, prior, device):
+        """The model's estimation data on the engine with its factor as clusters, and (beta, alpha)."""
+        _require(obj.fixef is not None, "fe belongs to a GLM.fit_fe model")
+        fam, lnk, X, names, yv, mv, ov, pv, labels, codes, _, _ = GLM._fe_data(
+            y, x.select(*obj.xnames), fe, obj.family, obj.link, offset, m, prior, True, quiet=True)
+        eng = _engine(device)
+        if fam == "negbin":
+            eng.set_theta(obj.theta)
+        eng.set_data(X, yv, mv, ov, pv)
+        eng.set_clusters(codes, len(labels))
+        _require(all(l in obj.fixef for l in labels.tolist()), "fe holds a label the model was not fitted with")
+        alpha = fe_offsets(obj.fixef, labels)
+        return eng, fam, lnk, np.asarray(obj.coefs, dtype=np.float64).reshape(-1), alpha
+
+    @staticmethod
     def _load(obj: GLMModel, y: Frame, x: Frame, offset, m, prior, device):
         _check_inputs(y, x)
         fam, lnk = _model_family_link(obj)
@@ -380,10 +515,26 @@ class GLM:
              device: int = 0, type: str = "const") -> np.ndarray:
         """Extension: the unscaled covariance inv(X'WX) at the fitted coefficients (R's
         summary(fit)$cov.unscaled); multiply by the dispersion for vcov(fit).  `type` "HC0".."HC3":
-        the sandwich covariance (sandwich::vcovHC) instead, which is final -- no dispersion applies."""
+        the sandwich covariance (sandwich::vcovHC) instead, which is final -- no dispersion applies.
+        (A GLM.fit_fe model: GLM.vcov_fe, which takes the factor.)"""
+        _require(getattr(obj, "fixef", None) is None, "a fixed-effects model needs its factor: GLM.vcov_fe(obj, y, x, fe)")
         _check_cov_type(type)
         eng, fam, lnk, beta = GLM._load(obj, y, x, offset, m, prior, device)
         return eng.vcov(beta, fam, lnk) if type == "const" else eng.vcov_robust(beta, fam, lnk, type=type)
+
+    @staticmethod
+    def vcov_fe(obj: GLMModel, y: Frame, x: Frame, fe: Frame, offset: Frame = None, m: Frame = None,
+                prior: Frame = None, device: int = 0, type: str = "const", cadjust: bool = True) -> np.ndarray:
+        """Extension: the covariance of a GLM.fit_fe model's coefficients on its estimation data, `fe` its
+        factor.  `type` "const": inv(A), the beta block of the dummy fit's unscaled covariance (multiply by
+        the dispersion); "HC0" / "HC1": clustered on `fe` (sglm_vcov_fe), the beta block of
+        sandwich::vcovCL on the dummy fit, `cadjust` as GLM.vcov_cluster -- final.  (GLM.vcov keeps its
+        signature; a fixed-effects model is refused there.)"""
+        if type != "const":
+            _check_cluster_type(type)
+        eng, fam, lnk, beta, alpha = GLM._load_fe(obj, y, x, fe, offset, m, prior, device)
+        return eng.vcov_fe(beta, alpha, fam, lnk, cluster=type != "const", type=type if type != "const" else "HC0",
+                           cadjust=cadjust)
 
     @staticmethod
     def vcov_cluster(obj: GLMModel, y: Frame, x: Frame, cluster: Frame, offset: Frame = None, m: Frame = None,
@@ -398,11 +549,20 @@ class GLM:
 
     @staticmethod
     def coeftest(obj: GLMModel, y: Frame, x: Frame, offset: Frame = None, m: Frame = None, prior: Frame = None,
-                 device: int = 0, type: str = "HC3", cluster: Frame = None, cadjust: bool = True) -> Frame:
+                 device: int = 0, type: str = "HC3", cluster: Frame = None, cadjust: bool = True,
+                 fe: Frame = None) -> Frame:
         """Extension: lmtest::coeftest(fit, vcov. = vcovHC(fit, type)) -- name, estimate, robust
         standard error sqrt(diag V), z statistic and its two-sided normal p-value.  With `cluster` (one
         column of labels) the covariance is vcovCL(fit, cluster, type, cadjust) and `type` must be "HC0"
-        or "HC1"."""
+        or "HC1".  A GLM.fit_fe model takes its factor `fe` and is clustered on it by default (`type` "HC1"
+        unless "HC0" or "const" is given)."""
+        if fe is not None or getattr(obj, "fixef", None) is not None:
+            _require(cluster is None, "a fixed-effects model is clustered on its own factor fe")
+            t = type if type in ("const", "HC0", "HC1") else "HC1"
+            _require(fe is not None and getattr(obj, "fixef", None) is not None, "fe belongs to a GLM.fit_fe model, which needs it")
+            V = GLM.vcov_fe(obj, y, x, fe, offset, m, prior, device, t, cadjust)
+            beta = np.asarray(obj.coefs, dtype=np.float64).reshape(-1)
+            return _coef_table(obj.xnames, beta, V, L.load().sglm_pval_normal)
         if cluster is not None:
             V = GLM.vcov_cluster(obj, y, x, cluster, offset, m, prior, device, type, cadjust)
             beta = np.asarray(obj.coefs, dtype=np.float64).reshape(-1)
