@@ -70,7 +70,9 @@ extern "C" {
                               sglm_get_cluster_ms, sglm_cluster_plan, sglm_set_theta, sglm_get_theta,
                               sglm_get_theta_ms, sglm_nb_theta_terms, sglm_theta_ml, sglm_fit_glm_start, sglm_fit_glm_nb
                               (with sglm_nb_opts / sglm_nb_result), sglm_fit_glm_fe (with sglm_fe_info),
-                              sglm_fe_pass, sglm_vcov_fe, sglm_get_fe_ms; (new values only:) SGLM_SQRT and
+                              sglm_fe_pass, sglm_vcov_fe, sglm_get_fe_ms, sglm_set_fe2, sglm_fe2_plan,
+                              sglm_fit_glm_fe2 (with sglm_fe2_opts / sglm_fe2_info), sglm_fe2_pass,
+                              sglm_vcov_fe2, sglm_get_fe2_ms; (new values only:) SGLM_SQRT and
                               the non-canonical (family, link) pairs of enum sglm_link's table,
                               SGLM_NEGBIN and its three pairs */
 
@@ -541,6 +543,83 @@ int sglm_vcov_fe(sglm_engine *h, const sglm_glm_opts *opts, const double *beta, 
 /* Kernel times of the last fixed-effects step: the weights kernel, segment sums, combine, the Gram pass over
  * the group sums (HIP events; a multi-device handle: its slowest shard; -1 before any call). */
 int sglm_get_fe_ms(sglm_engine *h, double *weights_ms, double *sum_ms, double *combine_ms, double *gram_ms);
+
+/* ---- two-way fixed effects: a second absorbed factor beside the one of sglm_set_clusters (fixest::feglm /
+ * fepois with two factors: unit x time panels, gravity models, worker x firm) ----
+ * The model eta_i = x_i' beta + alpha_{g(i)} + gamma_{h(i)} + offset_i.  Factor 1 (G levels) is the factor of
+ * sglm_set_clusters, factor 2 (H levels) that of sglm_set_fe2.  At (beta, alpha, gamma) one ordinary pass with
+ * the effective offset o* = offset + alpha_g + gamma_h gives w, z, X'WX and X'Wz.  With M = [X | z], the level
+ * sums S1 [G x (p+1)], S2 [H x (p+1)] of w M and the level weights W1, W2, the concentrated system is
+ *   [A | b] = X'W[X | z] - S_X' Y,   Y = [a ; c] a solution of K Y = S, K = D'WD of the never formed dummies,
+ * and Y comes from block Gauss-Seidel sweeps on the level coefficients (alternating projections):
+ *   a_g <- (S1_g - sum_{i in g} w_i c_{h(i)}) / W1_g,   c_h <- (S2_h - sum_{i in h} w_i a_{g(i)}) / W2_h.
+ * Then beta+ = inv(A) b, alpha+ = alpha + a_z - a_X beta+, gamma+ = gamma + c_z - c_X beta+.  No demeaned copy
+ * of X is stored.  The sweeps of an iteration start from the Y of the one before (zero at the first) and stop
+ * when the largest column-wise relative change of Y over one full sweep (max |change| / max |Y| per column
+ * over both factors, then the maximum over the columns) is <= sweep_tol.  A factor-2 level that is the only
+ * one of its component is an exact null direction: its c stays 0, and when every factor-2 level is such
+ * (H = 1, or factor 2 a function of factor 1) one sweep is exact and is all that runs.
+ *
+ * K is singular with one null vector per connected component of the bipartite graph on the levels.  The
+ * components are counted over all declared rows: a row of prior weight 0 still links its two levels.  Within
+ * each component gamma of the lowest factor-2 code is 0 and alpha takes up the shift, so (alpha, gamma) are the
+ * coefficients of the dummy fit on [X | D1 | D2 without those columns].  A level without weight has a = c = 0
+ * and a NaN effect.  df_residual = n - p - (G_eff + H_eff - ncomp), fixest's count.
+ *
+ * sglm_set_fe2 declares the second factor: dense codes 0 <= ids2[i] < H, the rules of sglm_set_clusters (local,
+ * NULL clears, dropped whenever the resident data are replaced).  It requires sglm_set_clusters; replacing or
+ * clearing the clusters drops it.  The host sorts the rows by code (stable: a level's rows ascend), cuts each
+ * level's rows into chunks of a compile-time length and keeps n_chunk <= H + ceil(n / chunk) rows of sums:
+ * the memory does not depend on how the two factors interleave.
+ *
+ * Scope: sglm_fit_glm_fe's, narrowed to one device without a communicator (a multi-device handle or a handle
+ * with a communicator is SGLM_EINVAL before any launch).  No floating-point atomics: every order of summation
+ * depends on (ids1, ids2, n, p) only, results are run-to-run bitwise identical.  The resident data, the offset,
+ * the clusters and every other entry point behave as before. */
+typedef struct {
+  double sweep_tol; /* 0: 1e-12 */
+  int max_sweeps;   /* 0: 10000 (fixest's fixef.iter); reaching it is SGLM_EINVAL */
+} sglm_fe2_opts;
+typedef struct {
+  int32_t G_eff, H_eff; /* levels with positive weight at the solution */
+  int32_t ncomp;        /* connected components of the level graph over the declared rows */
+  int32_t sweeps_last;  /* sweeps of the last iteration */
+  int64_t sweeps_total;
+  double df_residual;   /* n - p - (G_eff + H_eff - ncomp) */
+  double weights_ms, sum1_ms, sum2_ms, sweep_ms, cross_ms; /* as sglm_get_fe2_ms, of the last iteration */
+} sglm_fe2_info;
+int sglm_set_fe2(sglm_engine *h, const int32_t *ids2, int64_t n_local, int32_t H);
+/* The engine's plan for two factors (no device is touched): *chunk_len (a compile-time constant), *nchunk,
+ * chunk_start [nchunk + 1] (positions in list), chunk_level [nchunk], list [n] (the rows ordered by factor-2
+ * code, ascending within a code), *ncomp and comp_low [ncomp <= H] (each component's lowest factor-2 code,
+ * ascending).  Any output may be NULL (query *nchunk first).  A code out of range is SGLM_EINVAL. */
+int sglm_fe2_plan(const int32_t *ids1, const int32_t *ids2, int64_t n, int32_t G, int32_t H, int64_t *chunk_len,
+                  int64_t *nchunk, int64_t *chunk_start, int32_t *chunk_level, int64_t *list, int32_t *ncomp,
+                  int32_t *comp_low);
+/* The fit: glm_drive over the two-way step, so start, stop rule, trace, null deviance, final statistics and
+ * solve rule are sglm_fit_glm's.  alpha [G], gamma [H] out; fe2 and info may be NULL.  The absorbed-column
+ * check of sglm_fit_glm_fe carries over (SGLM_ESINGULAR naming the column), and so does the uninformative-level
+ * check, on both factors before the first pass (SGLM_EINVAL with a count and the first offender, naming the
+ * factor). */
+int sglm_fit_glm_fe2(sglm_engine *h, const sglm_glm_opts *opts, const sglm_fe2_opts *fe2, sglm_preglm *out,
+                     double *alpha, double *gamma, sglm_fe2_info *info);
+/* The test-level step at any (beta, alpha, gamma), the sweeps started from zero: A [p*p] col-major, b [p],
+ * group1 [G*(p+2)] = S1_X [G x p] col-major | t1 | W1, group2 [H*(p+2)] likewise, Y [(G+H)*(p+1)] col-major
+ * (a above c), scalars [8], *sweeps; any output may be NULL.  beta == NULL selects opts' initial mode (alpha and
+ * gamma may then be NULL: zeros).  No uninformative-level check, no absorbed-column check. */
+int sglm_fe2_pass(sglm_engine *h, const sglm_glm_opts *opts, const sglm_fe2_opts *fe2, const double *beta,
+                  const double *alpha, const double *gamma, double *A, double *b, double *group1, double *group2,
+                  double *Y, double *scalars, int *sweeps);
+/* The covariance of beta at (beta, alpha, gamma).  cluster == 0: inv(A).  cluster != 0: clustered on factor 1,
+ * V = a inv(A) M inv(A), M = S'S, S_g = sum_{i in g} u_i x_i - U_g a_g - sum_{i in g} u_i c_{h(i)} with a, c the
+ * X columns of Y; a is sglm_vcov_fe's with p + G_eff replaced by p + G_eff + H_eff - ncomp.  SGLM_HC2 / SGLM_HC3
+ * are SGLM_EINVAL.  A NaN effect is read as 0. */
+int sglm_vcov_fe2(sglm_engine *h, const sglm_glm_opts *opts, const sglm_fe2_opts *fe2, const double *beta,
+                  const double *alpha, const double *gamma, int cluster, int hc_type, int cadjust, double *cov,
+                  double *meat);
+/* Kernel times of the last two-way step, ms [5]: weights, factor-1 sums, factor-2 sums, sweeps, cross product
+ * (HIP events; -1 before any call). */
+int sglm_get_fe2_ms(sglm_engine *h, double *ms);
 
 int sglm_get_stats(sglm_engine *h, sglm_stats *out);
 /* The kernel an engine would run a pass of an n x p shard with (enum sglm_pass_kernel, -1 on bad

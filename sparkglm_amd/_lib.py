@@ -42,6 +42,7 @@ EXPORTS = [
     "sglm_set_theta", "sglm_get_theta", "sglm_get_theta_ms", "sglm_nb_theta_terms", "sglm_theta_ml", "sglm_fit_glm_start",
     "sglm_fit_glm_nb",
     "sglm_fit_glm_fe", "sglm_fe_pass", "sglm_vcov_fe", "sglm_get_fe_ms",
+    "sglm_set_fe2", "sglm_fe2_plan", "sglm_fit_glm_fe2", "sglm_fe2_pass", "sglm_vcov_fe2", "sglm_get_fe2_ms",
 ]
 PREDICT_LINK, PREDICT_RESPONSE = 0, 1
 RESID_TYPES = {"response": 0, "working": 1, "pearson": 2, "deviance": 3}  # enum sglm_resid_type
@@ -73,6 +74,16 @@ class NbResult(C.Structure):
 class FeInfo(C.Structure):
     _fields_ = [("G_eff", C.c_int32), ("df_residual", C.c_double), ("weights_ms", C.c_double),
                 ("sum_ms", C.c_double), ("combine_ms", C.c_double), ("gram_ms", C.c_double)]
+
+
+class Fe2Opts(C.Structure):
+    _fields_ = [("sweep_tol", C.c_double), ("max_sweeps", C.c_int)]
+
+
+class Fe2Info(C.Structure):
+    _fields_ = [("G_eff", C.c_int32), ("H_eff", C.c_int32), ("ncomp", C.c_int32), ("sweeps_last", C.c_int32),
+                ("sweeps_total", C.c_int64), ("df_residual", C.c_double), ("weights_ms", C.c_double),
+                ("sum1_ms", C.c_double), ("sum2_ms", C.c_double), ("sweep_ms", C.c_double), ("cross_ms", C.c_double)]
 
 
 class PreLM(C.Structure):
@@ -219,6 +230,17 @@ def load():
         "sglm_fe_pass": ([h, C.POINTER(GlmOpts), dp, dp, dp, dp, dp, dp], C.c_int),
         "sglm_vcov_fe": ([h, C.POINTER(GlmOpts), dp, dp, C.c_int, C.c_int, C.c_int, dp, dp], C.c_int),
         "sglm_get_fe_ms": ([h, dp, dp, dp, dp], C.c_int),
+        "sglm_set_fe2": ([h, C.POINTER(C.c_int32), C.c_int64, C.c_int32], C.c_int),
+        "sglm_fe2_plan": ([C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.c_int32,
+                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                           C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
+        "sglm_fit_glm_fe2": ([h, C.POINTER(GlmOpts), C.POINTER(Fe2Opts), C.POINTER(PreGLM), dp, dp,
+                              C.POINTER(Fe2Info)], C.c_int),
+        "sglm_fe2_pass": ([h, C.POINTER(GlmOpts), C.POINTER(Fe2Opts), dp, dp, dp, dp, dp, dp, dp, dp, dp,
+                           C.POINTER(C.c_int)], C.c_int),
+        "sglm_vcov_fe2": ([h, C.POINTER(GlmOpts), C.POINTER(Fe2Opts), dp, dp, dp, C.c_int, C.c_int, C.c_int, dp, dp],
+                          C.c_int),
+        "sglm_get_fe2_ms": ([h, dp], C.c_int),
         "sglm_cluster_plan": ([C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int64),
                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
     }
@@ -260,6 +282,30 @@ def cluster_plan(ids, G: int):
     check(lib.sglm_cluster_plan(ip, n, int(G), None, None, start.ctypes.data_as(C.POINTER(C.c_int64)),
                                 clus.ctypes.data_as(C.POINTER(C.c_int32))), "sglm_cluster_plan")
     return tile.value, start, clus
+
+
+def fe2_plan(ids1, ids2, G: int, H: int):
+    """dict(chunk_len, chunk_start [nchunk + 1], chunk_level [nchunk], list [n], ncomp, comp_low [ncomp]): the
+    engine's plan for two factors with dense codes (sglm_fe2_plan; no GPU) -- factor 2's rows ordered by code,
+    cut into chunks, and the connected components of the level graph with each one's lowest factor-2 code."""
+    import numpy as np
+    ids1 = np.ascontiguousarray(ids1, dtype=np.int32).reshape(-1)
+    ids2 = np.ascontiguousarray(ids2, dtype=np.int32).reshape(-1)
+    if ids1.shape != ids2.shape:
+        raise IllegalArgumentException("requirement failed: ids1 and ids2 have the same number of rows")
+    n = ids1.shape[0]
+    lib = load()
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a.size else None
+    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    clen, nch, ncomp = C.c_int64(), C.c_int64(), C.c_int32()
+    check(lib.sglm_fe2_plan(ip(ids1), ip(ids2), n, int(G), int(H), C.byref(clen), C.byref(nch), None, None, None,
+                            C.byref(ncomp), None), "sglm_fe2_plan")
+    start, level = np.zeros(nch.value + 1, dtype=np.int64), np.zeros(max(nch.value, 1), dtype=np.int32)
+    rows, low = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(ncomp.value, 1), dtype=np.int32)
+    check(lib.sglm_fe2_plan(ip(ids1), ip(ids2), n, int(G), int(H), None, None, lp(start), ip(level), lp(rows), None,
+                            ip(low)), "sglm_fe2_plan")
+    return dict(chunk_len=clen.value, chunk_start=start, chunk_level=level[: nch.value], list=rows[:n],
+                ncomp=ncomp.value, comp_low=low[: ncomp.value])
 
 
 def last_error() -> str:

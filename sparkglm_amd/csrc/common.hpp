@@ -314,6 +314,119 @@ struct FeGroupArgs {
   double* y;
 };
 
+// Two-way fixed effects: a second absorbed factor beside the cluster factor (fe2.hip; fe2.cpp).
+// Factor 2's rows are listed per level in ascending order (a stable counting sort by code) and each level's
+// list is cut into chunks of FE2_CHUNK positions; the chunks, already ordered by level, feed combine_kernel.
+constexpr int FE2_CHUNK = 128;
+// fe2_rows_kernel: one value (two for FE_CHECK) per row, the arithmetic of fe_weights_kernel's rows
+//   FE_WZ     out0 = w z
+//   FE_CHECK  out0 = y, out1 = m - y (binomial; else 1) on the rows of positive prior weight, else 0
+struct Fe2RowsArgs {
+  const double* y;
+  const double* eta;
+  const double* m;           // may be null
+  const double* off;         // the effective offset o* (FE_WZ)
+  const double* prior;       // may be null
+  int64_t n, ld;             // rows; the outputs are written up to ld (zeros past n)
+  int family, link, mode, kind;
+  double mu0, theta;
+  double* out0;
+  double* out1;              // FE_CHECK only
+};
+// fe2_list_sum_kernel: R[k, j] = sum_{q in chunk k} v[row] X[row, j] (j < p), r0[row] (j = p), r1[row]
+// (j = p + 1), row = list[q], positions in ascending order.  p = 0: only the two row vectors are summed.
+struct Fe2ListSumArgs {
+  const double* X;           // col-major, leading dimension ld
+  int64_t ld;
+  int p;
+  const double* v;
+  const double* r0;
+  const double* r1;
+  const int64_t* list;       // [n] rows ordered by factor-2 level, ascending within a level
+  const int64_t* chunk_start;  // [nchunk + 1] positions in list
+  int64_t nchunk;
+  double* R;                 // [nchunk][p + 2]
+  const int64_t* order;      // [nchunk] the chunks by their first row (null: as they lie): work unit u takes chunk order[u]
+};
+// fe2_gather_kernel: R[k, j] = sum_{q in unit k} v[row] src[id[row], j], j < nc, row = list[q] (list null:
+// row = q), positions in ascending order; unit k is [start[k], start[k + 1]).
+struct Fe2GatherArgs {
+  const double* v;
+  const int32_t* id;         // [n] the level of the other factor, validated on the host
+  const double* src;         // row-major level matrix, leading dimension lds
+  int64_t lds;
+  int nc;
+  const int64_t* list;
+  const int64_t* start;      // [nunit + 1]
+  int64_t nunit;
+  double* R;                 // [nunit][nc]
+  const int64_t* order;      // [nunit] or null, as Fe2ListSumArgs::order
+};
+// fe2_update_kernel: Y[l, j] = (S[l, j] - T[l, j]) / W_l, 0 where W_l = 0 or the level is pinned; the largest
+// |change| and |Y| of column j go to stop[j] and stop[ldy + j] (integer max on the bit patterns).
+struct Fe2UpdateArgs {
+  const double* S;           // col-major sums S | t | W (p + 2 columns), leading dimension ldS
+  const double* T;           // col-major (p + 1 columns), leading dimension ldS
+  int64_t ldS, L;
+  int p;
+  const int32_t* pin;        // may be null
+  double* Y;                 // row-major [L][ldy]
+  int64_t ldy;
+  unsigned long long* stop;  // [2 ldy]
+};
+// fe2_cross_kernel: per-slice partials of S_X' Y over the levels of both factors on fp64 MFMA;
+// part [nslice[0] + nslice[1]][PR][PC] row-major, PR = 16 ceil(p / 16), PC = 16 ceil((p + 1) / 16).
+struct Fe2CrossArgs {
+  const double* S[2];
+  int64_t ldS[2];
+  const double* Y[2];
+  int64_t L[2], slice_rows[2];
+  int nslice[2];
+  int p;
+  int64_t ldy;
+  double* part;
+};
+// fe2_offset_kernel: out_i = off_i + alpha[id1_i] + gamma[id2_i], zeros on the rows in [n, ld)
+struct Fe2OffsetArgs {
+  const double* off;         // may be null
+  const double* alpha;
+  const double* gamma;
+  const int32_t* id1;
+  const int32_t* id2;
+  int64_t n, ld;
+  double* out;
+};
+// fe2_effect_kernel: eff_l += Y[l, p] - sum_j Y[l, j] beta_j where W_l > 0.
+// fe2_normalise_kernel: the shift of a level's component (gamma at the component's lowest factor-2 code)
+// taken off gamma and added to alpha.
+struct Fe2EffectArgs {
+  const double* Y;
+  int64_t ldy, L;
+  int p;
+  const double* W;           // [L]
+  const double* beta;
+  double* eff;               // [L]
+};
+struct Fe2NormArgs {
+  double* alpha;
+  double* gamma;
+  const double* gamma_raw;   // a copy of gamma taken before the kernel
+  const int32_t* comp1;      // [G] component of each level (-1: no rows)
+  const int32_t* comp2;      // [H]
+  const int32_t* low;        // [ncomp] lowest factor-2 code of each component
+  int64_t G, H;
+};
+// fe2_meat_kernel: the rows S_g = Su_g - U_g a_g - Tu_g of the clustered meat into a design X [ld x p], y = 0
+struct Fe2MeatArgs {
+  const double* Su;          // col-major S | U | . of the u-weighted sums, leading dimension ld
+  const double* Tu;          // col-major gather sums of u c, leading dimension ld
+  const double* Y1;          // row-major [G][ldy]
+  int64_t G, ld, ldy;
+  int p;
+  double* X;
+  double* y;
+};
+
 // Arguments of the final-statistics pass (stats_kernel).
 struct StatsArgs {
   const double* y;

@@ -287,6 +287,13 @@ struct sglm_engine : public sglm::Backend {
   // kernel times of the last FE step: weights, segment sums, combine, Gram over the group sums (-1: none yet)
   double fe_ms[4] = {-1.0, -1.0, -1.0, -1.0};
 
+  // ---- two-way fixed effects (fe2.hip; fe2.cpp): the second factor of sglm_set_fe2, its row lists, the
+  // level matrices of the sweeps and their scratch; dropped with the clusters ----
+  struct Fe2State;
+  Fe2State* fe2 = nullptr;
+  // kernel times of the last two-way step: weights, factor-1 sums, factor-2 sums, sweeps, cross product
+  double fe2_ms[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};
+
   // ---- group: single-process multi-device handle (sglm_create_multi): the shards' engines; this
   // handle then only routes and reduces (one process owns all GPUs, as SURVEY 8(b) asks) ----
   std::vector<sglm_engine*> subs;
@@ -414,6 +421,9 @@ struct sglm_engine : public sglm::Backend {
   int fe_offset_local();
   int fe_sums_local(int kind, int mode, int family, int link, double mu0);
   int fe_sync();
+
+  // ---- fe2.cpp ----
+  void free_fe2();
 };
 
 namespace sglm {
@@ -433,6 +443,15 @@ int cluster_count(sglm_engine* h, int32_t* G);
 // The cluster sums S (fe: the group sums S | t | W, sglm_engine::dfg) summed in place over the handle's
 // shards or ranks; every rank (a group: shard 0) ends with bitwise the same sums.
 int sum_cluster_scores(sglm_engine* h, bool fe = false);
+
+// ---- fe.cpp: what the two-way fixed-effects fits (fe2.cpp) share with the one-way ones ----
+// what every fixed-effects entry point requires, before any launch; the buffers of a step
+int fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G);
+// the group sums of `kind` (common.hpp FeKind) over the cluster factor into shard 0's dfg, synchronised
+int fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0);
+// SGLM_ESINGULAR naming column j, which the fixed effects absorb
+int absorbed_error(int64_t j);
+constexpr double FE_ABSORBED_RATIO = 1e-10;  // A_jj below this part of X'WX_jj: fixest's collin.tol
 
 // ---- diagnostics.cpp: what the covariance estimators share ----
 // inv(X'WX) at beta (collective over a communicator), the bread of both sandwich estimators

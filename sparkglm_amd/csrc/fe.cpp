@@ -21,9 +21,8 @@
 
 using namespace sglm;
 
-// A column whose within-group weighted sum of squares A_jj is below this part of X'WX_jj is constant within
-// every group (an intercept among them): absorbed by the fixed effects, A is singular.  fixest's collin.tol.
-static constexpr double FE_ABSORBED_RATIO = 1e-10;
+// A column whose within-group weighted sum of squares A_jj is below FE_ABSORBED_RATIO (engine.hpp) of X'WX_jj
+// is constant within every group (an intercept among them): absorbed by the fixed effects, A is singular.
 
 void sglm_engine::free_fe() {
   dev_free({&dfo, &dalpha, &dfq, &dfqp, &dfg, &dfg2});
@@ -186,8 +185,10 @@ struct FeScope {
   }
 };
 
+}  // namespace
+
 // what every entry point requires, before any launch; collective (cluster_count)
-int fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G) {
+int sglm::fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G) {
   if (!opts || !family_link_valid(opts->family, opts->link)) {
     set_error("requirement failed: opts with a supported family/link");
     return SGLM_EINVAL;
@@ -205,6 +206,8 @@ int fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G) {
     if (int rc = s->fe_prepare()) return rc;
   return SGLM_OK;
 }
+
+namespace {
 
 // kernel times of the step just synchronised: the slowest shard
 int fe_times(sglm_engine* h, bool rows) {
@@ -228,8 +231,10 @@ int fe_times(sglm_engine* h, bool rows) {
   return SGLM_OK;
 }
 
+}  // namespace
+
 // The group sums of `kind` over every shard and rank: shard 0 of every rank ends with bitwise the same dfg
-int fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0) {
+int sglm::fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0) {
   const std::vector<sglm_engine*>& shards = h->shards();
   for (sglm_engine* s : shards)
     if (int rc = s->fe_sums_local(kind, mode, family, link, mu0)) return rc;
@@ -241,6 +246,14 @@ int fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, doub
     for (sglm_engine* s : shards) s->fe_stale = true;
   return sum_cluster_scores(h, true);
 }
+
+int sglm::absorbed_error(int64_t j) {
+  set_error("breeze.linalg.MatrixSingularException: column " + std::to_string(j) + " of X is constant within every "
+            "group (an intercept, or a regressor that only varies between groups): the fixed effects absorb it");
+  return SGLM_ESINGULAR;
+}
+
+namespace {
 
 // alpha += (t - s' beta) / W from the sums of the last step, on shard 0; a group's other shards get a copy
 int fe_alpha_step(sglm_engine* h, const double* beta) {
@@ -288,12 +301,6 @@ int fe_group_gram(sglm_engine* h, bool meat, double* packed) {
   if (int rc = in->pass(MODE_LM_GRAM, nullptr, 0.0, 0.0, FAM_GAUSSIAN, LNK_IDENTITY, packed)) return rc;
   h->fe_ms[3] = in->last_pass_ms;
   return SGLM_OK;
-}
-
-int absorbed_error(int64_t j) {
-  set_error("breeze.linalg.MatrixSingularException: column " + std::to_string(j) + " of X is constant within every "
-            "group (an intercept, or a regressor that only varies between groups): the fixed effects absorb it");
-  return SGLM_ESINGULAR;
 }
 
 // One step at the shards' (alpha, o*): packed = lower tri A | b | the pass's scalars, all-reduced

@@ -91,6 +91,19 @@ hipError_t launch_fe_offset(const FeOffsetArgs& a, int grid, hipStream_t st);
 hipError_t launch_fe_alpha(const FeGroupArgs& a, hipStream_t st);
 hipError_t launch_fe_scale(const FeGroupArgs& a, hipStream_t st);
 
+// two-way fixed effects (fe2.hip): the sums over factor 2's row lists, the gathers of the sweeps, the level
+// update with its stop-rule maxima, the cross product S_X' Y, the offset and the effects
+int fe2_grid(int ncu, int64_t units);
+hipError_t launch_fe2_rows(const Fe2RowsArgs& a, hipStream_t st);
+hipError_t launch_fe2_list_sum(const Fe2ListSumArgs& a, int ncu, hipStream_t st);
+hipError_t launch_fe2_gather(const Fe2GatherArgs& a, int ncu, hipStream_t st);
+hipError_t launch_fe2_update(const Fe2UpdateArgs& a, hipStream_t st);
+hipError_t launch_fe2_cross(const Fe2CrossArgs& a, double* out, hipStream_t st);  // out [PR][PC]: the slices summed in order
+hipError_t launch_fe2_offset(const Fe2OffsetArgs& a, hipStream_t st);
+hipError_t launch_fe2_effect(const Fe2EffectArgs& a, hipStream_t st);
+hipError_t launch_fe2_normalise(const Fe2NormArgs& a, hipStream_t st);
+hipError_t launch_fe2_meat(const Fe2MeatArgs& a, hipStream_t st);
+
 // theta terms of the negative binomial (theta.hip): [grid][NS] partials for launch_reduce_stats; loglik: T_LL too
 hipError_t launch_theta_terms(const ThetaArgs& a, int grid, bool loglik, hipStream_t st, hipEvent_t e0 = nullptr,
                               hipEvent_t e1 = nullptr);

@@ -15,6 +15,7 @@ void sglm_engine::free_clusters(bool inner_too) {
   dclidx = nullptr;
   dev_free({&dR, &dP});
   free_fe();
+  free_fe2();
   cl_levels.clear();
   cl_G = 0;
   cl_nseg = cl_ntiles = 0;

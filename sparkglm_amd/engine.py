@@ -51,6 +51,21 @@ class FitFE:
 
 
 @dataclass
+class FitFE2:
+    """sglm_fit_glm_fe2: the fit of beta, the effects alpha [G] and gamma [H] (NaN: a level without weight;
+    gamma is 0 at the lowest factor-2 code of every component), the sweeps (last iteration, total), the levels
+    with weight, the components of the level graph and df_residual = n - p - (G_eff + H_eff - ncomp)."""
+    fit: FitGLM
+    alpha: np.ndarray
+    gamma: np.ndarray
+    sweeps: tuple
+    df_residual: float
+    ncomp: int
+    G_eff: int
+    H_eff: int
+
+
+@dataclass
 class ThetaML:
     """sglm_theta_ml (MASS::theta.ml)."""
     theta: float
@@ -485,6 +500,7 @@ class Engine:
         integer or string dtype -- are factorised (np.unique); with `G` given, `ids` are dense codes in
         [0, G): the form the ranks of a communicator need, so that codes are global.  `ids=None`
         clears.  A call that replaces the data (set_data, reserve, synth, ...) drops the clusters."""
+        self._nfe2 = 0  # replacing or clearing the clusters drops the second factor (set_fe2)
         if ids is None:
             L.check(self._lib.sglm_set_clusters(self._h, None, 0, 0), "sglm_set_clusters")
             self._nclusters = 0
@@ -598,6 +614,118 @@ class Engine:
         t = [C.c_double() for _ in range(4)]
         L.check(self._lib.sglm_get_fe_ms(self._h, *[C.byref(v) for v in t]), "sglm_get_fe_ms")
         return tuple(v.value for v in t)
+
+    # ---- two-way fixed effects: a second factor beside the one of set_clusters ----
+    def set_fe2(self, ids, H=None):
+        """The second fixed-effects factor of every resident row (sglm_set_fe2), after set_clusters.  With
+        `H=None` the labels are factorised (np.unique); with `H` given, `ids` are dense codes in [0, H).
+        `ids=None` clears.  Replacing the data or the clusters drops it."""
+        if ids is None:
+            L.check(self._lib.sglm_set_fe2(self._h, None, 0, 0), "sglm_set_fe2")
+            self._nfe2 = 0
+            return self
+        ids = np.asarray(ids).reshape(-1)
+        if H is None:
+            labels, ids = np.unique(ids, return_inverse=True)
+            H = len(labels)
+        elif ids.dtype.kind not in "iu":
+            raise L.IllegalArgumentException("requirement failed: with H given, ids are integer codes in [0, H)")
+        elif ids.size and (ids.min() < 0 or ids.max() >= H):  # before the cast to int32 can wrap a code
+            raise L.IllegalArgumentException(f"requirement failed: every code of the second factor in [0, H = {H})")
+        codes = np.ascontiguousarray(ids, dtype=np.int32)
+        self._nfe2 = 0
+        L.check(self._lib.sglm_set_fe2(self._h, codes.ctypes.data_as(C.POINTER(C.c_int32)), codes.shape[0], int(H)),
+                "sglm_set_fe2")
+        self._nfe2 = int(H)
+        return self
+
+    def _H(self) -> int:
+        return int(getattr(self, "_nfe2", 0))
+
+    def _gamma(self, gamma):
+        a = np.ascontiguousarray(gamma, dtype=np.float64).reshape(-1)
+        if a.shape[0] != self._H():
+            raise L.IllegalArgumentException(f"requirement failed: gamma has {a.shape[0]} entries for "
+                                             f"{self._H()} levels (set_fe2)")
+        return a
+
+    @staticmethod
+    def _fe2_opts(sweep_tol, max_sweeps):
+        return L.Fe2Opts(float(sweep_tol), int(max_sweeps))
+
+    def fit_glm_fe2(self, family="poisson", link="log", tol=1e-6, verbose=False, max_iter=0, init="single",
+                    npart=0, max_trace=512, sweep_tol=0.0, max_sweeps=0) -> FitFE2:
+        """The GLM with one fixed effect per cluster of set_clusters and one per level of set_fe2, both
+        absorbed (sglm_fit_glm_fe2; fixest::feglm with two factors): every iterate is that of fit_glm on
+        [X | D1 | D2 without one column per component].  X holds no intercept."""
+        o = glm_opts(family, link, tol, verbose, max_iter, init, npart)
+        fo = self._fe2_opts(sweep_tol, max_sweeps)
+        coefs, se = np.zeros(self.p), np.zeros(self.p)
+        trace = np.full(max_trace, np.nan)
+        pre = L.PreGLM(L.ptr(coefs), L.ptr(se), 0, 0, 0, 0, 0, 0, 0, L.ptr(trace), max_trace)
+        alpha, gamma = np.zeros(max(self._G(), 1)), np.zeros(max(self._H(), 1))
+        info = L.Fe2Info()
+        L.check(self._lib.sglm_fit_glm_fe2(self._h, C.byref(o), C.byref(fo), C.byref(pre), L.ptr(alpha), L.ptr(gamma),
+                                           C.byref(info)), "sglm_fit_glm_fe2")
+        f = FitGLM(coefs, se, pre.deviance, pre.null_deviance, pre.pearson, pre.loglik, pre.iter, pre.nrow,
+                   pre.npart, trace[: pre.iter + 1].copy())
+        return FitFE2(f, alpha[: self._G()], gamma[: self._H()], (info.sweeps_last, info.sweeps_total),
+                      info.df_residual, info.ncomp, info.G_eff, info.H_eff)
+
+    def fe2_pass(self, beta=None, alpha=None, gamma=None, family="poisson", link="log", init="single",
+                 sweep_tol=0.0, max_sweeps=0, sums=True):
+        """One two-way step at (beta, alpha, gamma), the sweeps started from zero (sglm_fe2_pass): dict(A, b,
+        S1 [G x p], t1, W1, S2 [H x p], t2, W2, Y [(G + H) x (p + 1)], scalars, sweeps).  beta=None: the
+        initial mode at mean(y).  sums=False: dict(A, b, scalars, sweeps) only -- the level sums and Y are not
+        copied to the host."""
+        o = glm_opts(family, link, init=init)
+        fo = self._fe2_opts(sweep_tol, max_sweeps)
+        p, G, H = self.p, self._G(), self._H()
+        A, b, s = np.zeros((p, p), order="F"), np.zeros(p), np.zeros(L.NS)
+        g1 = np.zeros(max(G, 1) * (p + 2)) if sums else None
+        g2 = np.zeros(max(H, 1) * (p + 2)) if sums else None
+        Y = np.zeros((max(G + H, 1), p + 1), order="F") if sums else None
+        k = C.c_int()
+        bb = None if beta is None else self._beta(beta)
+        aa = None if alpha is None else self._alpha(alpha)
+        gg = None if gamma is None else self._gamma(gamma)
+        L.check(self._lib.sglm_fe2_pass(self._h, C.byref(o), C.byref(fo), L.ptr(bb), L.ptr(aa), L.ptr(gg),
+                                        A.ctypes.data_as(L.dp), L.ptr(b), L.ptr(g1), L.ptr(g2),
+                                        None if Y is None else Y.ctypes.data_as(L.dp), L.ptr(s), C.byref(k)),
+                "sglm_fe2_pass")
+        if not sums:
+            return dict(A=A, b=b, scalars=s, sweeps=k.value)
+        out = dict(A=A, b=b, Y=Y, scalars=s, sweeps=k.value)
+        for tag, g, n in (("1", g1, G), ("2", g2, H)):
+            out["S" + tag] = g[: n * p].reshape((n, p), order="F")
+            out["t" + tag] = g[n * p: n * (p + 1)].copy()
+            out["W" + tag] = g[n * (p + 1): n * (p + 2)].copy()
+        return out
+
+    def vcov_fe2(self, beta, alpha, gamma, family="poisson", link="log", cluster=True, type="HC1", cadjust=True,
+                 return_meat=False, sweep_tol=0.0, max_sweeps=0):
+        """The covariance of beta at (beta, alpha, gamma) of a two-way fit (sglm_vcov_fe2): inv(A) with
+        cluster=False, else clustered on factor 1 -- the beta block of sandwich::vcovCL on the dummy fit."""
+        if cluster and type not in L.CLUSTER_TYPES:
+            raise L.IllegalArgumentException(f"requirement failed: with clusters, type must be one of "
+                                             f"{list(L.CLUSTER_TYPES)}, got {type!r}")
+        o = glm_opts(family, link)
+        fo = self._fe2_opts(sweep_tol, max_sweeps)
+        b, a, g = self._beta(beta), self._alpha(alpha), self._gamma(gamma)
+        cov = np.zeros((self.p, self.p), order="F")
+        meat = np.zeros((self.p, self.p), order="F") if return_meat else None
+        L.check(self._lib.sglm_vcov_fe2(self._h, C.byref(o), C.byref(fo), L.ptr(b), L.ptr(a), L.ptr(g),
+                                        int(bool(cluster)), L.HC_TYPES.get(type, 0), int(bool(cadjust)),
+                                        cov.ctypes.data_as(L.dp),
+                                        None if meat is None else meat.ctypes.data_as(L.dp)), "sglm_vcov_fe2")
+        return (cov, meat) if return_meat else cov
+
+    def fe2_ms(self):
+        """Kernel times (weights, factor-1 sums, factor-2 sums, sweeps, cross product) of the last two-way
+        step (HIP events)."""
+        t = np.zeros(5)
+        L.check(self._lib.sglm_get_fe2_ms(self._h, L.ptr(t)), "sglm_get_fe2_ms")
+        return tuple(t)
 
     def influence_ms(self) -> float:
         """Kernel time of the last influence() call (HIP events)."""

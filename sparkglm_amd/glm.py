@@ -101,10 +101,15 @@ class GLMModel:
     fixef: Optional[dict] = None
     fe_dropped_groups: int = 0
     fe_dropped_rows: int = 0
+    # GLM.fit_fe(fe2=) only: the second factor's effects (label -> gamma; 0 at the lowest label of every connected
+    # component of the two factors' levels, NaN: a level without weight), the components and the sweeps
+    fixef2: Optional[dict] = None
+    fe_ncomp: int = 0
+    fe_sweeps: Optional[tuple] = None
 
     def predict(self, newData: Frame, type: str = "response", offset: Optional[Frame] = None,
                 m: Optional[Frame] = None, device: int = 0, cov=None, dispersion: Optional[float] = None,
-                fe: Optional[Frame] = None) -> Frame:
+                fe: Optional[Frame] = None, fe2: Optional[Frame] = None) -> Frame:
         """Extension (the reference has no GLM predict): (index, value) rows of the
         linear predictor newX * coefs (+ offset) on the "link" scale, or of mu = unlink(eta, m)
         on the "response" scale (m = binomial trials, default 1) -- R's predict.glm(type=).
@@ -117,7 +122,8 @@ class GLMModel:
         (_dispersion).  Without `cov` the result is unchanged.
 
         A GLM.fit_fe model takes `fe`, one column with each new row's label of the absorbed factor: the
-        label's alpha is added to the offset, and a label the fit has not seen predicts NaN."""
+        label's alpha is added to the offset, and a label the fit has not seen predicts NaN.  A two-way model
+        (GLM.fit_fe(fe2=)) takes `fe2` in the same way."""
         _require(len(set(self.xnames) - set(newData.columns)) == 0,
                  "Not all predictors in the estimation data are in the data to be predicted")
         fam, lnk = _model_family_link(self)
@@ -130,8 +136,14 @@ class GLMModel:
                      "of labels")
             _require(fe.count() == newData.count(), "The two DataFrames must have the same number of rows")
             off = fe_offsets(self.fixef, fe[fe.columns[0]], off)
+            if self.fixef2 is not None:
+                _require(fe2 is not None and len(fe2.columns) == 1 and fe2.count() == newData.count(),
+                         "a two-way fixed-effects model predicts with fe2 as well, one column of labels")
+                off = fe_offsets(self.fixef2, fe2[fe2.columns[0]], off)
+            else:
+                _require(fe2 is None, "fe2 belongs to a GLM.fit_fe(fe2=) model")
         else:
-            _require(fe is None, "fe belongs to a GLM.fit_fe model")
+            _require(fe is None and fe2 is None, "fe belongs to a GLM.fit_fe model")
         vals = _engine(device).predict_new(newX, beta, fam, lnk, type, off, mv)
         cols = {"index": np.arange(len(vals), dtype=np.int64), "value": vals}
         if cov is not None:
@@ -308,6 +320,25 @@ def fe_uninformative(codes, G, y, family, m=None, prior=None):
     return (a == 0) != (b == 0)
 
 
+def fe2_drop(codes1, codes2, y, family, m=None, prior=None):
+    """(keep [n] bool, rounds): the rows left after the levels without a finite effect are dropped from either
+    factor again and again until none is left -- dropping a unit's rows can leave a period with only zeros."""
+    n = len(y)
+    keep = np.ones(n, dtype=bool)
+    rounds = 0
+    c1, c2 = np.asarray(codes1).reshape(-1), np.asarray(codes2).reshape(-1)
+    G, H = (int(c1.max()) + 1, int(c2.max()) + 1) if n else (0, 0)
+    pr = np.ones(n) if prior is None else np.asarray(prior, dtype=np.float64)
+    while True:
+        w = np.where(keep, pr, 0.0)  # a dropped row counts as a row without weight
+        bad = fe_uninformative(c1, G, y, family, m, w)[c1] | fe_uninformative(c2, H, y, family, m, w)[c2]
+        bad &= keep
+        if not bad.any():
+            return keep, rounds
+        keep &= ~bad
+        rounds += 1
+
+
 def fe_offsets(fixef, labels, offset=None):
     """offset + alpha[label] per row; NaN where the label is not among the fitted effects."""
     labels = np.asarray(labels).reshape(-1)
@@ -450,9 +481,63 @@ class GLM:
         return fam, lnk, X, names, yv, mv, ov, pv, labels, codes, ngroups, nrows
 
     @staticmethod
+    def _fe2_data(y, x, fe, fe2, family, link, offset, m, prior, drop_uninformative, quiet=False):
+        """The arrays of a two-way fit: _fe_data's with the second factor coded too and the uninformative levels
+        of either factor dropped until none is left.  Returns _fe_data's tuple with (labels2, codes2) inserted
+        after codes, and the dropped levels counted over both factors."""
+        _require(len(fe2.columns) == 1, "The 'fe2' DataFrame must have only one column")
+        _require(fe2.count() == y.count(), "The two DataFrames must have the same number of rows")
+        fam, lnk, X, names, yv, mv, ov, pv, labels, codes, _, _ = GLM._fe_data(
+            y, x, fe, family, link, offset, m, prior, False, quiet=True)
+        labels2, codes2 = fe_codes(fe2[fe2.columns[0]])
+        nlev = nrows = 0
+        if drop_uninformative:
+            keep, _ = fe2_drop(codes, codes2, yv, fam, mv, pv)
+            if not keep.all():
+                nrows = int((~keep).sum())
+                nlev = (len(labels) - len(np.unique(codes[keep]))) + (len(labels2) - len(np.unique(codes2[keep])))
+                if not quiet:
+                    print(f"NOTE: {nlev} fixed effect(s) ({nrows} rows) removed because of only 0"
+                          f"{' (or only m)' if fam == 'binomial' else ''} outcomes.")
+                X, yv = np.asfortranarray(X[keep]), yv[keep]
+                mv, ov, pv = (None if v is None else v[keep] for v in (mv, ov, pv))
+                labels, codes = fe_codes(labels[codes[keep]])
+                labels2, codes2 = fe_codes(labels2[codes2[keep]])
+        return fam, lnk, X, names, yv, mv, ov, pv, labels, codes, labels2, codes2, nlev, nrows
+
+    @staticmethod
+    def _fit_fe2(y, x, fe, fe2, family, link, offset, m, prior, drop_uninformative, tol, verbose, theta, device,
+                 sweep_tol, max_sweeps):
+        fam, lnk, X, names, yv, mv, ov, pv, labels, codes, labels2, codes2, nlev, nrows = GLM._fe2_data(
+            y, x, fe, fe2, family, link, offset, m, prior, drop_uninformative)
+        eng = _engine(device)
+        if fam == "negbin":
+            _require(theta is not None, "family negbin needs theta (GLM.fit_nb estimates it without fixed effects)")
+            eng.set_theta(theta)
+        eng.set_data(X, yv, mv, ov, pv)
+        eng.set_clusters(codes, len(labels))
+        eng.set_fe2(codes2, len(labels2))
+        npart = x.rdd.partitions.size()
+        r = eng.fit_glm_fe2(fam, lnk, tol=tol, verbose=verbose, init="single" if npart == 1 else "multiple",
+                            npart=npart, sweep_tol=sweep_tol, max_sweeps=max_sweeps)
+        obj = GLM.createObj(x.select(*names), y, _to_pre(r.fit), "negbin" if fam == "negbin" else family, link)
+        neff = r.G_eff + r.H_eff - r.ncomp
+        obj.dfResidual, obj.dfNull = float(r.df_residual), float(r.fit.nrow - 1.0)
+        obj.pDispersion = obj.pearson / obj.dfResidual
+        obj.aic = -2.0 * obj.loglik + 2.0 * (len(names) + neff)
+        obj.theta = None if fam != "negbin" else float(theta)
+        item = lambda l: l.item() if hasattr(l, "item") else l
+        obj.fixef = {item(l): float(a) for l, a in zip(labels, r.alpha)}
+        obj.fixef2 = {item(l): float(a) for l, a in zip(labels2, r.gamma)}
+        obj.fe_dropped_groups, obj.fe_dropped_rows = nlev, nrows
+        obj.fe_ncomp, obj.fe_sweeps = r.ncomp, r.sweeps
+        return obj
+
+    @staticmethod
     def fit_fe(y: Frame, x: Frame, fe: Frame, family: str = "poisson", link: str = "log", offset: Frame = None,
                m: Frame = None, prior: Frame = None, drop_uninformative: bool = True, tol: float = 1e-6,
-               verbose: bool = False, theta: Optional[float] = None, device: int = 0) -> GLMModel:
+               verbose: bool = False, theta: Optional[float] = None, device: int = 0, fe2: Frame = None,
+               sweep_tol: float = 0.0, max_sweeps: int = 0) -> GLMModel:
         """Extension: the GLM with one fixed effect per level of `fe` (one column of labels of any dtype),
         absorbed rather than expanded into dummy columns (fixest::feglm / fepois, Stata's xtpoisson, fe):
         coefficients, standard errors, deviances and iterations are those of GLM.fit on [x | dummies of fe].
@@ -462,7 +547,16 @@ class GLM:
         engine refuses the fit).  The model carries `fixef` (label -> alpha), dfResidual = n - p - G_eff and
         the counts of dropped groups and rows; family "negbin" fits at the given `theta`.  For binomial
         models with few rows per level the estimates carry the incidental-parameters bias of every
-        dummy-variable fit (the engine applies no correction)."""
+        dummy-variable fit (the engine applies no correction).
+
+        With `fe2` (one more column of labels of any dtype) the fit absorbs two factors (fixest's feglm with
+        `| fe + fe2`; sglm_fit_glm_fe2): uninformative levels of either factor are dropped repeatedly until
+        none is left, the model carries `fixef` and `fixef2` (gamma is 0 at the lowest label of every connected
+        component of the levels), dfResidual = n - p - (G_eff + H_eff - components), and `sweep_tol` /
+        `max_sweeps` bound the alternating sweeps (0: 1e-12 and 10000).  One device, no communicator."""
+        if fe2 is not None:
+            return GLM._fit_fe2(y, x, fe, fe2, family, link, offset, m, prior, drop_uninformative, tol, verbose,
+                                theta, device, sweep_tol, max_sweeps)
         fam, lnk, X, names, yv, mv, ov, pv, labels, codes, ngroups, nrows = GLM._fe_data(
             y, x, fe, family, link, offset, m, prior, drop_uninformative)
         eng = _engine(device)
@@ -523,8 +617,26 @@ class GLM:
         return eng.vcov(beta, fam, lnk) if type == "const" else eng.vcov_robust(beta, fam, lnk, type=type)
 
     @staticmethod
+    def _load_fe2(obj: GLMModel, y, x, fe, fe2, offset, m, prior, device):
+        """The two-way model's estimation data on the engine with both factors, and (beta, alpha, gamma)."""
+        _require(obj.fixef is not None and obj.fixef2 is not None, "fe2 belongs to a GLM.fit_fe(fe2=) model")
+        fam, lnk, X, names, yv, mv, ov, pv, labels, codes, labels2, codes2, _, _ = GLM._fe2_data(
+            y, x.select(*obj.xnames), fe, fe2, obj.family, obj.link, offset, m, prior, True, quiet=True)
+        eng = _engine(device)
+        if fam == "negbin":
+            eng.set_theta(obj.theta)
+        eng.set_data(X, yv, mv, ov, pv)
+        eng.set_clusters(codes, len(labels))
+        eng.set_fe2(codes2, len(labels2))
+        _require(all(l in obj.fixef for l in labels.tolist()) and all(l in obj.fixef2 for l in labels2.tolist()),
+                 "fe / fe2 hold a label the model was not fitted with")
+        return (eng, fam, lnk, np.asarray(obj.coefs, dtype=np.float64).reshape(-1), fe_offsets(obj.fixef, labels),
+                fe_offsets(obj.fixef2, labels2))
+
+    @staticmethod
     def vcov_fe(obj: GLMModel, y: Frame, x: Frame, fe: Frame, offset: Frame = None, m: Frame = None,
-                prior: Frame = None, device: int = 0, type: str = "const", cadjust: bool = True) -> np.ndarray:
+                prior: Frame = None, device: int = 0, type: str = "const", cadjust: bool = True,
+                fe2: Frame = None) -> np.ndarray:
         """Extension: the covariance of a GLM.fit_fe model's coefficients on its estimation data, `fe` its
         factor.  `type` "const": inv(A), the beta block of the dummy fit's unscaled covariance (multiply by
         the dispersion); "HC0" / "HC1": clustered on `fe` (sglm_vcov_fe), the beta block of
@@ -532,6 +644,11 @@ class GLM:
         signature; a fixed-effects model is refused there.)"""
         if type != "const":
             _check_cluster_type(type)
+        if fe2 is not None or getattr(obj, "fixef2", None) is not None:  # two-way: clustered on fe (factor 1)
+            _require(fe2 is not None, "a two-way fixed-effects model needs fe2 as well")
+            eng, fam, lnk, beta, alpha, gamma = GLM._load_fe2(obj, y, x, fe, fe2, offset, m, prior, device)
+            return eng.vcov_fe2(beta, alpha, gamma, fam, lnk, cluster=type != "const",
+                                type=type if type != "const" else "HC0", cadjust=cadjust)
         eng, fam, lnk, beta, alpha = GLM._load_fe(obj, y, x, fe, offset, m, prior, device)
         return eng.vcov_fe(beta, alpha, fam, lnk, cluster=type != "const", type=type if type != "const" else "HC0",
                            cadjust=cadjust)
@@ -550,7 +667,7 @@ class GLM:
     @staticmethod
     def coeftest(obj: GLMModel, y: Frame, x: Frame, offset: Frame = None, m: Frame = None, prior: Frame = None,
                  device: int = 0, type: str = "HC3", cluster: Frame = None, cadjust: bool = True,
-                 fe: Frame = None) -> Frame:
+                 fe: Frame = None, fe2: Frame = None) -> Frame:
         """Extension: lmtest::coeftest(fit, vcov. = vcovHC(fit, type)) -- name, estimate, robust
         standard error sqrt(diag V), z statistic and its two-sided normal p-value.  With `cluster` (one
         column of labels) the covariance is vcovCL(fit, cluster, type, cadjust) and `type` must be "HC0"
@@ -560,7 +677,7 @@ class GLM:
             _require(cluster is None, "a fixed-effects model is clustered on its own factor fe")
             t = type if type in ("const", "HC0", "HC1") else "HC1"
             _require(fe is not None and getattr(obj, "fixef", None) is not None, "fe belongs to a GLM.fit_fe model, which needs it")
-            V = GLM.vcov_fe(obj, y, x, fe, offset, m, prior, device, t, cadjust)
+            V = GLM.vcov_fe(obj, y, x, fe, offset, m, prior, device, t, cadjust, fe2=fe2)
             beta = np.asarray(obj.coefs, dtype=np.float64).reshape(-1)
             return _coef_table(obj.xnames, beta, V, L.load().sglm_pval_normal)
         if cluster is not None:
