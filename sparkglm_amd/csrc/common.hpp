@@ -286,6 +286,10 @@ struct FeArgs {
   int64_t ntiles;
   double* w;                 // [ld]; null: not stored (FE_CHECK)
   double* Q;                 // [nseg][2]
+  // the two values Q sums, per row [ld] (zeros past n and on rows of prior weight 0); null: not stored.
+  // va: w z | u | y; vb: w | 0 | m - y or 1.  The two-way fits sum them over factor 2's row lists.
+  double* va;
+  double* vb;
 };
 // fe_offset_kernel: out_i = off_i + alpha[cluster of row i] per segment, zeros on the rows in [n, ld)
 struct FeOffsetArgs {
@@ -318,21 +322,7 @@ struct FeGroupArgs {
 // Factor 2's rows are listed per level in ascending order (a stable counting sort by code) and each level's
 // list is cut into chunks of FE2_CHUNK positions; the chunks, already ordered by level, feed combine_kernel.
 constexpr int FE2_CHUNK = 128;
-// fe2_rows_kernel: one value (two for FE_CHECK) per row, the arithmetic of fe_weights_kernel's rows
-//   FE_WZ     out0 = w z
-//   FE_CHECK  out0 = y, out1 = m - y (binomial; else 1) on the rows of positive prior weight, else 0
-struct Fe2RowsArgs {
-  const double* y;
-  const double* eta;
-  const double* m;           // may be null
-  const double* off;         // the effective offset o* (FE_WZ)
-  const double* prior;       // may be null
-  int64_t n, ld;             // rows; the outputs are written up to ld (zeros past n)
-  int family, link, mode, kind;
-  double mu0, theta;
-  double* out0;
-  double* out1;              // FE_CHECK only
-};
+// The per-row values it sums (w z and w; y and m - y for the check) are fe_weights_kernel's (FeArgs::va, vb).
 // fe2_list_sum_kernel: R[k, j] = sum_{q in chunk k} v[row] X[row, j] (j < p), r0[row] (j = p), r1[row]
 // (j = p + 1), row = list[q], positions in ascending order.  p = 0: only the two row vectors are summed.
 struct Fe2ListSumArgs {

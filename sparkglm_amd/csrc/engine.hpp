@@ -255,8 +255,12 @@ struct sglm_engine : public sglm::Backend {
   int32_t cl_G = 0;                               // clusters declared for the resident rows (0: none set)
   int64_t cl_nseg = 0, cl_ntiles = 0;
   // one allocation: seg_start [nseg + 2] | tile_seg [ntiles + 1] | cl_seg [nseg] | per combine level
-  // chunk_start [nchunk + 1], chunk_dst [nchunk]
+  // chunk_start [nchunk + 1], chunk_dst [nchunk] | seg_cluster [nseg]
   int64_t* dclidx = nullptr;
+  const int64_t* seg_start() const { return dclidx; }
+  const int64_t* tile_seg() const { return dclidx + cl_nseg + 2; }
+  const int64_t* cl_seg() const { return tile_seg() + cl_ntiles + 1; }          // the segments ordered by cluster
+  const int64_t* seg_cluster() const { return dclidx + cl_segcl_off; }          // as int64
   double* dR = nullptr;                           // segment sums [nseg][p]
   // the combine's levels (common.hpp CombineArgs): offsets into dclidx; rows of dP the level reads
   // (level 0 reads R through cl_seg) and writes
@@ -275,7 +279,7 @@ struct sglm_engine : public sglm::Backend {
 
   // ---- fixed effects over the cluster factor (fe.hip; fe.cpp): sglm_fit_glm_fe / sglm_fe_pass / sglm_vcov_fe ----
   int64_t cl_prow = 0;                            // rows of dP (the combine's scratch)
-  int64_t cl_segcl_off = 0;                       // offset in dclidx of seg_cluster [nseg] (as int64)
+  int64_t cl_segcl_off = 0;                       // offset in dclidx of seg_cluster [nseg]
   const double* off_override = nullptr;           // while set, the pass reads its offset here (o* = o + alpha_g)
   double *dfo = nullptr, *dalpha = nullptr;       // o* [n_pad]; alpha [G]
   double *dfq = nullptr, *dfqp = nullptr;         // per-segment scalar sums [nseg][2]; their combine scratch [cl_prow][2]
@@ -410,6 +414,9 @@ struct sglm_engine : public sglm::Backend {
   int uscore_local(const double* beta, int family, int link);
   int ensure_cl_inner();  // the internal engine whose design is [G x p]
   int cluster_sums_local();
+  // the combine tree over the cluster factor's segments: the unit sums R [nseg][ncol] into S (scratch P)
+  int combine_clusters(const double* R, double* P, int ncol, double* S, int64_t ldS, hipEvent_t e0 = nullptr,
+                       hipEvent_t e1 = nullptr);
   int cluster_sync();
   int64_t cluster_len() const { return cl_inner->n_pad * p; }  // doubles of S, padding included
 
@@ -417,9 +424,11 @@ struct sglm_engine : public sglm::Backend {
   void free_fe();
   int fe_prepare();
   int64_t fe_len() const { return cl_inner->n_pad * (p + 2); }  // doubles of S | t | W, padding included
-  int fe_set_alpha(const double* alpha);  // null: zeros
+  // effects [L] to dst on this device; a NaN (a level without weight) is read as 0; null: zeros
+  int set_effects(double* dst, const double* src, int64_t L);
   int fe_offset_local();
-  int fe_sums_local(int kind, int mode, int family, int link, double mu0);
+  // va, vb: where the kernel stores the two per-row values it sums (common.hpp FeArgs), or null
+  int fe_sums_local(int kind, int mode, int family, int link, double mu0, double* va = nullptr, double* vb = nullptr);
   int fe_sync();
 
   // ---- fe2.cpp ----
@@ -443,15 +452,70 @@ int cluster_count(sglm_engine* h, int32_t* G);
 // The cluster sums S (fe: the group sums S | t | W, sglm_engine::dfg) summed in place over the handle's
 // shards or ranks; every rank (a group: shard 0) ends with bitwise the same sums.
 int sum_cluster_scores(sglm_engine* h, bool fe = false);
+// The combine tree's plan.  An open range is a destination row of S and the positions [lo, hi) it owns in the
+// level's input (ascending, contiguous).  A range is cut into chunks of CLUSTER_CHUNK positions.  One chunk: it is
+// summed into S and the range is done.  Several: each is summed into a row of the scratch, and those rows are
+// the range at the next level.  Appends per level chunk_start [nchunk + 1], chunk_dst [nchunk] to idx and fills
+// levels; returns the rows of the scratch.
+struct CombineRange {
+  int64_t dst, lo, hi;
+};
+int64_t plan_combine(std::vector<CombineRange> cur, std::vector<int64_t>& idx,
+                     std::vector<sglm_engine::CombineLevel>& levels);
+// The tree's launches on s's stream: unit sums R [.][ncol] (level 0 reads them through idx0, null: as they lie),
+// scratch P, into S; `base` is the device copy of the planner's idx.  e0 / e1: recorded at the start of the
+// first level and the end of the last (no level: no launch, neither is recorded).
+int combine_levels(sglm_engine* s, const std::vector<sglm_engine::CombineLevel>& levels, const int64_t* base,
+                   const int64_t* idx0, const double* R, double* P, int ncol, double* S, int64_t ldS,
+                   hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// The refusals of a clustered covariance: hc_type; cadjust once G is known
+int check_cluster_hc(int hc_type);
+int check_cadjust(int cadjust, int32_t G);
+// cov = f C M C with f from HC1's (nrows - 1) / (nrows - p - absorbed) and cadjust's G / (G - 1); the meat
+// copied out.  `at` closes the refusal of a covariance that is not finite ("beta", "(beta, alpha)").
+int clustered_finish(int hc_type, double nrows, int64_t p, int64_t absorbed, int32_t G, int cadjust,
+                     const std::vector<double>& C, const std::vector<double>& M, const char* at, double* cov,
+                     double* meat);
 
 // ---- fe.cpp: what the two-way fixed-effects fits (fe2.cpp) share with the one-way ones ----
 // what every fixed-effects entry point requires, before any launch; the buffers of a step
 int fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G);
-// the group sums of `kind` (common.hpp FeKind) over the cluster factor into shard 0's dfg, synchronised
-int fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0);
+// While it lives every IRLS pass of the handle's shards stores eta; at its end the passes read the shards'
+// own offsets again.
+struct FeScope {
+  sglm_engine* h;
+  explicit FeScope(sglm_engine* handle) : h(handle) {
+    for (sglm_engine* s : h->shards()) s->want_eta = true;
+  }
+  ~FeScope() {
+    for (sglm_engine* s : h->shards()) {
+      s->want_eta = false;
+      s->off_override = nullptr;
+    }
+  }
+};
+// the group sums of `kind` (common.hpp FeKind) over the cluster factor into shard 0's dfg, synchronised;
+// va, vb as sglm_engine::fe_sums_local
+int fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0, double* va = nullptr,
+                  double* vb = nullptr);
 // SGLM_ESINGULAR naming column j, which the fixed effects absorb
 int absorbed_error(int64_t j);
 constexpr double FE_ABSORBED_RATIO = 1e-10;  // A_jj below this part of X'WX_jj: fixest's collin.tol
+// (mode, mu0) of a step entry point: at beta, or at the initial mean when beta is null (collective)
+int fe_step_mode(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, int* mode, double* mu0);
+// a step's packed = lower tri A | b | scalars into the outputs that are wanted
+void fe_unpack_step(const double* packed, int64_t p, double* A, double* b, double* scalars);
+// The bread C = inv(A) of a step's packed A (its time and path into the handle); `singular`: the message
+int fe_bread(sglm_engine* h, double* packed, const char* singular, std::vector<double>& C);
+// the covariance of a call without clustering: the bread itself, a zero meat
+int fe_plain_cov(const std::vector<double>& C, double* cov, double* meat);
+// columns [col0, col0 + ncol) of a col-major level buffer on s's device, the first L rows of each, to the host
+int download_cols(sglm_engine* s, const double* buf, int64_t ld, int64_t L, int64_t col0, int64_t ncol, double* out);
+// levels of positive weight W; the effect (where given) of every other level becomes NaN
+int32_t count_weighted(const std::vector<double>& W, double* effects);
+// ab = a [L] | b [L], the check's two sums per level: levels of which exactly one is 0 (both 0: no row of
+// positive weight) have no finite effect -- their count and the first of them
+std::pair<int64_t, int64_t> uninformative_levels(const std::vector<double>& ab);
 
 // ---- diagnostics.cpp: what the covariance estimators share ----
 // inv(X'WX) at beta (collective over a communicator), the bread of both sandwich estimators

@@ -12,6 +12,10 @@
 // pass is this step: the solve, the stop rule, the trace and the final statistics are sglm_fit_glm's, and
 // the fixed effects move by alpha += (t - s' beta+) / W (fe_alpha_kernel) at the start of the next pass,
 // when beta+ is known.
+//
+// What the two-way fits (fe2.cpp) share is here too: the frame of a step entry point (fe_step_mode,
+// fe_unpack_step), the bread (fe_bread), the downloads and scans of level buffers, FeScope (engine.hpp).
+// The refusals and the finish of a clustered covariance are vcov_cluster.cpp's.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -63,13 +67,12 @@ int sglm_engine::fe_prepare() {
   return SGLM_OK;
 }
 
-// alpha [G] to the device; a NaN (a group without weight) is read as 0; null: zeros
-int sglm_engine::fe_set_alpha(const double* alpha) {
+int sglm_engine::set_effects(double* dst, const double* src, int64_t L) {
   HIPCHK(hipSetDevice(device));
-  std::vector<double> a((size_t)cl_G, 0.0);
-  if (alpha)
-    for (int32_t g = 0; g < cl_G; ++g) a[(size_t)g] = std::isnan(alpha[g]) ? 0.0 : alpha[g];
-  HIPCHK(hipMemcpyAsync(dalpha, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
+  std::vector<double> a((size_t)L, 0.0);
+  if (src)
+    for (int64_t l = 0; l < L; ++l) a[(size_t)l] = std::isnan(src[l]) ? 0.0 : src[l];
+  HIPCHK(hipMemcpyAsync(dst, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));
   return SGLM_OK;
 }
@@ -80,9 +83,9 @@ int sglm_engine::fe_offset_local() {
   FeOffsetArgs a{};
   a.off = doff;
   a.alpha = dalpha;
-  a.seg_start = dclidx;
-  a.tile_seg = dclidx + cl_nseg + 2;
-  a.seg_cluster = dclidx + cl_segcl_off;
+  a.seg_start = seg_start();
+  a.tile_seg = tile_seg();
+  a.seg_cluster = seg_cluster();
   a.ntiles = cl_ntiles;
   a.n = n;
   a.ld = n_pad;
@@ -93,7 +96,7 @@ int sglm_engine::fe_offset_local() {
 }
 
 // The row values of `kind` (common.hpp FeKind) and this shard's group sums into dfg: enqueued on the stream
-int sglm_engine::fe_sums_local(int kind, int mode, int family, int link, double mu0) {
+int sglm_engine::fe_sums_local(int kind, int mode, int family, int link, double mu0, double* va, double* vb) {
   HIPCHK(hipSetDevice(device));
   const int64_t ld = cl_inner->n_pad;
   // as S of the cluster-robust covariance: the combine rewrites the rows of the groups that have a segment
@@ -116,11 +119,13 @@ int sglm_engine::fe_sums_local(int kind, int mode, int family, int link, double 
   a.kind = kind;
   a.mu0 = mu0;
   a.theta = theta;
-  a.seg_start = dclidx;
-  a.tile_seg = dclidx + cl_nseg + 2;
+  a.seg_start = seg_start();
+  a.tile_seg = tile_seg();
   a.ntiles = cl_ntiles;
   a.w = kind == FE_CHECK ? nullptr : domega;
   a.Q = dfq;
+  a.va = va;
+  a.vb = vb;
   HIPCHK(launch_fe_weights(a, fe_grid(ncu, cl_ntiles), st, evf[0], evf[1]));
   const bool rows = kind != FE_CHECK;  // the sums of w x (u x) as well
   if (rows) {
@@ -135,31 +140,10 @@ int sglm_engine::fe_sums_local(int kind, int mode, int family, int link, double 
     c.ntiles = cl_ntiles;
     c.R = dR;
     HIPCHK(launch_cluster_sum(c, cluster_sum_grid(ncu, n, (int)p), st, evcl[0], evcl[1]));
+    if (int rc = combine_clusters(dR, dP, (int)p, dfg, ld, evcl[2], nullptr)) return rc;
   }
-  const int64_t* cl_seg = a.tile_seg + cl_ntiles + 1;
-  for (size_t l = 0; l < cl_levels.size(); ++l) {
-    const CombineLevel& lv = cl_levels[l];
-    CombineArgs c{};
-    c.idx = l == 0 ? cl_seg : nullptr;
-    c.chunk_start = dclidx + lv.start_off;
-    c.chunk_dst = dclidx + lv.dst_off;
-    c.nchunk = lv.nchunk;
-    c.ldS = ld;
-    if (rows) {
-      c.in = l == 0 ? dR : dP + lv.in_row * p;
-      c.p = (int)p;
-      c.S = dfg;
-      c.out = dP ? dP + lv.out_row * p : nullptr;
-      HIPCHK(launch_cluster_combine(c, ncu, st, l == 0 ? evcl[2] : nullptr, nullptr));
-    }
-    // the per-segment scalars through the same tree: two columns, t | W
-    c.in = l == 0 ? dfq : dfqp + lv.in_row * 2;
-    c.p = 2;
-    c.S = dfg + ld * p;
-    c.out = dfqp ? dfqp + lv.out_row * 2 : nullptr;
-    HIPCHK(launch_cluster_combine(c, ncu, st, nullptr, rows && l + 1 == cl_levels.size() ? evcl[3] : nullptr));
-  }
-  return SGLM_OK;
+  // the per-segment scalars through the same tree: two columns, t | W (evcl[2] to evcl[3] spans both trees)
+  return combine_clusters(dfq, dfqp, 2, dfg + ld * p, ld, nullptr, rows ? evcl[3] : nullptr);
 }
 
 int sglm_engine::fe_sync() {
@@ -167,25 +151,6 @@ int sglm_engine::fe_sync() {
   HIPCHK(hipStreamSynchronize(st));
   return SGLM_OK;
 }
-
-namespace {
-
-// While it lives every IRLS pass of the handle's shards stores eta; at its end the passes read the shards'
-// own offsets again.
-struct FeScope {
-  sglm_engine* h;
-  explicit FeScope(sglm_engine* handle) : h(handle) {
-    for (sglm_engine* s : h->shards()) s->want_eta = true;
-  }
-  ~FeScope() {
-    for (sglm_engine* s : h->shards()) {
-      s->want_eta = false;
-      s->off_override = nullptr;
-    }
-  }
-};
-
-}  // namespace
 
 // what every entry point requires, before any launch; collective (cluster_count)
 int sglm::fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G) {
@@ -234,10 +199,10 @@ int fe_times(sglm_engine* h, bool rows) {
 }  // namespace
 
 // The group sums of `kind` over every shard and rank: shard 0 of every rank ends with bitwise the same dfg
-int sglm::fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0) {
+int sglm::fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0, double* va, double* vb) {
   const std::vector<sglm_engine*>& shards = h->shards();
-  for (sglm_engine* s : shards)
-    if (int rc = s->fe_sums_local(kind, mode, family, link, mu0)) return rc;
+  for (sglm_engine* s : shards)  // (va, vb: one shard's rows -- the two-way fits, which ask for them, have one)
+    if (int rc = s->fe_sums_local(kind, mode, family, link, mu0, va, vb)) return rc;
   for (sglm_engine* s : shards)
     if (int rc = s->fe_sync()) return rc;
   if (int rc = fe_times(h, kind != FE_CHECK)) return rc;
@@ -251,6 +216,75 @@ int sglm::absorbed_error(int64_t j) {
   set_error("breeze.linalg.MatrixSingularException: column " + std::to_string(j) + " of X is constant within every "
             "group (an intercept, or a regressor that only varies between groups): the fixed effects absorb it");
   return SGLM_ESINGULAR;
+}
+
+int sglm::fe_step_mode(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, int* mode, double* mu0) {
+  *mode = MODE_IRLS;
+  *mu0 = 0.0;
+  if (beta) return SGLM_OK;
+  double sums[2];
+  if (int rc = h->global_sums(sums)) return rc;
+  *mu0 = sums[0] / sums[1];
+  *mode = opts->init_mode == SGLM_INIT_MULTIPLE ? MODE_INIT_MULTI : MODE_INIT_SINGLE;
+  return SGLM_OK;
+}
+
+void sglm::fe_unpack_step(const double* packed, int64_t p, double* A, double* b, double* scalars) {
+  std::vector<double> g((size_t)(p * p)), x((size_t)p);
+  unpack_gram(packed, p, g.data(), x.data());
+  if (A) std::memcpy(A, g.data(), sizeof(double) * g.size());
+  if (b) std::memcpy(b, x.data(), sizeof(double) * x.size());
+  if (scalars) std::memcpy(scalars, packed + tri_count(p) + p, sizeof(double) * NS);
+}
+
+int sglm::fe_bread(sglm_engine* h, double* packed, const char* singular, std::vector<double>& C) {
+  const int64_t p = h->ncols();
+  std::vector<double> x((size_t)p);
+  std::unique_ptr<SolverIface> solver = h->make_solver(p);
+  const double t0 = now_ms();
+  if (const int srv = solver->solve(packed, x.data())) {
+    if (srv == SGLM_ESINGULAR) set_error(singular);
+    return srv;
+  }
+  C.resize((size_t)(p * p));
+  if (int rc = solver->inverse(C.data())) return rc;
+  h->solve_ms += now_ms() - t0;
+  h->solve_path = solver->path();
+  return SGLM_OK;
+}
+
+int sglm::fe_plain_cov(const std::vector<double>& C, double* cov, double* meat) {
+  std::memcpy(cov, C.data(), sizeof(double) * C.size());
+  if (meat) std::fill(meat, meat + C.size(), 0.0);
+  return SGLM_OK;
+}
+
+int sglm::download_cols(sglm_engine* s, const double* buf, int64_t ld, int64_t L, int64_t col0, int64_t ncol,
+                        double* out) {
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipMemcpy2D(out, sizeof(double) * L, buf + col0 * ld, sizeof(double) * ld, sizeof(double) * L, (size_t)ncol,
+                     hipMemcpyDeviceToHost));
+  return SGLM_OK;
+}
+
+int32_t sglm::count_weighted(const std::vector<double>& W, double* effects) {
+  int32_t count = 0;
+  for (size_t l = 0; l < W.size(); ++l) {
+    if (W[l] > 0.0) count += 1;
+    else if (effects) effects[l] = std::numeric_limits<double>::quiet_NaN();
+  }
+  return count;
+}
+
+std::pair<int64_t, int64_t> sglm::uninformative_levels(const std::vector<double>& ab) {
+  const size_t L = ab.size() / 2;
+  int64_t count = 0, first = -1;
+  for (size_t l = 0; l < L; ++l)
+    if ((ab[l] == 0.0) != (ab[L + l] == 0.0)) {
+      count += 1;
+      if (first < 0) first = (int64_t)l;
+    }
+  return {count, first};
 }
 
 namespace {
@@ -276,7 +310,7 @@ int fe_alpha_step(sglm_engine* h, const double* beta) {
     HIPCHK(hipMemcpyAsync(al.data(), s0->dalpha, sizeof(double) * al.size(), hipMemcpyDeviceToHost, s0->st));
     HIPCHK(hipStreamSynchronize(s0->st));
     for (size_t d = 1; d < shards.size(); ++d)
-      if (int rc = shards[d]->fe_set_alpha(al.data())) return rc;
+      if (int rc = shards[d]->set_effects(shards[d]->dalpha, al.data(), s0->cl_G)) return rc;
   }
   return SGLM_OK;
 }
@@ -328,18 +362,14 @@ int fe_offsets(sglm_engine* h) {
 
 int fe_set_alpha_all(sglm_engine* h, const double* alpha) {
   for (sglm_engine* s : h->shards())
-    if (int rc = s->fe_set_alpha(alpha)) return rc;
+    if (int rc = s->set_effects(s->dalpha, alpha, s->cl_G)) return rc;
   return SGLM_OK;
 }
 
 // columns [col0, col0 + ncol) of shard 0's group sums, the first G rows of each, to the host
-int fe_download(sglm_engine* h, const double* buf, int64_t col0, int64_t ncol, double* out) {
+int fe_download(sglm_engine* h, int64_t col0, int64_t ncol, double* out) {
   sglm_engine* s0 = h->shards()[0];
-  HIPCHK(hipSetDevice(s0->device));
-  const int64_t ld = s0->cl_inner->n_pad, G = s0->cl_G;
-  HIPCHK(hipMemcpy2D(out, sizeof(double) * G, buf + col0 * ld, sizeof(double) * ld, sizeof(double) * G, (size_t)ncol,
-                     hipMemcpyDeviceToHost));
-  return SGLM_OK;
+  return download_cols(s0, s0->dfg, s0->cl_inner->n_pad, s0->cl_G, col0, ncol, out);
 }
 
 // The fit's Backend: glm_drive's pass is the fixed-effects step; no deviance-only passes (every pass's sums
@@ -368,13 +398,8 @@ int fe_uninformative(sglm_engine* h, int family, int link, int32_t G) {
   if (family != FAM_BINOMIAL && family != FAM_POISSON && family != FAM_NEGBIN) return SGLM_OK;
   if (int rc = fe_group_sums(h, FE_CHECK, MODE_IRLS, family, link, 0.0)) return rc;
   std::vector<double> ab((size_t)(2 * G));
-  if (int rc = fe_download(h, h->shards()[0]->dfg, h->ncols(), 2, ab.data())) return rc;
-  int64_t count = 0, first = -1;
-  for (int32_t g = 0; g < G; ++g)
-    if ((ab[(size_t)g] == 0.0) != (ab[(size_t)(G + g)] == 0.0)) {  // both 0: no row of positive weight
-      count += 1;
-      if (first < 0) first = g;
-    }
+  if (int rc = fe_download(h, h->ncols(), 2, ab.data())) return rc;
+  const auto [count, first] = uninformative_levels(ab);
   if (count == 0) return SGLM_OK;
   set_error("requirement failed: " + std::to_string(count) + " group(s) have no finite fixed effect -- every row of "
             "positive prior weight has y = 0" + (family == FAM_BINOMIAL ? " or y = m" : "") + "; the first is group " +
@@ -405,12 +430,8 @@ int sglm_fit_glm_fe(sglm_engine* h, const sglm_glm_opts* opts, sglm_preglm* out,
   sglm_engine* s0 = h->shards()[0];
   HIPCHK(hipSetDevice(s0->device));
   HIPCHK(hipMemcpy(alpha, s0->dalpha, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost));
-  if (int rc = fe_download(h, s0->dfg, h->ncols() + 1, 1, W.data())) return rc;
-  int32_t geff = 0;
-  for (int32_t g = 0; g < G; ++g) {
-    if (W[(size_t)g] > 0.0) geff += 1;
-    else alpha[g] = std::numeric_limits<double>::quiet_NaN();
-  }
+  if (int rc = fe_download(h, h->ncols() + 1, 1, W.data())) return rc;
+  const int32_t geff = count_weighted(W, alpha);
   if (info) {
     info->G_eff = geff;
     info->df_residual = out->nrow - (double)h->ncols() - (double)geff;
@@ -428,24 +449,16 @@ int sglm_fe_pass(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, 
   if (int rc = fe_check(h, opts, &G)) return rc;
   FeScope scope(h);
   const int64_t p = h->ncols();
-  double mu0 = 0.0;
-  int mode = MODE_IRLS;
-  if (!beta) {
-    double sums[2];
-    if (int rc = h->global_sums(sums)) return rc;
-    mu0 = sums[0] / sums[1];
-    mode = opts->init_mode == SGLM_INIT_MULTIPLE ? MODE_INIT_MULTI : MODE_INIT_SINGLE;
-  }
+  double mu0;
+  int mode;
+  if (int rc = fe_step_mode(h, opts, beta, &mode, &mu0)) return rc;
   if (int rc = fe_set_alpha_all(h, alpha)) return rc;
   if (int rc = fe_offsets(h)) return rc;
-  std::vector<double> packed((size_t)packed_len(p)), g((size_t)(p * p)), x((size_t)p);
+  std::vector<double> packed((size_t)packed_len(p));
   if (int rc = fe_step(h, opts->family, opts->link, mode, beta, mu0, false, packed.data())) return rc;
-  unpack_gram(packed.data(), p, g.data(), x.data());
-  if (A) std::memcpy(A, g.data(), sizeof(double) * g.size());
-  if (b) std::memcpy(b, x.data(), sizeof(double) * x.size());
-  if (scalars) std::memcpy(scalars, packed.data() + tri_count(p) + p, sizeof(double) * NS);
+  fe_unpack_step(packed.data(), p, A, b, scalars);
   if (group)
-    if (int rc = fe_download(h, h->shards()[0]->dfg, 0, p + 2, group)) return rc;
+    if (int rc = fe_download(h, 0, p + 2, group)) return rc;
   return SGLM_OK;
 }
 
@@ -455,39 +468,22 @@ int sglm_vcov_fe(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, 
     set_error("requirement failed: beta, alpha, cov");
     return SGLM_EINVAL;
   }
-  if (cluster && hc_type != SGLM_HC0 && hc_type != SGLM_HC1) {
-    set_error("requirement failed: hc_type SGLM_HC0 or SGLM_HC1 under clustering (HC2 / HC3 need per-cluster "
-              "leverage blocks, which the engine does not form)");
-    return SGLM_EINVAL;
-  }
+  if (cluster)
+    if (int rc = check_cluster_hc(hc_type)) return rc;
   int32_t G = 0;
   if (int rc = fe_check(h, opts, &G)) return rc;
-  if (cluster && cadjust && G < 2) {
-    set_error("requirement failed: cadjust (the factor G / (G - 1)) needs G >= 2 clusters");
-    return SGLM_EINVAL;
-  }
+  if (cluster)
+    if (int rc = check_cadjust(cadjust, G)) return rc;
   FeScope scope(h);
   const int64_t p = h->ncols();
-  const std::vector<sglm_engine*>& shards = h->shards();
-  sglm_engine* s0 = shards[0];
+  sglm_engine* s0 = h->shards()[0];
   if (int rc = fe_set_alpha_all(h, alpha)) return rc;
   if (int rc = fe_offsets(h)) return rc;
-  std::vector<double> packed((size_t)packed_len(p)), C((size_t)(p * p)), M((size_t)(p * p)), x((size_t)p);
+  std::vector<double> packed((size_t)packed_len(p)), C, M((size_t)(p * p)), x((size_t)p);
   if (int rc = fe_step(h, opts->family, opts->link, MODE_IRLS, beta, 0.0, true, packed.data())) return rc;
-  std::unique_ptr<SolverIface> solver = h->make_solver(p);
-  const double t0 = now_ms();
-  if (const int srv = solver->solve(packed.data(), x.data())) {
-    if (srv == SGLM_ESINGULAR) set_error("breeze.linalg.MatrixSingularException: the within-group X'WX is singular");
-    return srv;
-  }
-  if (int rc = solver->inverse(C.data())) return rc;
-  h->solve_ms += now_ms() - t0;
-  h->solve_path = solver->path();
-  if (!cluster) {
-    std::memcpy(cov, C.data(), sizeof(double) * C.size());
-    if (meat) std::fill(meat, meat + p * p, 0.0);
-    return SGLM_OK;
-  }
+  const char* singular = "breeze.linalg.MatrixSingularException: the within-group X'WX is singular";
+  if (int rc = fe_bread(h, packed.data(), singular, C)) return rc;
+  if (!cluster) return fe_plain_cov(C, cov, meat);
   // the w-weighted sums s | W stay in dfg2 while the u-weighted ones S | U are formed in dfg
   HIPCHK(hipSetDevice(s0->device));
   if (!s0->dfg2)
@@ -495,24 +491,15 @@ int sglm_vcov_fe(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, 
       return rc;
   HIPCHK(hipMemcpyAsync(s0->dfg2, s0->dfg, sizeof(double) * (size_t)s0->fe_len(), hipMemcpyDeviceToDevice, s0->st));
   std::vector<double> W((size_t)G);
-  if (int rc = fe_download(h, s0->dfg, p + 1, 1, W.data())) return rc;
-  int32_t geff = 0;
-  for (double w : W) geff += w > 0.0 ? 1 : 0;
+  if (int rc = fe_download(h, p + 1, 1, W.data())) return rc;
+  const int32_t geff = count_weighted(W, nullptr);
   if (int rc = fe_group_sums(h, FE_SCORE, MODE_IRLS, opts->family, opts->link, 0.0)) return rc;
   if (int rc = fe_group_gram(h, true, packed.data())) return rc;
   unpack_gram(packed.data(), p, M.data(), x.data());
   double nrows = (double)(h->group() ? h->g_n : h->n);  // every row of every shard, weight 0 included
   if (hc_type == SGLM_HC1 && !h->group())
     if (int rc = h->allreduce_small(&nrows, 1)) return rc;
-  double f = hc_type == SGLM_HC1 ? (nrows - 1.0) / (nrows - (double)p - (double)geff) : 1.0;
-  if (cadjust) f *= (double)G / ((double)G - 1.0);
-  if (!sandwich_product(C, M, p, f, cov)) {
-    set_error("requirement failed: the cluster-robust covariance is not finite (a row whose mean leaves the "
-              "family's range at (beta, alpha))");
-    return SGLM_EINVAL;
-  }
-  if (meat) std::memcpy(meat, M.data(), sizeof(double) * M.size());
-  return SGLM_OK;
+  return clustered_finish(hc_type, nrows, p, geff, G, cadjust, C, M, "(beta, alpha)", cov, meat);
 }
 
 int sglm_get_fe_ms(sglm_engine* h, double* weights_ms, double* sum_ms, double* combine_ms, double* gram_ms) {

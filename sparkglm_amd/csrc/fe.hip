@@ -6,8 +6,9 @@
 //   the row's value (FeKind: working weight, signed score) from rowmath.hpp's reference-order functions --
 //   the arithmetic of the pass's own reference rows, at the eta the pass stored and the effective offset
 //   o* -- stored to w (zeros on the padding rows and on rows of prior weight 0) and, with its companion
-//   (w z), left in LDS.  No segment crosses a tile (cluster_segments), so the tile then sums its own
-//   segments, in two fixed steps: pieces (runs of rows within one segment and one block of 8 rows) by the
+//   (w z), left in LDS; a caller that sums the two values over other row sets (fe2.cpp, over factor 2's
+//   lists) has them stored per row as well (FeArgs::va, vb), so no second pass recomputes them.  No
+//   segment crosses a tile (cluster_segments), so the tile then sums its own segments, in two fixed steps: pieces (runs of rows within one segment and one block of 8 rows) by the
 //   thread of their first row, then each segment's pieces by one thread, both in ascending row order, and
 //   the two sums go to Q.  No atomics; the order is a function of (ids, n) alone.  (A serial sum per
 //   segment measured 3.8 ms at 10^8 rows in full-tile segments against 2.5 ms in segments of 50: one
@@ -33,6 +34,7 @@ constexpr int FE_NT = CLUSTER_TILE_ROWS;
 constexpr int FE_WG_PER_CU = 16;
 constexpr int FE_SUB = 8;  // rows per piece of the tile's segment sums
 static_assert(FE_NT % 64 == 0 && FE_NT % FE_SUB == 0, "whole waves, whole pieces");
+static_assert(FE_NT % RB == 0, "the tiles of n rows cover the ld = n rounded up to RB rows of the per-row outputs");
 
 // w and w z of one row in the reference operation order (pass_row_ref / pass_row_ref_x / pass_row_ref_nb
 // without their unit deviance, which the pass itself sums): from the same primitives, as influence_row.
@@ -87,7 +89,11 @@ __global__ void __launch_bounds__(FE_NT) fe_weights_kernel(FeArgs a) {
         }
       }
     }
-    if (a.w && row < a.ld) a.w[row] = out;
+    if (row < a.ld) {  // (the tiles cover every row below ld: ld is n rounded up to RB rows)
+      if (a.w) a.w[row] = out;
+      if (a.va) a.va[row] = va;
+      if (a.vb) a.vb[row] = vb;
+    }
     sa[r] = va;
     sb[r] = vb;
     head[r] = 0;

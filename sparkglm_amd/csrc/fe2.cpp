@@ -4,11 +4,11 @@
 //
 // One step at (beta, alpha, gamma): o* = offset + alpha_g + gamma_h (fe2_offset_kernel); an ordinary pass that
 // reads o* and stores eta; the one-way step's weights kernel and segment sums give w and S1 | t1 | W1 over
-// factor 1 (fe.cpp); fe2_rows_kernel and fe2_list_sum_kernel give S2 | t2 | W2 over factor 2's row lists,
-// joined by the combine tree; block Gauss-Seidel sweeps on the level coefficients Y = [a ; c]
-// (fe2_gather_kernel + combine + fe2_update_kernel per half sweep) until the largest column-wise relative
-// change is below the tolerance; the cross product S_X' Y on fp64 MFMA (fe2_cross_kernel), symmetrised on the
-// host, and the downdate [A | b] = X'W[X | z] - S_X' Y.  The fit is glm_drive over a Backend whose pass is
+// factor 1 (fe.cpp) and leave w z per row beside w; fe2_list_sum_kernel sums [w x | w z | w] into S2 | t2 | W2
+// over factor 2's row lists, joined by the combine tree (vcov_cluster.cpp's planner and launcher); block
+// Gauss-Seidel sweeps on the level coefficients Y = [a ; c] (fe2_gather_kernel + combine + fe2_update_kernel
+// per half sweep) until the largest column-wise relative change is below the tolerance; the cross product
+// S_X' Y on fp64 MFMA (fe2_cross_kernel), symmetrised on the host, and the downdate [A | b] = X'W[X | z] - S_X' Y.  The fit is glm_drive over a Backend whose pass is
 // this step; the effects move by alpha += a_z - a_X beta+, gamma += c_z - c_X beta+ at the start of the next
 // pass and are normalised per connected component of the level graph.  No second copy of X is made.
 #include <algorithm>
@@ -101,7 +101,10 @@ struct sglm_engine::Fe2State {
   // list [n] | chunk_start [nchunk + 1] | per combine level chunk_start [nchunk_l + 1], chunk_dst [nchunk_l] |
   // order [nchunk]: the chunks by their first row, the order in which the kernels' work units take them
   int64_t* didx = nullptr;
-  int64_t order_off = 0;
+  int64_t n = 0, order_off = 0;
+  const int64_t* list() const { return didx; }
+  const int64_t* chunks() const { return didx + n; }
+  const int64_t* order() const { return didx + order_off; }
   std::vector<sglm_engine::CombineLevel> levels;
   // allocated by prepare (they depend on p and on the cluster factor's buffers)
   int64_t ld1 = 0;
@@ -150,9 +153,9 @@ int upload(T** dst, const std::vector<T>& v, const char* what) {
 // the cluster factor's code of every resident row, from the segments the device keeps
 int cluster_ids(sglm_engine* s, std::vector<int32_t>& ids1) {
   std::vector<int64_t> start((size_t)s->cl_nseg + 1), clus((size_t)std::max<int64_t>(s->cl_nseg, 1));
-  HIPCHK(hipMemcpy(start.data(), s->dclidx, sizeof(int64_t) * start.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(start.data(), s->seg_start(), sizeof(int64_t) * start.size(), hipMemcpyDeviceToHost));
   if (s->cl_nseg > 0)
-    HIPCHK(hipMemcpy(clus.data(), s->dclidx + s->cl_segcl_off, sizeof(int64_t) * (size_t)s->cl_nseg,
+    HIPCHK(hipMemcpy(clus.data(), s->seg_cluster(), sizeof(int64_t) * (size_t)s->cl_nseg,
                      hipMemcpyDeviceToHost));
   ids1.assign((size_t)s->n, 0);
   for (int64_t k = 0; k < s->cl_nseg; ++k)
@@ -173,6 +176,7 @@ int set_fe2_local(sglm_engine* s, const int32_t* ids2, int32_t H) {
   }
   Fe2* F = s->fe2 = new Fe2();
   F->H = H;
+  F->n = s->n;
   F->ncomp = (int32_t)pl.low.size();
   F->nchunk = (int64_t)pl.chunk_level.size();
   F->ld2 = ((int64_t)H + 31) / 32 * 32;
@@ -187,42 +191,13 @@ int set_fe2_local(sglm_engine* s, const int32_t* ids2, int32_t H) {
   // the combine's levels over the chunks, which are ordered by level already (vcov_cluster.cpp's rule)
   std::vector<int64_t> idx(pl.list);
   idx.insert(idx.end(), pl.chunk_start.begin(), pl.chunk_start.end());
-  struct Range {
-    int32_t g;
-    int64_t lo, hi;
-  };
-  std::vector<Range> cur, next;
+  std::vector<CombineRange> open;
   for (int64_t k = 0; k < F->nchunk; ++k) {
-    if (cur.empty() || cur.back().g != pl.chunk_level[(size_t)k]) cur.push_back({pl.chunk_level[(size_t)k], k, k + 1});
-    else cur.back().hi = k + 1;
+    const int32_t level = pl.chunk_level[(size_t)k];
+    if (open.empty() || open.back().dst != level) open.push_back({level, k, k + 1});
+    else open.back().hi = k + 1;
   }
-  int64_t prow = 0, in_row = -1;
-  while (!cur.empty()) {
-    sglm_engine::CombineLevel lv{};
-    lv.start_off = (int64_t)idx.size();
-    lv.in_row = in_row;
-    lv.out_row = prow;
-    std::vector<int64_t> dst;
-    next.clear();
-    int64_t out = 0;
-    for (const Range& r : cur) {
-      const int64_t nch = (r.hi - r.lo + CLUSTER_CHUNK - 1) / CLUSTER_CHUNK;
-      if (nch > 1) next.push_back({r.g, out, out + nch});
-      for (int64_t c = 0; c < nch; ++c) {
-        idx.push_back(r.lo + c * CLUSTER_CHUNK);
-        dst.push_back(nch == 1 ? (int64_t)r.g : -(out++ + 1));
-      }
-    }
-    idx.push_back(cur.back().hi);
-    lv.nchunk = (int64_t)dst.size();
-    lv.dst_off = (int64_t)idx.size();
-    idx.insert(idx.end(), dst.begin(), dst.end());
-    F->levels.push_back(lv);
-    in_row = prow;
-    prow += out;
-    cur.swap(next);
-  }
-  F->prow = prow;
+  F->prow = plan_combine(std::move(open), idx, F->levels);
   F->order_off = (int64_t)idx.size();
   {
     std::vector<int64_t> order((size_t)F->nchunk);
@@ -296,16 +271,6 @@ int fe2_prepare(sglm_engine* s) {
   return SGLM_OK;
 }
 
-// While it lives every IRLS pass of the handle stores eta; at its end the passes read the handle's own offset again
-struct Fe2Scope {
-  sglm_engine* h;
-  explicit Fe2Scope(sglm_engine* handle) : h(handle) { h->want_eta = true; }
-  ~Fe2Scope() {
-    h->want_eta = false;
-    h->off_override = nullptr;
-  }
-};
-
 // what every two-way entry point requires, before any launch
 int fe2_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G) {
   if (!opts || !family_link_valid(opts->family, opts->link)) {
@@ -327,28 +292,6 @@ int fe2_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G) {
   return fe2_prepare(h);
 }
 
-int combine_levels(sglm_engine* s, const std::vector<sglm_engine::CombineLevel>& levels, const int64_t* base,
-                   const int64_t* idx0, const double* R, double* P, int ncol, double* S, int64_t ldS) {
-  for (size_t l = 0; l < levels.size(); ++l) {
-    const sglm_engine::CombineLevel& lv = levels[l];
-    CombineArgs c{};
-    c.in = l == 0 ? R : P + lv.in_row * ncol;
-    c.idx = l == 0 ? idx0 : nullptr;
-    c.chunk_start = base + lv.start_off;
-    c.chunk_dst = base + lv.dst_off;
-    c.nchunk = lv.nchunk;
-    c.p = ncol;
-    c.S = S;
-    c.ldS = ldS;
-    c.out = P ? P + lv.out_row * ncol : nullptr;
-    HIPCHK(launch_cluster_combine(c, s->ncu, s->st));
-  }
-  return SGLM_OK;
-}
-
-const int64_t* list_of(const sglm_engine* s) { return s->fe2->didx; }
-const int64_t* chunks_of(const sglm_engine* s) { return s->fe2->didx + s->n; }
-
 // the sums over factor 2's lists of [v x | r0 | r1] (ncolx = p) or of [r0 | r1] alone (ncolx = 0) into S
 int list_sums(sglm_engine* s, int ncolx, const double* v, const double* r0, const double* r1, double* S) {
   Fe2* F = s->fe2;
@@ -359,11 +302,11 @@ int list_sums(sglm_engine* s, int ncolx, const double* v, const double* r0, cons
   a.v = v;
   a.r0 = r0;
   a.r1 = r1;
-  a.list = list_of(s);
-  a.chunk_start = chunks_of(s);
+  a.list = F->list();
+  a.chunk_start = F->chunks();
   a.nchunk = F->nchunk;
   a.R = F->dR2;
-  a.order = F->didx + F->order_off;
+  a.order = F->order();
   HIPCHK(launch_fe2_list_sum(a, s->ncu, s->st));
   return combine_levels(s, F->levels, F->didx, nullptr, F->dR2, F->dP2, ncolx + 2, S, F->ld2);
 }
@@ -378,12 +321,11 @@ int gather1(sglm_engine* s, const double* v) {
   a.lds = F->ldy;
   a.nc = (int)s->p + 1;
   a.list = nullptr;
-  a.start = s->dclidx;
+  a.start = s->seg_start();
   a.nunit = s->cl_nseg;
   a.R = F->dRg;
   HIPCHK(launch_fe2_gather(a, s->ncu, s->st));
-  const int64_t* cl_seg = s->dclidx + s->cl_nseg + 2 + s->cl_ntiles + 1;
-  return combine_levels(s, s->cl_levels, s->dclidx, cl_seg, F->dRg, F->dPg, (int)s->p + 1, F->dT1, F->ld1);
+  return s->combine_clusters(F->dRg, F->dPg, (int)s->p + 1, F->dT1, F->ld1);
 }
 
 // T2[h, :] = sum_{i in h} v_i Y1[g(i), :] over factor 2's chunks
@@ -395,11 +337,11 @@ int gather2(sglm_engine* s, const double* v) {
   a.src = F->dY1;
   a.lds = F->ldy;
   a.nc = (int)s->p + 1;
-  a.list = list_of(s);
-  a.start = chunks_of(s);
+  a.list = F->list();
+  a.start = F->chunks();
   a.nunit = F->nchunk;
   a.R = F->dRg;
-  a.order = F->didx + F->order_off;
+  a.order = F->order();
   HIPCHK(launch_fe2_gather(a, s->ncu, s->st));
   return combine_levels(s, F->levels, F->didx, nullptr, F->dRg, F->dPg, (int)s->p + 1, F->dT2, F->ld2);
 }
@@ -503,25 +445,10 @@ int fe2_step(sglm_engine* h, const sglm_fe2_opts* o, int family, int link, int m
   const int64_t p = h->p;
   if (int rc = offsets(h)) return rc;
   if (int rc = h->pass(mode, beta, mu0, 0.0, family, link, packed)) return rc;
-  if (int rc = fe_group_sums(h, FE_WZ, mode, family, link, mu0)) return rc;  // w in domega, S1 | t1 | W1 in dfg
+  // w in domega, w z in dwz, S1 | t1 | W1 in dfg
+  if (int rc = fe_group_sums(h, FE_WZ, mode, family, link, mu0, F->dwz)) return rc;
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipEventRecord(F->ev[0], h->st));
-  Fe2RowsArgs r{};
-  r.y = h->dy;
-  r.eta = h->deta;
-  r.m = h->dm;
-  r.off = h->dfo;
-  r.prior = h->dprior;
-  r.n = h->n;
-  r.ld = h->n_pad;
-  r.family = family;
-  r.link = link;
-  r.mode = mode;
-  r.kind = FE_WZ;
-  r.mu0 = mu0;
-  r.theta = h->theta;
-  r.out0 = F->dwz;
-  HIPCHK(launch_fe2_rows(r, h->st));
   if (int rc = list_sums(h, (int)p, h->domega, F->dwz, h->domega, F->dS2)) return rc;
   HIPCHK(hipEventRecord(F->ev[1], h->st));
   HIPCHK(hipEventRecord(F->ev[2], h->st));
@@ -601,17 +528,6 @@ int effects_step(sglm_engine* h, const double* beta) {
   return SGLM_OK;
 }
 
-// effects [L] to the device, a NaN (a level without weight) read as 0; null: zeros
-int set_effects(sglm_engine* h, double* dst, const double* src, int64_t L) {
-  HIPCHK(hipSetDevice(h->device));
-  std::vector<double> a((size_t)L, 0.0);
-  if (src)
-    for (int64_t l = 0; l < L; ++l) a[(size_t)l] = std::isnan(src[l]) ? 0.0 : src[l];
-  HIPCHK(hipMemcpyAsync(dst, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, h->st));
-  HIPCHK(hipStreamSynchronize(h->st));
-  return SGLM_OK;
-}
-
 int zero_Y(sglm_engine* h) {
   Fe2* F = h->fe2;
   HIPCHK(hipSetDevice(h->device));
@@ -620,26 +536,14 @@ int zero_Y(sglm_engine* h) {
   return SGLM_OK;
 }
 
-// columns [col0, col0 + ncol) of a col-major level buffer, the first L rows of each, to the host
-int download_cols(sglm_engine* h, const double* buf, int64_t ld, int64_t L, int64_t col0, int64_t ncol, double* out) {
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemcpy2D(out, sizeof(double) * L, buf + col0 * ld, sizeof(double) * ld, sizeof(double) * L, (size_t)ncol,
-                     hipMemcpyDeviceToHost));
-  return SGLM_OK;
-}
-
-// levels of positive weight at the last step
-int count_levels(sglm_engine* h, int32_t* geff, int32_t* heff, std::vector<double>* W1out = nullptr,
-                 std::vector<double>* W2out = nullptr) {
+// W1, W2 of the last step: levels of positive weight; the effects (where given) of the others become NaN
+int count_levels(sglm_engine* h, int32_t* geff, int32_t* heff, double* alpha = nullptr, double* gamma = nullptr) {
   Fe2* F = h->fe2;
   std::vector<double> W1((size_t)h->cl_G), W2((size_t)F->H);
   if (int rc = download_cols(h, h->dfg, F->ld1, h->cl_G, h->p + 1, 1, W1.data())) return rc;
   if (int rc = download_cols(h, F->dS2, F->ld2, F->H, h->p + 1, 1, W2.data())) return rc;
-  *geff = *heff = 0;
-  for (double w : W1) *geff += w > 0.0 ? 1 : 0;
-  for (double w : W2) *heff += w > 0.0 ? 1 : 0;
-  if (W1out) W1out->swap(W1);
-  if (W2out) W2out->swap(W2);
+  *geff = count_weighted(W1, alpha);
+  *heff = count_weighted(W2, gamma);
   return SGLM_OK;
 }
 
@@ -675,34 +579,16 @@ int uninformative2(sglm_engine* h, int family, int link) {
   for (int f = 0; f < 2; ++f) {
     const int64_t L = f ? F->H : h->cl_G;
     std::vector<double> ab((size_t)(2 * L));
-    if (f == 0) {
-      if (int rc = fe_group_sums(h, FE_CHECK, MODE_IRLS, family, link, 0.0)) return rc;
+    if (f == 0) {  // y and m - y (or 1) of every row into dwz and domega on the way
+      if (int rc = fe_group_sums(h, FE_CHECK, MODE_IRLS, family, link, 0.0, F->dwz, h->domega)) return rc;
       if (int rc = download_cols(h, h->dfg, F->ld1, L, p, 2, ab.data())) return rc;
     } else {
       HIPCHK(hipSetDevice(h->device));
-      Fe2RowsArgs r{};
-      r.y = h->dy;
-      r.m = h->dm;
-      r.prior = h->dprior;
-      r.n = h->n;
-      r.ld = h->n_pad;
-      r.family = family;
-      r.link = link;
-      r.mode = MODE_IRLS;
-      r.kind = FE_CHECK;
-      r.out0 = F->dwz;
-      r.out1 = h->domega;
-      HIPCHK(launch_fe2_rows(r, h->st));
       if (int rc = list_sums(h, 0, nullptr, F->dwz, h->domega, F->dT2)) return rc;  // (p + 1 >= 2 columns)
       HIPCHK(hipStreamSynchronize(h->st));
       if (int rc = download_cols(h, F->dT2, F->ld2, L, 0, 2, ab.data())) return rc;
     }
-    int64_t count = 0, first = -1;
-    for (int64_t l = 0; l < L; ++l)
-      if ((ab[(size_t)l] == 0.0) != (ab[(size_t)(L + l)] == 0.0)) {  // both 0: no row of positive weight
-        count += 1;
-        if (first < 0) first = l;
-      }
+    const auto [count, first] = uninformative_levels(ab);
     if (count == 0) continue;
     set_error("requirement failed: " + std::to_string(count) + " level(s) of factor " + std::to_string(f + 1) +
               " have no finite fixed effect -- every row of positive prior weight has y = 0" +
@@ -772,9 +658,9 @@ int sglm_fit_glm_fe2(sglm_engine* h, const sglm_glm_opts* opts, const sglm_fe2_o
   int32_t G = 0;
   if (int rc = fe2_check(h, opts, &G)) return rc;
   Fe2* F = h->fe2;
-  Fe2Scope scope(h);
-  if (int rc = set_effects(h, h->dalpha, nullptr, G)) return rc;
-  if (int rc = set_effects(h, F->dgamma, nullptr, F->H)) return rc;
+  FeScope scope(h);
+  if (int rc = h->set_effects(h->dalpha, nullptr, G)) return rc;
+  if (int rc = h->set_effects(F->dgamma, nullptr, F->H)) return rc;
   if (int rc = zero_Y(h)) return rc;
   if (int rc = uninformative2(h, opts->family, opts->link)) return rc;
   Fe2Backend be(h, fe2);
@@ -782,16 +668,11 @@ int sglm_fit_glm_fe2(sglm_engine* h, const sglm_glm_opts* opts, const sglm_fe2_o
   h->solve_ms += be.solve_ms;
   h->solve_path = be.solve_path;
   // the effects of the last pass (at out->coefs) and the weights of that pass: a level without weight has none
-  std::vector<double> W1, W2;
-  int32_t geff = 0, heff = 0;
-  if (int rc = count_levels(h, &geff, &heff, &W1, &W2)) return rc;
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipMemcpy(alpha, h->dalpha, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(gamma, F->dgamma, sizeof(double) * (size_t)F->H, hipMemcpyDeviceToHost));
-  for (int32_t g = 0; g < G; ++g)
-    if (!(W1[(size_t)g] > 0.0)) alpha[g] = std::numeric_limits<double>::quiet_NaN();
-  for (int32_t l = 0; l < F->H; ++l)
-    if (!(W2[(size_t)l] > 0.0)) gamma[l] = std::numeric_limits<double>::quiet_NaN();
+  int32_t geff = 0, heff = 0;
+  if (int rc = count_levels(h, &geff, &heff, alpha, gamma)) return rc;
   if (info) {
     info->G_eff = geff;
     info->H_eff = heff;
@@ -814,26 +695,18 @@ int sglm_fe2_pass(sglm_engine* h, const sglm_glm_opts* opts, const sglm_fe2_opts
   int32_t G = 0;
   if (int rc = fe2_check(h, opts, &G)) return rc;
   Fe2* F = h->fe2;
-  Fe2Scope scope(h);
+  FeScope scope(h);
   const int64_t p = h->p, H = F->H;
-  double mu0 = 0.0;
-  int mode = MODE_IRLS;
-  if (!beta) {
-    double sums[2];
-    if (int rc = h->global_sums(sums)) return rc;
-    mu0 = sums[0] / sums[1];
-    mode = opts->init_mode == SGLM_INIT_MULTIPLE ? MODE_INIT_MULTI : MODE_INIT_SINGLE;
-  }
-  if (int rc = set_effects(h, h->dalpha, alpha, G)) return rc;
-  if (int rc = set_effects(h, F->dgamma, gamma, H)) return rc;
+  double mu0;
+  int mode;
+  if (int rc = fe_step_mode(h, opts, beta, &mode, &mu0)) return rc;
+  if (int rc = h->set_effects(h->dalpha, alpha, G)) return rc;
+  if (int rc = h->set_effects(F->dgamma, gamma, H)) return rc;
   if (int rc = zero_Y(h)) return rc;
-  std::vector<double> packed((size_t)packed_len(p)), g((size_t)(p * p)), x((size_t)p);
+  std::vector<double> packed((size_t)packed_len(p));
   int k = 0;
   if (int rc = fe2_step(h, fe2, opts->family, opts->link, mode, beta, mu0, false, 0, packed.data(), &k)) return rc;
-  unpack_gram(packed.data(), p, g.data(), x.data());
-  if (A) std::memcpy(A, g.data(), sizeof(double) * g.size());
-  if (b) std::memcpy(b, x.data(), sizeof(double) * x.size());
-  if (scalars) std::memcpy(scalars, packed.data() + tri_count(p) + p, sizeof(double) * NS);
+  fe_unpack_step(packed.data(), p, A, b, scalars);
   if (sweeps) *sweeps = k;
   if (group1)
     if (int rc = download_cols(h, h->dfg, F->ld1, G, 0, p + 2, group1)) return rc;
@@ -860,40 +733,24 @@ int sglm_vcov_fe2(sglm_engine* h, const sglm_glm_opts* opts, const sglm_fe2_opts
     set_error("requirement failed: beta, alpha, gamma, cov");
     return SGLM_EINVAL;
   }
-  if (cluster && hc_type != SGLM_HC0 && hc_type != SGLM_HC1) {
-    set_error("requirement failed: hc_type SGLM_HC0 or SGLM_HC1 under clustering (HC2 / HC3 need per-cluster "
-              "leverage blocks, which the engine does not form)");
-    return SGLM_EINVAL;
-  }
+  if (cluster)
+    if (int rc = check_cluster_hc(hc_type)) return rc;
   int32_t G = 0;
   if (int rc = fe2_check(h, opts, &G)) return rc;
-  if (cluster && cadjust && G < 2) {
-    set_error("requirement failed: cadjust (the factor G / (G - 1)) needs G >= 2 clusters");
-    return SGLM_EINVAL;
-  }
+  if (cluster)
+    if (int rc = check_cadjust(cadjust, G)) return rc;
   Fe2* F = h->fe2;
-  Fe2Scope scope(h);
+  FeScope scope(h);
   const int64_t p = h->p;
-  if (int rc = set_effects(h, h->dalpha, alpha, G)) return rc;
-  if (int rc = set_effects(h, F->dgamma, gamma, F->H)) return rc;
+  if (int rc = h->set_effects(h->dalpha, alpha, G)) return rc;
+  if (int rc = h->set_effects(F->dgamma, gamma, F->H)) return rc;
   if (int rc = zero_Y(h)) return rc;
-  std::vector<double> packed((size_t)packed_len(p)), C((size_t)(p * p)), M((size_t)(p * p)), x((size_t)p);
+  std::vector<double> packed((size_t)packed_len(p)), C, M((size_t)(p * p)), x((size_t)p);
   int k = 0;
   if (int rc = fe2_step(h, fe2, opts->family, opts->link, MODE_IRLS, beta, 0.0, true, 0, packed.data(), &k)) return rc;
-  std::unique_ptr<SolverIface> solver = h->make_solver(p);
-  const double t0 = now_ms();
-  if (const int srv = solver->solve(packed.data(), x.data())) {
-    if (srv == SGLM_ESINGULAR) set_error("breeze.linalg.MatrixSingularException: the two-way within X'WX is singular");
-    return srv;
-  }
-  if (int rc = solver->inverse(C.data())) return rc;
-  h->solve_ms += now_ms() - t0;
-  h->solve_path = solver->path();
-  if (!cluster) {
-    std::memcpy(cov, C.data(), sizeof(double) * C.size());
-    if (meat) std::fill(meat, meat + p * p, 0.0);
-    return SGLM_OK;
-  }
+  const char* singular = "breeze.linalg.MatrixSingularException: the two-way within X'WX is singular";
+  if (int rc = fe_bread(h, packed.data(), singular, C)) return rc;
+  if (!cluster) return fe_plain_cov(C, cov, meat);
   int32_t geff = 0, heff = 0;
   if (int rc = count_levels(h, &geff, &heff)) return rc;
   // the u-weighted sums S | U over factor 1 into dfg (u in domega), then sum_{i in g} u_i c_{h(i)} into T1
@@ -916,16 +773,9 @@ int sglm_vcov_fe2(sglm_engine* h, const sglm_glm_opts* opts, const sglm_fe2_opts
   h->cl_S_stale = true;                 // the cluster-robust covariance's S lives in the same design
   if (int rc = in->pass(MODE_LM_GRAM, nullptr, 0.0, 0.0, FAM_GAUSSIAN, LNK_IDENTITY, packed.data())) return rc;
   unpack_gram(packed.data(), p, M.data(), x.data());
-  const double nrows = (double)h->n;  // every row, weight 0 included
-  double f = hc_type == SGLM_HC1 ? (nrows - 1.0) / (nrows - (double)p - (double)(geff + heff - F->ncomp)) : 1.0;
-  if (cadjust) f *= (double)G / ((double)G - 1.0);
-  if (!sandwich_product(C, M, p, f, cov)) {
-    set_error("requirement failed: the cluster-robust covariance is not finite (a row whose mean leaves the "
-              "family's range at (beta, alpha, gamma))");
-    return SGLM_EINVAL;
-  }
-  if (meat) std::memcpy(meat, M.data(), sizeof(double) * M.size());
-  return SGLM_OK;
+  // nrows: every row, weight 0 included
+  const int64_t absorbed = geff + heff - F->ncomp;
+  return clustered_finish(hc_type, (double)h->n, p, absorbed, G, cadjust, C, M, "(beta, alpha, gamma)", cov, meat);
 }
 
 int sglm_get_fe2_ms(sglm_engine* h, double* ms) {

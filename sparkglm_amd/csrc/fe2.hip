@@ -7,7 +7,9 @@
 //   (chunk, 64-column slab): segment_sum_kernel's structure with the 32 staged rows addressed through the
 //   list -- lane l loads row l % 32 of column 2 q + l / 32, the products go transposed into LDS (row stride
 //   65 doubles), the next 32 rows are loaded into registers before the walk, and in the walk a lane owns a
-//   column and adds the staged rows in list order.  The two row vectors ride along as columns p and p + 1.
+//   column and adds the staged rows in list order.  The two row vectors ride along as columns p and p + 1:
+//   w z and w (the check: y and m - y), which fe.hip's fe_weights_kernel stored per row -- no kernel here
+//   evaluates a row's family or link.
 // fe2_gather_kernel     R[k, :] = sum over unit k of v_i src[id_i, :], src a row-major level matrix: one wave
 //   per (unit, slab), a lane owns a column, every gathered row is one contiguous read.  The units are the
 //   segments of the cluster factor (rows consecutive) or the chunks of factor 2's list.
@@ -23,7 +25,6 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
-#include "rowmath.hpp"
 
 namespace sglm {
 
@@ -35,47 +36,6 @@ constexpr int F2_WG_PER_CU = 16;
 static_assert(FE2_CHUNK % F2_SUB == 0, "chunks are whole staged steps");
 
 typedef double d4 __attribute__((ext_vector_type(4)));
-
-// w z of one row in the reference operation order: fe.hip's fe_row, from the same primitives
-__device__ __noinline__ double fe2_row_wz(int fam, int lnk, int mode, double eta, double y, double m, double off,
-                                           double pw, double mu0, double theta) {
-  const bool x = noncanonical_pair(fam, lnk);
-  double mu;
-  if (mode == MODE_IRLS) {
-    mu = x ? unlink_fn_x(lnk, eta) : unlink_fn(fam, lnk, eta, m);
-  } else {
-    eta = x ? link_fn_x(lnk, mu0) : link_fn(fam, lnk, mu0, m);
-    mu = mode == MODE_INIT_SINGLE ? mu0 : (x ? unlink_fn_x(lnk, eta) : unlink_fn(fam, lnk, eta, m));
-  }
-  const double g = x ? lprime_fn_x(lnk, mu) : lprime_fn(fam, lnk, mu, m);
-  const double v = fam == FAM_NEGBIN ? nb_variance(mu, theta) : variance_fn(fam, mu, m);
-  const double w = pw * (1.0 / (v * (g * g)));
-  const double z = (eta + ((y + (-1.0 * mu)) * g)) + (-1.0 * off);
-  return w * z;
-}
-
-__global__ void __launch_bounds__(256) fe2_rows_kernel(Fe2RowsArgs a) {
-  for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < a.ld; row += (int64_t)gridDim.x * 256) {
-    double v0 = 0.0, v1 = 0.0;
-    if (row < a.n) {
-      const double pw = a.prior ? a.prior[row] : 1.0;
-      if (pw != 0.0) {
-        const double y = a.y[row], m = a.m ? a.m[row] : 1.0;
-        if (a.kind == FE_CHECK) {
-          if (pw > 0.0) {
-            v0 = y;
-            v1 = a.family == FAM_BINOMIAL ? m - y : 1.0;
-          }
-        } else {
-          const double eta = a.mode == MODE_IRLS ? a.eta[row] : 0.0;
-          v0 = fe2_row_wz(a.family, a.link, a.mode, eta, y, m, a.off ? a.off[row] : 0.0, pw, a.mu0, a.theta);
-        }
-      }
-    }
-    a.out0[row] = v0;
-    if (a.out1) a.out1[row] = v1;
-  }
-}
 
 __global__ void __launch_bounds__(64) fe2_list_sum_kernel(Fe2ListSumArgs a) {
   __shared__ double xs[F2_SUB * F2_LDW];
@@ -270,14 +230,6 @@ inline unsigned blocks_of(int64_t n, int64_t cap = 65536) {
 // one wave per unit until the device is full: nothing depends on the grid
 int fe2_grid(int ncu, int64_t units) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(units, (int64_t)ncu * F2_WG_PER_CU));
-}
-
-hipError_t launch_fe2_rows(const Fe2RowsArgs& a, hipStream_t st) {
-  if (a.ld < 1 || !a.y || !a.out0 || (a.kind == FE_CHECK && !a.out1) ||
-      (a.kind != FE_CHECK && a.mode == MODE_IRLS && !a.eta))
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL(fe2_rows_kernel, dim3(blocks_of(a.ld)), dim3(256), 0, st, a);
-  return hipGetLastError();
 }
 
 hipError_t launch_fe2_list_sum(const Fe2ListSumArgs& a, int ncu, hipStream_t st) {

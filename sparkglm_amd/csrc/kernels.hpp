@@ -94,7 +94,6 @@ hipError_t launch_fe_scale(const FeGroupArgs& a, hipStream_t st);
 // two-way fixed effects (fe2.hip): the sums over factor 2's row lists, the gathers of the sweeps, the level
 // update with its stop-rule maxima, the cross product S_X' Y, the offset and the effects
 int fe2_grid(int ncu, int64_t units);
-hipError_t launch_fe2_rows(const Fe2RowsArgs& a, hipStream_t st);
 hipError_t launch_fe2_list_sum(const Fe2ListSumArgs& a, int ncu, hipStream_t st);
 hipError_t launch_fe2_gather(const Fe2GatherArgs& a, int ncu, hipStream_t st);
 hipError_t launch_fe2_update(const Fe2UpdateArgs& a, hipStream_t st);

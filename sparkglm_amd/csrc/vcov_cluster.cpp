@@ -29,6 +29,65 @@ void sglm_engine::free_clusters(bool inner_too) {
   }
 }
 
+// The combine's plan (engine.hpp): level by level, the open ranges cut into chunks
+int64_t sglm::plan_combine(std::vector<CombineRange> cur, std::vector<int64_t>& idx,
+                           std::vector<sglm_engine::CombineLevel>& levels) {
+  std::vector<CombineRange> next;
+  int64_t prow = 0;  // rows of the scratch handed out so far (a level reads the rows the one before wrote)
+  int64_t in_row = -1;
+  while (!cur.empty()) {
+    sglm_engine::CombineLevel lv{};
+    lv.start_off = (int64_t)idx.size();
+    lv.in_row = in_row;
+    lv.out_row = prow;
+    std::vector<int64_t> dst;
+    next.clear();
+    int64_t out = 0;
+    for (const CombineRange& r : cur) {
+      const int64_t nch = (r.hi - r.lo + CLUSTER_CHUNK - 1) / CLUSTER_CHUNK;
+      if (nch > 1) next.push_back({r.dst, out, out + nch});
+      for (int64_t c = 0; c < nch; ++c) {
+        idx.push_back(r.lo + c * CLUSTER_CHUNK);
+        dst.push_back(nch == 1 ? r.dst : -(out++ + 1));
+      }
+    }
+    idx.push_back(cur.back().hi);
+    lv.nchunk = (int64_t)dst.size();
+    lv.dst_off = (int64_t)idx.size();
+    idx.insert(idx.end(), dst.begin(), dst.end());
+    levels.push_back(lv);
+    in_row = prow;
+    prow += out;
+    cur.swap(next);
+  }
+  return prow;
+}
+
+int sglm::combine_levels(sglm_engine* s, const std::vector<sglm_engine::CombineLevel>& levels, const int64_t* base,
+                         const int64_t* idx0, const double* R, double* P, int ncol, double* S, int64_t ldS,
+                         hipEvent_t e0, hipEvent_t e1) {
+  for (size_t l = 0; l < levels.size(); ++l) {
+    const sglm_engine::CombineLevel& lv = levels[l];
+    CombineArgs c{};
+    c.in = l == 0 ? R : P + lv.in_row * ncol;
+    c.idx = l == 0 ? idx0 : nullptr;
+    c.chunk_start = base + lv.start_off;
+    c.chunk_dst = base + lv.dst_off;
+    c.nchunk = lv.nchunk;
+    c.p = ncol;
+    c.S = S;
+    c.ldS = ldS;
+    c.out = P ? P + lv.out_row * ncol : nullptr;
+    HIPCHK(launch_cluster_combine(c, s->ncu, s->st, l == 0 ? e0 : nullptr, l + 1 == levels.size() ? e1 : nullptr));
+  }
+  return SGLM_OK;
+}
+
+int sglm_engine::combine_clusters(const double* R, double* P, int ncol, double* S, int64_t ldS, hipEvent_t e0,
+                                  hipEvent_t e1) {
+  return combine_levels(this, cl_levels, dclidx, cl_seg(), R, P, ncol, S, ldS, e0, e1);
+}
+
 // The segments of this shard's rows under ids, the combine's levels over their CSR by cluster, and
 // the buffers of the segment sums and of the combine's partial sums.
 int sglm_engine::set_clusters_local(const int32_t* ids, int64_t nl, int32_t G) {
@@ -47,63 +106,30 @@ int sglm_engine::set_clusters_local(const int32_t* ids, int64_t nl, int32_t G) {
   const int64_t ntiles = (n + CLUSTER_TILE_ROWS - 1) / CLUSTER_TILE_ROWS;
   // seg_start [nseg + 2] | tile_seg [ntiles + 1] | cl_seg [nseg] | the levels' chunk_start, chunk_dst | seg_cluster [nseg]
   std::vector<int64_t> idx((size_t)(nseg + 2 + ntiles + 1 + nseg));
-  std::vector<int32_t> seg_cluster((size_t)nseg);
+  std::vector<int32_t> seg_cl((size_t)nseg);
   std::vector<int64_t> cl_ptr((size_t)G + 1, 0);
   {
-    int64_t* seg_start = idx.data();
-    int64_t* tile_seg = seg_start + nseg + 2;
-    int64_t* cl_seg = tile_seg + ntiles + 1;
-    (void)cluster_segments(ids, n, G, seg_start, seg_cluster.data());
-    seg_start[nseg + 1] = std::numeric_limits<int64_t>::max();  // never a row: the walk past the last segment
+    int64_t* start = idx.data();
+    int64_t* tile = start + nseg + 2;
+    int64_t* by_cluster = tile + ntiles + 1;
+    (void)cluster_segments(ids, n, G, start, seg_cl.data());
+    start[nseg + 1] = std::numeric_limits<int64_t>::max();  // never a row: the walk past the last segment
     for (int64_t k = 0; k < nseg; ++k)
-      if (seg_start[k] % CLUSTER_TILE_ROWS == 0) tile_seg[seg_start[k] / CLUSTER_TILE_ROWS] = k;
-    tile_seg[ntiles] = nseg;
+      if (start[k] % CLUSTER_TILE_ROWS == 0) tile[start[k] / CLUSTER_TILE_ROWS] = k;
+    tile[ntiles] = nseg;
     // segments stably ordered by cluster: a cluster's segments in row order
-    for (int64_t k = 0; k < nseg; ++k) cl_ptr[(size_t)seg_cluster[(size_t)k] + 1] += 1;
+    for (int64_t k = 0; k < nseg; ++k) cl_ptr[(size_t)seg_cl[(size_t)k] + 1] += 1;
     for (int32_t g = 0; g < G; ++g) cl_ptr[(size_t)g + 1] += cl_ptr[(size_t)g];
     std::vector<int64_t> at(cl_ptr.begin(), cl_ptr.end() - 1);
-    for (int64_t k = 0; k < nseg; ++k) cl_seg[at[(size_t)seg_cluster[(size_t)k]]++] = k;
+    for (int64_t k = 0; k < nseg; ++k) by_cluster[at[(size_t)seg_cl[(size_t)k]]++] = k;
   }
-  // The combine's levels.  A level's input is a list of rows in which every cluster still open owns a
-  // contiguous range (level 0: the CSR positions of its segments); the range is cut into chunks of
-  // CLUSTER_CHUNK rows.  One chunk: it is summed into S and the cluster is done.  Several: each is
-  // summed into a row of the scratch, and those rows are the cluster's range at the next level.
-  struct Range {
-    int32_t g;
-    int64_t lo, hi;
-  };
-  std::vector<Range> cur, next;
+  // the combine's levels: at level 0 a cluster owns the CSR positions of its segments
+  std::vector<CombineRange> open;
   for (int32_t g = 0; g < G; ++g)
-    if (cl_ptr[(size_t)g + 1] > cl_ptr[(size_t)g]) cur.push_back({g, cl_ptr[(size_t)g], cl_ptr[(size_t)g + 1]});
-  int64_t prow = 0;  // rows of the scratch handed out so far (a level reads the rows the one before wrote)
-  int64_t in_row = -1;
-  while (!cur.empty()) {
-    CombineLevel lv{};
-    lv.start_off = (int64_t)idx.size();
-    lv.in_row = in_row;
-    lv.out_row = prow;
-    std::vector<int64_t> dst;
-    next.clear();
-    int64_t out = 0;
-    for (const Range& r : cur) {
-      const int64_t nch = (r.hi - r.lo + CLUSTER_CHUNK - 1) / CLUSTER_CHUNK;
-      if (nch > 1) next.push_back({r.g, out, out + nch});
-      for (int64_t c = 0; c < nch; ++c) {
-        idx.push_back(r.lo + c * CLUSTER_CHUNK);
-        dst.push_back(nch == 1 ? (int64_t)r.g : -(out++ + 1));
-      }
-    }
-    idx.push_back(cur.back().hi);
-    lv.nchunk = (int64_t)dst.size();
-    lv.dst_off = (int64_t)idx.size();
-    idx.insert(idx.end(), dst.begin(), dst.end());
-    cl_levels.push_back(lv);
-    in_row = prow;
-    prow += out;
-    cur.swap(next);
-  }
+    if (cl_ptr[(size_t)g + 1] > cl_ptr[(size_t)g]) open.push_back({g, cl_ptr[(size_t)g], cl_ptr[(size_t)g + 1]});
+  const int64_t prow = plan_combine(std::move(open), idx, cl_levels);
   cl_segcl_off = (int64_t)idx.size();  // seg_cluster [nseg]: the fixed-effects offset kernel's (fe.hip)
-  idx.insert(idx.end(), seg_cluster.begin(), seg_cluster.end());
+  idx.insert(idx.end(), seg_cl.begin(), seg_cl.end());
   cl_prow = prow;
   hipError_t e = hipMalloc(&dclidx, sizeof(int64_t) * idx.size());
   if (e == hipSuccess) e = hipMalloc(&dR, sizeof(double) * (size_t)std::max<int64_t>(nseg * p, 1));
@@ -188,28 +214,12 @@ int sglm_engine::cluster_sums_local() {
   a.p = (int)p;
   a.n = n;
   a.u = domega;
-  a.seg_start = dclidx;
-  a.tile_seg = a.seg_start + cl_nseg + 2;
+  a.seg_start = seg_start();
+  a.tile_seg = tile_seg();
   a.ntiles = cl_ntiles;
   a.R = dR;
   HIPCHK(launch_cluster_sum(a, cluster_sum_grid(ncu, n, (int)p), st, evcl[0], evcl[1]));
-  const int64_t* cl_seg = a.tile_seg + cl_ntiles + 1;
-  for (size_t l = 0; l < cl_levels.size(); ++l) {
-    const CombineLevel& lv = cl_levels[l];
-    CombineArgs c{};
-    c.in = l == 0 ? dR : dP + lv.in_row * p;
-    c.idx = l == 0 ? cl_seg : nullptr;
-    c.chunk_start = dclidx + lv.start_off;
-    c.chunk_dst = dclidx + lv.dst_off;
-    c.nchunk = lv.nchunk;
-    c.p = (int)p;
-    c.S = cl_inner->dX;
-    c.ldS = cl_inner->n_pad;
-    c.out = dP ? dP + lv.out_row * p : nullptr;
-    HIPCHK(launch_cluster_combine(c, ncu, st, l == 0 ? evcl[2] : nullptr,
-                                  l + 1 == cl_levels.size() ? evcl[3] : nullptr));
-  }
-  return SGLM_OK;
+  return combine_clusters(dR, dP, (int)p, cl_inner->dX, cl_inner->n_pad, evcl[2], evcl[3]);
 }
 
 int sglm_engine::cluster_sync() {
@@ -316,6 +326,33 @@ int sglm::cluster_count(sglm_engine* h, int32_t* Gout) {
   return SGLM_OK;
 }
 
+int sglm::check_cluster_hc(int hc_type) {
+  if (hc_type == SGLM_HC0 || hc_type == SGLM_HC1) return SGLM_OK;
+  set_error("requirement failed: hc_type SGLM_HC0 or SGLM_HC1 under clustering (HC2 / HC3 need per-cluster "
+            "leverage blocks, which the engine does not form)");
+  return SGLM_EINVAL;
+}
+
+int sglm::check_cadjust(int cadjust, int32_t G) {
+  if (!cadjust || G >= 2) return SGLM_OK;
+  set_error("requirement failed: cadjust (the factor G / (G - 1)) needs G >= 2 clusters");
+  return SGLM_EINVAL;
+}
+
+int sglm::clustered_finish(int hc_type, double nrows, int64_t p, int64_t absorbed, int32_t G, int cadjust,
+                           const std::vector<double>& C, const std::vector<double>& M, const char* at, double* cov,
+                           double* meat) {
+  double f = hc_type == SGLM_HC1 ? (nrows - 1.0) / (nrows - (double)p - (double)absorbed) : 1.0;
+  if (cadjust) f *= (double)G / ((double)G - 1.0);
+  if (!sandwich_product(C, M, p, f, cov)) {
+    set_error(std::string("requirement failed: the cluster-robust covariance is not finite (a row whose mean leaves "
+                          "the family's range at ") + at + ")");
+    return SGLM_EINVAL;
+  }
+  if (meat) std::memcpy(meat, M.data(), sizeof(double) * M.size());
+  return SGLM_OK;
+}
+
 extern "C" {
 
 int sglm_cluster_plan(const int32_t* ids, int64_t n, int32_t G, int64_t* tile_rows, int64_t* nseg, int64_t* seg_start,
@@ -364,11 +401,7 @@ int sglm_vcov_cluster(sglm_engine* h, const sglm_glm_opts* opts, const double* b
     set_error("requirement failed: opts with a supported family/link, beta, cov");
     return SGLM_EINVAL;
   }
-  if (hc_type != SGLM_HC0 && hc_type != SGLM_HC1) {
-    set_error("requirement failed: hc_type SGLM_HC0 or SGLM_HC1 under clustering (HC2 / HC3 need per-cluster "
-              "leverage blocks, which the engine does not form)");
-    return SGLM_EINVAL;
-  }
+  if (int rc = check_cluster_hc(hc_type)) return rc;
   if (int rc = check_handle(h)) return rc;
   if (int rc = check_ready(h)) return rc;
   if (int rc = require_fused_or_narrow(h, "the cluster-robust covariance needs")) return rc;
@@ -378,10 +411,7 @@ int sglm_vcov_cluster(sglm_engine* h, const sglm_glm_opts* opts, const double* b
   }
   int32_t G = 0;
   if (int rc = cluster_count(h, &G)) return rc;
-  if (cadjust && G < 2) {
-    set_error("requirement failed: cadjust (the factor G / (G - 1)) needs G >= 2 clusters");
-    return SGLM_EINVAL;
-  }
+  if (int rc = check_cadjust(cadjust, G)) return rc;
   const std::vector<sglm_engine*>& shards = h->shards();
   const int64_t p = h->ncols();
   std::vector<double> C((size_t)(p * p)), M((size_t)(p * p)), x((size_t)p);
@@ -408,15 +438,7 @@ int sglm_vcov_cluster(sglm_engine* h, const sglm_glm_opts* opts, const double* b
   double nrows = (double)(h->group() ? h->g_n : h->n);  // HC1: every row of every shard, weight 0 included
   if (hc_type == SGLM_HC1 && !h->group())
     if (int rc = h->allreduce_small(&nrows, 1)) return rc;
-  double f = hc_type == SGLM_HC1 ? (nrows - 1.0) / (nrows - (double)p) : 1.0;
-  if (cadjust) f *= (double)G / ((double)G - 1.0);
-  if (!sandwich_product(C, M, p, f, cov)) {
-    set_error("requirement failed: the cluster-robust covariance is not finite (a row whose mean leaves the "
-              "family's range at beta)");
-    return SGLM_EINVAL;
-  }
-  if (meat) std::memcpy(meat, M.data(), sizeof(double) * M.size());
-  return SGLM_OK;
+  return clustered_finish(hc_type, nrows, p, 0, G, cadjust, C, M, "beta", cov, meat);
 }
 
 int sglm_get_cluster_ms(sglm_engine* h, double* score_ms, double* sum_ms, double* combine_ms, double* gram_ms) {

@@ -279,16 +279,27 @@ class Engine:
         """`start` (R's start=): coefficients the iterations begin at (sglm_fit_glm_start); dev_trace[0] is
         then the deviance at `start`.  family "negbin" fits at the handle's theta (set_theta)."""
         o = glm_opts(family, link, tol, verbose, max_iter, init, npart)
-        coefs, se = np.zeros(self.p), np.zeros(self.p)
-        trace = np.full(max_trace, np.nan)
-        pre = L.PreGLM(L.ptr(coefs), L.ptr(se), 0, 0, 0, 0, 0, 0, 0, L.ptr(trace), max_trace)
+        pre, fit = self._pre(max_trace)
         if start is None:
             L.check(self._lib.sglm_fit_glm(self._h, C.byref(o), C.byref(pre)), "sglm_fit_glm")
         else:
             b = self._beta(start)
             L.check(self._lib.sglm_fit_glm_start(self._h, C.byref(o), L.ptr(b), C.byref(pre)), "sglm_fit_glm_start")
-        return FitGLM(coefs, se, pre.deviance, pre.null_deviance, pre.pearson, pre.loglik, pre.iter, pre.nrow,
-                      pre.npart, trace[: pre.iter + 1].copy())
+        return fit()
+
+    def _pre(self, max_trace):
+        """The PreGLM a fit writes, over fresh arrays, and the function that makes its FitGLM after the fit."""
+        coefs, se, trace = np.zeros(self.p), np.zeros(self.p), np.full(max_trace, np.nan)
+        pre = L.PreGLM(L.ptr(coefs), L.ptr(se), 0, 0, 0, 0, 0, 0, 0, L.ptr(trace), max_trace)
+        return pre, lambda: FitGLM(coefs, se, pre.deviance, pre.null_deviance, pre.pearson, pre.loglik, pre.iter,
+                                   pre.nrow, pre.npart, trace[: pre.iter + 1].copy())
+
+    def _cov_meat(self, return_meat, name, call):
+        """cov, or (cov, meat), of the covariance entry point `name`: call(cov pointer, meat pointer or None)."""
+        cov = np.zeros((self.p, self.p), order="F")
+        meat = np.zeros((self.p, self.p), order="F") if return_meat else None
+        L.check(call(cov.ctypes.data_as(L.dp), None if meat is None else meat.ctypes.data_as(L.dp)), name)
+        return (cov, meat) if return_meat else cov
 
     def _beta(self, beta):
         b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
@@ -336,15 +347,11 @@ class Engine:
         fits; theta stays set on the handle.  Zeros take the defaults 25 / 1e-8 / 25 / 2^-13."""
         o = glm_opts("negbin", link, tol, False, max_iter, init, npart)
         nbo = L.NbOpts(int(maxit), float(epsilon), int(theta_limit), float(theta_eps))
-        coefs, se = np.zeros(self.p), np.zeros(self.p)
-        trace = np.full(max_trace, np.nan)
-        pre = L.PreGLM(L.ptr(coefs), L.ptr(se), 0, 0, 0, 0, 0, 0, 0, L.ptr(trace), max_trace)
+        pre, fit = self._pre(max_trace)
         res = L.NbResult()
         L.check(self._lib.sglm_fit_glm_nb(self._h, C.byref(o), C.byref(nbo), C.byref(pre), C.byref(res)),
                 "sglm_fit_glm_nb")
-        f = FitGLM(coefs, se, pre.deviance, pre.null_deviance, pre.pearson, pre.loglik, pre.iter, pre.nrow,
-                   pre.npart, trace[: pre.iter + 1].copy())
-        return FitNB(f, res.theta, res.se_theta, res.twologlik, res.outer_iter, res.theta_warn, bool(res.converged))
+        return FitNB(fit(), res.theta, res.se_theta, res.twologlik, res.outer_iter, res.theta_warn, bool(res.converged))
 
     def fit_lm(self) -> FitLM:
         p = self.p
@@ -482,11 +489,8 @@ class Engine:
         if b.shape[0] != self.p:
             raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
                                              f"beta {b.shape[0]} rows")
-        cov = np.zeros((self.p, self.p), order="F")
-        meat = np.zeros((self.p, self.p), order="F") if return_meat else None
-        L.check(self._lib.sglm_vcov_robust(self._h, C.byref(o), L.ptr(b), L.HC_TYPES[type], cov.ctypes.data_as(L.dp),
-                                           None if meat is None else meat.ctypes.data_as(L.dp)), "sglm_vcov_robust")
-        return (cov, meat) if return_meat else cov
+        return self._cov_meat(return_meat, "sglm_vcov_robust", lambda cov, meat: self._lib.sglm_vcov_robust(
+            self._h, C.byref(o), L.ptr(b), L.HC_TYPES[type], cov, meat))
 
     def sandwich_ms(self):
         """Kernel times (score kernel, meat pass) of the last vcov_robust() call (HIP events)."""
@@ -505,18 +509,10 @@ class Engine:
             L.check(self._lib.sglm_set_clusters(self._h, None, 0, 0), "sglm_set_clusters")
             self._nclusters = 0
             return self
-        ids = np.asarray(ids).reshape(-1)
-        if G is None:
-            labels, ids = np.unique(ids, return_inverse=True)
-            G = len(labels)
-        elif ids.dtype.kind not in "iu":
-            raise L.IllegalArgumentException("requirement failed: with G given, ids are integer codes in [0, G)")
-        elif ids.size and (ids.min() < 0 or ids.max() >= G):  # before the cast to int32 can wrap a code
-            raise L.IllegalArgumentException(f"requirement failed: every cluster id in [0, G = {G})")
-        codes = np.ascontiguousarray(ids, dtype=np.int32)
-        L.check(self._lib.sglm_set_clusters(self._h, codes.ctypes.data_as(C.POINTER(C.c_int32)), codes.shape[0],
-                                            int(G)), "sglm_set_clusters")
-        self._nclusters = int(G)  # the length of the fixed-effects calls' alpha
+        codes, G = _codes(ids, G, "G", "cluster id")
+        L.check(self._lib.sglm_set_clusters(self._h, codes.ctypes.data_as(C.POINTER(C.c_int32)), codes.shape[0], G),
+                "sglm_set_clusters")
+        self._nclusters = G  # the length of the fixed-effects calls' alpha
         return self
 
     def vcov_cluster(self, beta, family="binomial", link="logit", type="HC1", cadjust=True, return_meat=False):
@@ -525,20 +521,14 @@ class Engine:
         "HC0" | "HC1" ((n - 1) / (n - p)); `cadjust` a further G / (G - 1).  The defaults are vcovCL's
         and Stata's regress, vce(cluster); "HC0" with cadjust is Stata's glm rule.  With `return_meat`
         the pair (V, M)."""
-        if type not in L.CLUSTER_TYPES:
-            raise L.IllegalArgumentException(f"requirement failed: with clusters, type must be one of "
-                                             f"{list(L.CLUSTER_TYPES)}, got {type!r}")
+        _cluster_type(type)
         o = glm_opts(family, link)
         b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
         if b.shape[0] != self.p:
             raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
                                              f"beta {b.shape[0]} rows")
-        cov = np.zeros((self.p, self.p), order="F")
-        meat = np.zeros((self.p, self.p), order="F") if return_meat else None
-        L.check(self._lib.sglm_vcov_cluster(self._h, C.byref(o), L.ptr(b), L.HC_TYPES[type], int(bool(cadjust)),
-                                            cov.ctypes.data_as(L.dp),
-                                            None if meat is None else meat.ctypes.data_as(L.dp)), "sglm_vcov_cluster")
-        return (cov, meat) if return_meat else cov
+        return self._cov_meat(return_meat, "sglm_vcov_cluster", lambda cov, meat: self._lib.sglm_vcov_cluster(
+            self._h, C.byref(o), L.ptr(b), L.HC_TYPES[type], int(bool(cadjust)), cov, meat))
 
     def cluster_ms(self):
         """Kernel times (score, segment sums, combine, the meat's Gram pass) of the last vcov_cluster()
@@ -553,25 +543,22 @@ class Engine:
         """The GLM with one fixed effect per cluster of set_clusters, absorbed (sglm_fit_glm_fe;
         fixest::feglm): every iterate is that of fit_glm on [X | dummies].  X holds no intercept."""
         o = glm_opts(family, link, tol, verbose, max_iter, init, npart)
-        coefs, se = np.zeros(self.p), np.zeros(self.p)
-        trace = np.full(max_trace, np.nan)
-        pre = L.PreGLM(L.ptr(coefs), L.ptr(se), 0, 0, 0, 0, 0, 0, 0, L.ptr(trace), max_trace)
+        pre, fit = self._pre(max_trace)
         alpha = np.zeros(max(self._G(), 1))
         info = L.FeInfo()
         L.check(self._lib.sglm_fit_glm_fe(self._h, C.byref(o), C.byref(pre), L.ptr(alpha), C.byref(info)),
                 "sglm_fit_glm_fe")
-        f = FitGLM(coefs, se, pre.deviance, pre.null_deviance, pre.pearson, pre.loglik, pre.iter, pre.nrow,
-                   pre.npart, trace[: pre.iter + 1].copy())
-        return FitFE(f, alpha[: self._G()], info.G_eff, info.df_residual)
+        return FitFE(fit(), alpha[: self._G()], info.G_eff, info.df_residual)
 
     def _G(self) -> int:
         return int(getattr(self, "_nclusters", 0))
 
-    def _alpha(self, alpha):
-        a = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
-        if a.shape[0] != self._G():
-            raise L.IllegalArgumentException(f"requirement failed: alpha has {a.shape[0]} entries for "
-                                             f"{self._G()} clusters (set_clusters)")
+    def _effects(self, v, name):
+        """alpha [G] or gamma [H] as a float64 vector of the declared length."""
+        a = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        want, what = (self._G(), "clusters (set_clusters)") if name == "alpha" else (self._H(), "levels (set_fe2)")
+        if a.shape[0] != want:
+            raise L.IllegalArgumentException(f"requirement failed: {name} has {a.shape[0]} entries for {want} {what}")
         return a
 
     def fe_pass(self, beta=None, alpha=None, family="poisson", link="log", init="single", sums=True):
@@ -583,7 +570,7 @@ class Engine:
         A, b, s = np.zeros((p, p), order="F"), np.zeros(p), np.zeros(L.NS)
         grp = np.zeros(max(G, 1) * (p + 2)) if sums else None
         bb = None if beta is None else self._beta(beta)
-        aa = None if alpha is None else self._alpha(alpha)
+        aa = None if alpha is None else self._effects(alpha, "alpha")
         L.check(self._lib.sglm_fe_pass(self._h, C.byref(o), L.ptr(bb), L.ptr(aa), A.ctypes.data_as(L.dp), L.ptr(b),
                                        L.ptr(grp), L.ptr(s)), "sglm_fe_pass")
         if not sums:
@@ -596,17 +583,13 @@ class Engine:
         """The covariance of beta at (beta, alpha) of a fixed-effects fit (sglm_vcov_fe): inv(A) with
         cluster=False, else clustered on the absorbed factor -- the beta block of sandwich::vcovCL on the
         dummy fit (`type` "HC0" | "HC1" with p + G_eff regressors, `cadjust`)."""
-        if cluster and type not in L.CLUSTER_TYPES:
-            raise L.IllegalArgumentException(f"requirement failed: with clusters, type must be one of "
-                                             f"{list(L.CLUSTER_TYPES)}, got {type!r}")
+        if cluster:
+            _cluster_type(type)
         o = glm_opts(family, link)
-        b, a = self._beta(beta), self._alpha(alpha)
-        cov = np.zeros((self.p, self.p), order="F")
-        meat = np.zeros((self.p, self.p), order="F") if return_meat else None
-        L.check(self._lib.sglm_vcov_fe(self._h, C.byref(o), L.ptr(b), L.ptr(a), int(bool(cluster)),
-                                       L.HC_TYPES.get(type, 0), int(bool(cadjust)), cov.ctypes.data_as(L.dp),
-                                       None if meat is None else meat.ctypes.data_as(L.dp)), "sglm_vcov_fe")
-        return (cov, meat) if return_meat else cov
+        b, a = self._beta(beta), self._effects(alpha, "alpha")
+        return self._cov_meat(return_meat, "sglm_vcov_fe", lambda cov, meat: self._lib.sglm_vcov_fe(
+            self._h, C.byref(o), L.ptr(b), L.ptr(a), int(bool(cluster)), L.HC_TYPES.get(type, 0), int(bool(cadjust)),
+            cov, meat))
 
     def fe_ms(self):
         """Kernel times (weights, segment sums, combine, the Gram pass over the group sums) of the last
@@ -624,30 +607,15 @@ class Engine:
             L.check(self._lib.sglm_set_fe2(self._h, None, 0, 0), "sglm_set_fe2")
             self._nfe2 = 0
             return self
-        ids = np.asarray(ids).reshape(-1)
-        if H is None:
-            labels, ids = np.unique(ids, return_inverse=True)
-            H = len(labels)
-        elif ids.dtype.kind not in "iu":
-            raise L.IllegalArgumentException("requirement failed: with H given, ids are integer codes in [0, H)")
-        elif ids.size and (ids.min() < 0 or ids.max() >= H):  # before the cast to int32 can wrap a code
-            raise L.IllegalArgumentException(f"requirement failed: every code of the second factor in [0, H = {H})")
-        codes = np.ascontiguousarray(ids, dtype=np.int32)
+        codes, H = _codes(ids, H, "H", "code of the second factor")
         self._nfe2 = 0
-        L.check(self._lib.sglm_set_fe2(self._h, codes.ctypes.data_as(C.POINTER(C.c_int32)), codes.shape[0], int(H)),
+        L.check(self._lib.sglm_set_fe2(self._h, codes.ctypes.data_as(C.POINTER(C.c_int32)), codes.shape[0], H),
                 "sglm_set_fe2")
-        self._nfe2 = int(H)
+        self._nfe2 = H
         return self
 
     def _H(self) -> int:
         return int(getattr(self, "_nfe2", 0))
-
-    def _gamma(self, gamma):
-        a = np.ascontiguousarray(gamma, dtype=np.float64).reshape(-1)
-        if a.shape[0] != self._H():
-            raise L.IllegalArgumentException(f"requirement failed: gamma has {a.shape[0]} entries for "
-                                             f"{self._H()} levels (set_fe2)")
-        return a
 
     @staticmethod
     def _fe2_opts(sweep_tol, max_sweeps):
@@ -660,16 +628,12 @@ class Engine:
         [X | D1 | D2 without one column per component].  X holds no intercept."""
         o = glm_opts(family, link, tol, verbose, max_iter, init, npart)
         fo = self._fe2_opts(sweep_tol, max_sweeps)
-        coefs, se = np.zeros(self.p), np.zeros(self.p)
-        trace = np.full(max_trace, np.nan)
-        pre = L.PreGLM(L.ptr(coefs), L.ptr(se), 0, 0, 0, 0, 0, 0, 0, L.ptr(trace), max_trace)
+        pre, fit = self._pre(max_trace)
         alpha, gamma = np.zeros(max(self._G(), 1)), np.zeros(max(self._H(), 1))
         info = L.Fe2Info()
         L.check(self._lib.sglm_fit_glm_fe2(self._h, C.byref(o), C.byref(fo), C.byref(pre), L.ptr(alpha), L.ptr(gamma),
                                            C.byref(info)), "sglm_fit_glm_fe2")
-        f = FitGLM(coefs, se, pre.deviance, pre.null_deviance, pre.pearson, pre.loglik, pre.iter, pre.nrow,
-                   pre.npart, trace[: pre.iter + 1].copy())
-        return FitFE2(f, alpha[: self._G()], gamma[: self._H()], (info.sweeps_last, info.sweeps_total),
+        return FitFE2(fit(), alpha[: self._G()], gamma[: self._H()], (info.sweeps_last, info.sweeps_total),
                       info.df_residual, info.ncomp, info.G_eff, info.H_eff)
 
     def fe2_pass(self, beta=None, alpha=None, gamma=None, family="poisson", link="log", init="single",
@@ -687,8 +651,8 @@ class Engine:
         Y = np.zeros((max(G + H, 1), p + 1), order="F") if sums else None
         k = C.c_int()
         bb = None if beta is None else self._beta(beta)
-        aa = None if alpha is None else self._alpha(alpha)
-        gg = None if gamma is None else self._gamma(gamma)
+        aa = None if alpha is None else self._effects(alpha, "alpha")
+        gg = None if gamma is None else self._effects(gamma, "gamma")
         L.check(self._lib.sglm_fe2_pass(self._h, C.byref(o), C.byref(fo), L.ptr(bb), L.ptr(aa), L.ptr(gg),
                                         A.ctypes.data_as(L.dp), L.ptr(b), L.ptr(g1), L.ptr(g2),
                                         None if Y is None else Y.ctypes.data_as(L.dp), L.ptr(s), C.byref(k)),
@@ -706,19 +670,14 @@ class Engine:
                  return_meat=False, sweep_tol=0.0, max_sweeps=0):
         """The covariance of beta at (beta, alpha, gamma) of a two-way fit (sglm_vcov_fe2): inv(A) with
         cluster=False, else clustered on factor 1 -- the beta block of sandwich::vcovCL on the dummy fit."""
-        if cluster and type not in L.CLUSTER_TYPES:
-            raise L.IllegalArgumentException(f"requirement failed: with clusters, type must be one of "
-                                             f"{list(L.CLUSTER_TYPES)}, got {type!r}")
+        if cluster:
+            _cluster_type(type)
         o = glm_opts(family, link)
         fo = self._fe2_opts(sweep_tol, max_sweeps)
-        b, a, g = self._beta(beta), self._alpha(alpha), self._gamma(gamma)
-        cov = np.zeros((self.p, self.p), order="F")
-        meat = np.zeros((self.p, self.p), order="F") if return_meat else None
-        L.check(self._lib.sglm_vcov_fe2(self._h, C.byref(o), C.byref(fo), L.ptr(b), L.ptr(a), L.ptr(g),
-                                        int(bool(cluster)), L.HC_TYPES.get(type, 0), int(bool(cadjust)),
-                                        cov.ctypes.data_as(L.dp),
-                                        None if meat is None else meat.ctypes.data_as(L.dp)), "sglm_vcov_fe2")
-        return (cov, meat) if return_meat else cov
+        b, a, g = self._beta(beta), self._effects(alpha, "alpha"), self._effects(gamma, "gamma")
+        return self._cov_meat(return_meat, "sglm_vcov_fe2", lambda cov, meat: self._lib.sglm_vcov_fe2(
+            self._h, C.byref(o), C.byref(fo), L.ptr(b), L.ptr(a), L.ptr(g), int(bool(cluster)), L.HC_TYPES.get(type, 0),
+            int(bool(cadjust)), cov, meat))
 
     def fe2_ms(self):
         """Kernel times (weights, factor-1 sums, factor-2 sums, sweeps, cross product) of the last two-way
@@ -745,6 +704,26 @@ class Engine:
 
     def reset_stats(self):
         L.check(self._lib.sglm_reset_stats(self._h))
+
+
+def _cluster_type(type):
+    if type not in L.CLUSTER_TYPES:
+        raise L.IllegalArgumentException(f"requirement failed: with clusters, type must be one of "
+                                         f"{list(L.CLUSTER_TYPES)}, got {type!r}")
+
+
+def _codes(ids, nlev, name, what):
+    """(int32 codes, level count) of a factor: labels of any dtype factorised (nlev None), or dense codes checked
+    to lie in [0, nlev); `name` / `what`: the count and a code in the caller's messages."""
+    ids = np.asarray(ids).reshape(-1)
+    if nlev is None:
+        labels, ids = np.unique(ids, return_inverse=True)
+        nlev = len(labels)
+    elif ids.dtype.kind not in "iu":
+        raise L.IllegalArgumentException(f"requirement failed: with {name} given, ids are integer codes in [0, {name})")
+    elif ids.size and (ids.min() < 0 or ids.max() >= nlev):  # before the cast to int32 can wrap a code
+        raise L.IllegalArgumentException(f"requirement failed: every {what} in [0, {name} = {nlev})")
+    return np.ascontiguousarray(ids, dtype=np.int32), int(nlev)
 
 
 def _ptype(t) -> int:

@@ -346,6 +346,51 @@ def fe_offsets(fixef, labels, offset=None):
     return a if offset is None else a + np.asarray(offset, dtype=np.float64)
 
 
+@dataclass
+class FeData:
+    """The arrays of a fixed-effects fit: the engine's family and link, X without its intercept and the names of
+    its columns, the row vectors (None: not given), the labels and dense codes of the factor (of both factors of
+    a two-way fit) and what was dropped as uninformative: levels over both factors, and rows."""
+    fam: str
+    lnk: str
+    X: np.ndarray
+    names: List[str]
+    y: np.ndarray
+    m: Optional[np.ndarray]
+    offset: Optional[np.ndarray]
+    prior: Optional[np.ndarray]
+    labels: np.ndarray
+    codes: np.ndarray
+    labels2: Optional[np.ndarray] = None
+    codes2: Optional[np.ndarray] = None
+    dropped: int = 0
+    dropped_rows: int = 0
+
+    def drop(self, keep, nlev: int, quiet: bool):
+        """Only the rows of `keep` stay, the factors are coded again; nlev levels go with the other rows."""
+        self.dropped, self.dropped_rows = nlev, int((~keep).sum())
+        if not quiet:
+            print(f"NOTE: {nlev} fixed effect(s) ({self.dropped_rows} rows) removed because of only 0"
+                  f"{' (or only m)' if self.fam == 'binomial' else ''} outcomes.")
+        self.X, self.y = np.asfortranarray(self.X[keep]), self.y[keep]
+        self.m, self.offset, self.prior = (None if v is None else v[keep] for v in (self.m, self.offset, self.prior))
+        self.labels, self.codes = fe_codes(self.labels[self.codes[keep]])
+        if self.codes2 is not None:
+            self.labels2, self.codes2 = fe_codes(self.labels2[self.codes2[keep]])
+
+    def load(self, theta, device: int) -> Engine:
+        """The data and the factors on the device's engine."""
+        eng = _engine(device)
+        if self.fam == "negbin":
+            _require(theta is not None, "family negbin needs theta (GLM.fit_nb estimates it without fixed effects)")
+            eng.set_theta(theta)
+        eng.set_data(self.X, self.y, self.m, self.offset, self.prior)
+        eng.set_clusters(self.codes, len(self.labels))
+        if self.codes2 is not None:
+            eng.set_fe2(self.codes2, len(self.labels2))
+        return eng
+
+
 class GLM:
     """Namespace mirroring `object GLM` (GLM.scala:55-1026)."""
 
@@ -447,9 +492,9 @@ class GLM:
         return obj
 
     @staticmethod
-    def _fe_data(y, x, fe, family, link, offset, m, prior, drop_uninformative, quiet=False):
+    def _fe_data(y, x, fe, family, link, offset, m, prior, drop_uninformative, quiet=False) -> FeData:
         """The arrays of a fixed-effects fit: the intercept removed, the labels coded, uninformative groups
-        dropped.  Returns (X, names, y, m, offset, prior, labels, codes, dropped groups, dropped rows)."""
+        dropped."""
         _check_inputs(y, x)
         _require(len(fe.columns) == 1, "The 'fe' DataFrame must have only one column")
         n = y.count()
@@ -467,71 +512,27 @@ class GLM:
         vec = lambda f: None if f is None else f.to_vector()
         yv, mv, ov, pv = y.to_vector(), vec(m), vec(offset), vec(prior)
         labels, codes = fe_codes(fe[fe.columns[0]])
+        d = FeData(fam, lnk, X, names, yv, mv, ov, pv, labels, codes)
         bad = fe_uninformative(codes, len(labels), yv, fam, mv, pv)
-        ngroups = nrows = 0
         if bad.any() and drop_uninformative:
-            keep = ~bad[codes]
-            ngroups, nrows = int(bad.sum()), int((~keep).sum())
-            if not quiet:
-                print(f"NOTE: {ngroups} fixed effect(s) ({nrows} rows) removed because of only 0"
-                      f"{' (or only m)' if fam == 'binomial' else ''} outcomes.")
-            X, yv = np.asfortranarray(X[keep]), yv[keep]
-            mv, ov, pv = (None if v is None else v[keep] for v in (mv, ov, pv))
-            labels, codes = fe_codes(labels[codes[keep]])
-        return fam, lnk, X, names, yv, mv, ov, pv, labels, codes, ngroups, nrows
+            d.drop(~bad[codes], int(bad.sum()), quiet)
+        return d
 
     @staticmethod
-    def _fe2_data(y, x, fe, fe2, family, link, offset, m, prior, drop_uninformative, quiet=False):
+    def _fe2_data(y, x, fe, fe2, family, link, offset, m, prior, drop_uninformative, quiet=False) -> FeData:
         """The arrays of a two-way fit: _fe_data's with the second factor coded too and the uninformative levels
-        of either factor dropped until none is left.  Returns _fe_data's tuple with (labels2, codes2) inserted
-        after codes, and the dropped levels counted over both factors."""
+        of either factor dropped until none is left."""
         _require(len(fe2.columns) == 1, "The 'fe2' DataFrame must have only one column")
         _require(fe2.count() == y.count(), "The two DataFrames must have the same number of rows")
-        fam, lnk, X, names, yv, mv, ov, pv, labels, codes, _, _ = GLM._fe_data(
-            y, x, fe, family, link, offset, m, prior, False, quiet=True)
-        labels2, codes2 = fe_codes(fe2[fe2.columns[0]])
-        nlev = nrows = 0
+        d = GLM._fe_data(y, x, fe, family, link, offset, m, prior, False, quiet=True)
+        d.labels2, d.codes2 = fe_codes(fe2[fe2.columns[0]])
         if drop_uninformative:
-            keep, _ = fe2_drop(codes, codes2, yv, fam, mv, pv)
+            keep, _ = fe2_drop(d.codes, d.codes2, d.y, d.fam, d.m, d.prior)
             if not keep.all():
-                nrows = int((~keep).sum())
-                nlev = (len(labels) - len(np.unique(codes[keep]))) + (len(labels2) - len(np.unique(codes2[keep])))
-                if not quiet:
-                    print(f"NOTE: {nlev} fixed effect(s) ({nrows} rows) removed because of only 0"
-                          f"{' (or only m)' if fam == 'binomial' else ''} outcomes.")
-                X, yv = np.asfortranarray(X[keep]), yv[keep]
-                mv, ov, pv = (None if v is None else v[keep] for v in (mv, ov, pv))
-                labels, codes = fe_codes(labels[codes[keep]])
-                labels2, codes2 = fe_codes(labels2[codes2[keep]])
-        return fam, lnk, X, names, yv, mv, ov, pv, labels, codes, labels2, codes2, nlev, nrows
-
-    @staticmethod
-    def _fit_fe2(y, x, fe, fe2, family, link, offset, m, prior, drop_uninformative, tol, verbose, theta, device,
-                 sweep_tol, max_sweeps):
-        fam, lnk, X, names, yv, mv, ov, pv, labels, codes, labels2, codes2, nlev, nrows = GLM._fe2_data(
-            y, x, fe, fe2, family, link, offset, m, prior, drop_uninformative)
-        eng = _engine(device)
-        if fam == "negbin":
-            _require(theta is not None, "family negbin needs theta (GLM.fit_nb estimates it without fixed effects)")
-            eng.set_theta(theta)
-        eng.set_data(X, yv, mv, ov, pv)
-        eng.set_clusters(codes, len(labels))
-        eng.set_fe2(codes2, len(labels2))
-        npart = x.rdd.partitions.size()
-        r = eng.fit_glm_fe2(fam, lnk, tol=tol, verbose=verbose, init="single" if npart == 1 else "multiple",
-                            npart=npart, sweep_tol=sweep_tol, max_sweeps=max_sweeps)
-        obj = GLM.createObj(x.select(*names), y, _to_pre(r.fit), "negbin" if fam == "negbin" else family, link)
-        neff = r.G_eff + r.H_eff - r.ncomp
-        obj.dfResidual, obj.dfNull = float(r.df_residual), float(r.fit.nrow - 1.0)
-        obj.pDispersion = obj.pearson / obj.dfResidual
-        obj.aic = -2.0 * obj.loglik + 2.0 * (len(names) + neff)
-        obj.theta = None if fam != "negbin" else float(theta)
-        item = lambda l: l.item() if hasattr(l, "item") else l
-        obj.fixef = {item(l): float(a) for l, a in zip(labels, r.alpha)}
-        obj.fixef2 = {item(l): float(a) for l, a in zip(labels2, r.gamma)}
-        obj.fe_dropped_groups, obj.fe_dropped_rows = nlev, nrows
-        obj.fe_ncomp, obj.fe_sweeps = r.ncomp, r.sweeps
-        return obj
+                left = len(np.unique(d.codes[keep])) + len(np.unique(d.codes2[keep]))
+                nlev = len(d.labels) + len(d.labels2) - left
+                d.drop(keep, nlev, quiet)
+        return d
 
     @staticmethod
     def fit_fe(y: Frame, x: Frame, fe: Frame, family: str = "poisson", link: str = "log", offset: Frame = None,
@@ -554,44 +555,51 @@ class GLM:
         none is left, the model carries `fixef` and `fixef2` (gamma is 0 at the lowest label of every connected
         component of the levels), dfResidual = n - p - (G_eff + H_eff - components), and `sweep_tol` /
         `max_sweeps` bound the alternating sweeps (0: 1e-12 and 10000).  One device, no communicator."""
-        if fe2 is not None:
-            return GLM._fit_fe2(y, x, fe, fe2, family, link, offset, m, prior, drop_uninformative, tol, verbose,
-                                theta, device, sweep_tol, max_sweeps)
-        fam, lnk, X, names, yv, mv, ov, pv, labels, codes, ngroups, nrows = GLM._fe_data(
-            y, x, fe, family, link, offset, m, prior, drop_uninformative)
-        eng = _engine(device)
-        if fam == "negbin":
-            _require(theta is not None, "family negbin needs theta (GLM.fit_nb estimates it without fixed effects)")
-            eng.set_theta(theta)
-        eng.set_data(X, yv, mv, ov, pv)
-        eng.set_clusters(codes, len(labels))
+        two = fe2 is not None
+        if two:
+            d = GLM._fe2_data(y, x, fe, fe2, family, link, offset, m, prior, drop_uninformative)
+        else:
+            d = GLM._fe_data(y, x, fe, family, link, offset, m, prior, drop_uninformative)
+        eng = d.load(theta, device)
         npart = x.rdd.partitions.size()
-        r = eng.fit_glm_fe(fam, lnk, tol=tol, verbose=verbose, init="single" if npart == 1 else "multiple",
-                           npart=npart)
-        obj = GLM.createObj(x.select(*names), y, _to_pre(r.fit), "negbin" if fam == "negbin" else family, link)
-        p = len(names)
+        kw = dict(tol=tol, verbose=verbose, init="single" if npart == 1 else "multiple", npart=npart)
+        r = eng.fit_glm_fe2(d.fam, d.lnk, sweep_tol=sweep_tol, max_sweeps=max_sweeps, **kw) if two else \
+            eng.fit_glm_fe(d.fam, d.lnk, **kw)
+        obj = GLM.createObj(x.select(*d.names), y, _to_pre(r.fit), "negbin" if d.fam == "negbin" else family, link)
+        neff = r.G_eff + r.H_eff - r.ncomp if two else r.G_eff
         obj.dfResidual, obj.dfNull = float(r.df_residual), float(r.fit.nrow - 1.0)
         obj.pDispersion = obj.pearson / obj.dfResidual
-        obj.aic = -2.0 * obj.loglik + 2.0 * (p + r.G_eff)  # createObj's rule with the effects counted
-        obj.theta = None if fam != "negbin" else float(theta)
-        obj.fixef = {(l.item() if hasattr(l, "item") else l): float(a) for l, a in zip(labels, r.alpha)}
-        obj.fe_dropped_groups, obj.fe_dropped_rows = ngroups, nrows
+        obj.aic = -2.0 * obj.loglik + 2.0 * (len(d.names) + neff)  # createObj's rule with the effects counted
+        obj.theta = None if d.fam != "negbin" else float(theta)
+        item = lambda l: l.item() if hasattr(l, "item") else l
+        obj.fixef = {item(l): float(a) for l, a in zip(d.labels, r.alpha)}
+        obj.fe_dropped_groups, obj.fe_dropped_rows = d.dropped, d.dropped_rows
+        if two:
+            obj.fixef2 = {item(l): float(a) for l, a in zip(d.labels2, r.gamma)}
+            obj.fe_ncomp, obj.fe_sweeps = r.ncomp, r.sweeps
         return obj
 
     @staticmethod
-    def _load_fe(obj: GLMModel, y, x, fe, offset, m, prior, device):
-        """The model's estimation data on the engine with its factor as clusters, and (beta, alpha)."""
-        _require(obj.fixef is not None, "fe belongs to a GLM.fit_fe model")
-        fam, lnk, X, names, yv, mv, ov, pv, labels, codes, _, _ = GLM._fe_data(
-            y, x.select(*obj.xnames), fe, obj.family, obj.link, offset, m, prior, True, quiet=True)
-        eng = _engine(device)
-        if fam == "negbin":
-            eng.set_theta(obj.theta)
-        eng.set_data(X, yv, mv, ov, pv)
-        eng.set_clusters(codes, len(labels))
-        _require(all(l in obj.fixef for l in labels.tolist()), "fe holds a label the model was not fitted with")
-        alpha = fe_offsets(obj.fixef, labels)
-        return eng, fam, lnk, np.asarray(obj.coefs, dtype=np.float64).reshape(-1), alpha
+    def _load_fe(obj: GLMModel, y, x, fe, offset, m, prior, device, fe2=None):
+        """The model's estimation data on the engine with its factor as clusters (a two-way model: both
+        factors), and (beta, alpha, gamma) -- gamma None without fe2."""
+        two = fe2 is not None
+        xs = x.select(*obj.xnames)
+        if two:
+            _require(obj.fixef is not None and obj.fixef2 is not None, "fe2 belongs to a GLM.fit_fe(fe2=) model")
+            d = GLM._fe2_data(y, xs, fe, fe2, obj.family, obj.link, offset, m, prior, True, quiet=True)
+        else:
+            _require(obj.fixef is not None, "fe belongs to a GLM.fit_fe model")
+            d = GLM._fe_data(y, xs, fe, obj.family, obj.link, offset, m, prior, True, quiet=True)
+        eng = d.load(obj.theta, device)
+        known = all(l in obj.fixef for l in d.labels.tolist())
+        if two:
+            _require(known and all(l in obj.fixef2 for l in d.labels2.tolist()),
+                     "fe / fe2 hold a label the model was not fitted with")
+        else:
+            _require(known, "fe holds a label the model was not fitted with")
+        return (eng, d.fam, d.lnk, np.asarray(obj.coefs, dtype=np.float64).reshape(-1), fe_offsets(obj.fixef, d.labels),
+                fe_offsets(obj.fixef2, d.labels2) if two else None)
 
     @staticmethod
     def _load(obj: GLMModel, y: Frame, x: Frame, offset, m, prior, device):
@@ -617,23 +625,6 @@ class GLM:
         return eng.vcov(beta, fam, lnk) if type == "const" else eng.vcov_robust(beta, fam, lnk, type=type)
 
     @staticmethod
-    def _load_fe2(obj: GLMModel, y, x, fe, fe2, offset, m, prior, device):
-        """The two-way model's estimation data on the engine with both factors, and (beta, alpha, gamma)."""
-        _require(obj.fixef is not None and obj.fixef2 is not None, "fe2 belongs to a GLM.fit_fe(fe2=) model")
-        fam, lnk, X, names, yv, mv, ov, pv, labels, codes, labels2, codes2, _, _ = GLM._fe2_data(
-            y, x.select(*obj.xnames), fe, fe2, obj.family, obj.link, offset, m, prior, True, quiet=True)
-        eng = _engine(device)
-        if fam == "negbin":
-            eng.set_theta(obj.theta)
-        eng.set_data(X, yv, mv, ov, pv)
-        eng.set_clusters(codes, len(labels))
-        eng.set_fe2(codes2, len(labels2))
-        _require(all(l in obj.fixef for l in labels.tolist()) and all(l in obj.fixef2 for l in labels2.tolist()),
-                 "fe / fe2 hold a label the model was not fitted with")
-        return (eng, fam, lnk, np.asarray(obj.coefs, dtype=np.float64).reshape(-1), fe_offsets(obj.fixef, labels),
-                fe_offsets(obj.fixef2, labels2))
-
-    @staticmethod
     def vcov_fe(obj: GLMModel, y: Frame, x: Frame, fe: Frame, offset: Frame = None, m: Frame = None,
                 prior: Frame = None, device: int = 0, type: str = "const", cadjust: bool = True,
                 fe2: Frame = None) -> np.ndarray:
@@ -646,10 +637,10 @@ class GLM:
             _check_cluster_type(type)
         if fe2 is not None or getattr(obj, "fixef2", None) is not None:  # two-way: clustered on fe (factor 1)
             _require(fe2 is not None, "a two-way fixed-effects model needs fe2 as well")
-            eng, fam, lnk, beta, alpha, gamma = GLM._load_fe2(obj, y, x, fe, fe2, offset, m, prior, device)
+            eng, fam, lnk, beta, alpha, gamma = GLM._load_fe(obj, y, x, fe, offset, m, prior, device, fe2)
             return eng.vcov_fe2(beta, alpha, gamma, fam, lnk, cluster=type != "const",
                                 type=type if type != "const" else "HC0", cadjust=cadjust)
-        eng, fam, lnk, beta, alpha = GLM._load_fe(obj, y, x, fe, offset, m, prior, device)
+        eng, fam, lnk, beta, alpha, _ = GLM._load_fe(obj, y, x, fe, offset, m, prior, device)
         return eng.vcov_fe(beta, alpha, fam, lnk, cluster=type != "const", type=type if type != "const" else "HC0",
                            cadjust=cadjust)
 

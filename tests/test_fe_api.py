@@ -63,19 +63,19 @@ def test_fe_data_codes_labels_drops_the_intercept_and_uninformative_groups(capsy
     prior = np.ones(len(y))
     out = GLM._fe_data(Frame({"y": y}), x, Frame({"firm": firm}), "poisson", "log", None, None,
                        Frame({"w": prior}), True)
-    fam, lnk, X, names, yv, mv, ov, pv, labels, codes, ngroups, nrows = out
-    assert (fam, lnk) == ("poisson", "log") and names == ["a", "b"] and X.shape == (48, 2)
+    labels, codes, ngroups, nrows = out.labels, out.codes, out.dropped, out.dropped_rows
+    assert (out.fam, out.lnk) == ("poisson", "log") and out.names == ["a", "b"] and out.X.shape == (48, 2)
     assert list(labels) == ["firm0", "firm1", "firm2", "firm4"] and ngroups == 1 and nrows == 12
-    assert codes.min() == 0 and codes.max() == 3 and len(codes) == 48 and len(yv) == 48 and len(pv) == 48
+    assert codes.min() == 0 and codes.max() == 3 and len(codes) == 48 and len(out.y) == 48 and len(out.prior) == 48
     assert np.array_equal(labels[codes], firm[firm != "firm3"])
     assert "1 fixed effect(s) (12 rows) removed" in capsys.readouterr().out
     # kept when asked: the engine then refuses the fit
     out = GLM._fe_data(Frame({"y": y}), x, Frame({"firm": firm}), "poisson", "log", None, None, None, False)
-    assert out[2].shape == (60, 2) and len(out[8]) == 5 and out[10] == 0
+    assert out.X.shape == (60, 2) and len(out.labels) == 5 and out.dropped == 0
     # integer labels, gaussian: nothing is uninformative
     out = GLM._fe_data(Frame({"y": y}), x, Frame({"id": np.arange(60) % 4 + 10}), "gaussian", "identity", None, None,
                        None, True)
-    assert list(out[8]) == [10, 11, 12, 13] and out[10] == 0
+    assert list(out.labels) == [10, 11, 12, 13] and out.dropped == 0
 
 
 def test_model_layer_refusals_without_a_device():

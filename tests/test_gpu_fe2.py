@@ -137,6 +137,50 @@ def test_a_level_of_several_chunks_and_two_combine_levels(eng):
                c["gamma"] * 0.5)
 
 
+def test_init_multiple_with_zero_weight_rows_and_a_partial_tile(eng):
+    """The initial pass in mode "multiple" (beta = alpha = gamma = None) on binomial counts with m: t2 and W2 are
+    sums over factor 2's lists of the per-row w z and w that the weights kernel stores -- several tiles, a last
+    partial one, and rows of prior weight 0, which must store exact zeros."""
+    n, p = sweep_n(5), 5
+    c, ids1, G, ids2, H, kw = case("binomial", "logit", n, p, "random", "sorted", zero_weights=True)
+    assert n > 2 * T and n % T != 0 and np.any(kw["pw"] == 0.0) and kw["m"] is not None
+    load(eng, c, ids1, G, ids2, H, kw)
+    check_pass(f"fe2_pass init multiple binomial {n}x{p}", eng, c, ids1, G, ids2, H, kw, "binomial", "logit",
+               None, None, None, mode=2)
+
+
+def test_uninformative_levels_of_factor_2_from_the_stored_row_values(eng):
+    """The check's sums over factor 2 come from the y and 1 the weights kernel stores per row: one level with
+    y = 0 on every row of positive weight, one whose only y > 0 sit on rows of prior weight 0; no level of
+    factor 1 is uninformative, so the refusal is factor 2's, with numpy's count and first level."""
+    n, p = sweep_n(5), 5
+    c, ids1, G, ids2, H, kw = case("poisson", "log", n, p, "random", "sorted", zero_weights=True)
+    pw, y = kw["pw"], c["y"].copy()
+    y[ids2 == 2] = 0.0
+    y[(ids2 == 6) & (pw > 0.0)] = 0.0
+    y[(ids2 == 6) & (pw == 0.0)] = 3.0
+    assert np.any((ids2 == 6) & (pw == 0.0))
+
+    def uninformative(ids, L):
+        a, b = np.zeros(L), np.zeros(L)
+        np.add.at(a, ids[pw > 0.0], y[pw > 0.0])
+        np.add.at(b, ids[pw > 0.0], 1.0)
+        return np.flatnonzero((a == 0.0) != (b == 0.0))
+
+    assert len(uninformative(ids1, G)) == 0
+    bad = uninformative(ids2, H)
+    assert list(bad) == [2, 6]
+    eng.set_data(c["X"], y, offset=kw["off"], prior=pw)
+    eng.set_clusters(ids1, G)
+    eng.set_fe2(ids2, H)
+    eng.reset_stats()
+    with pytest.raises(L.IllegalArgumentException,
+                       match=rf"{len(bad)} level\(s\) of factor 2 have no finite fixed effect.*"
+                             rf"first is level {bad[0]} of factor 2"):
+        eng.fit_glm_fe2("poisson", "log")
+    assert eng.stats()["passes"] == 0
+
+
 def check_fe2_fit(label, e, c, ids1, G, ids2, H, kw, fam, lnk, tol=1e-6):
     p = c["X"].shape[1]
     n = len(c["y"])

@@ -1,4 +1,4 @@
-"""Per-kernel gfx950 disassembly of the built device objects (build/obj/{kernels,fused_odd,narrow,wide,influence,theta}.o;
+"""Per-kernel gfx950 disassembly of the built device objects (build/obj/<name>.o for every name in OBJECTS;
 ISA_OBJDIR selects a variant build's objects).
 
     python tools/isa_dump.py OUTDIR            # one OUTDIR/<kernel>.s per kernel symbol
@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-OBJECTS = ("kernels", "fused_odd", "narrow", "wide", "influence", "theta")
+OBJECTS = ("kernels", "fused_odd", "narrow", "wide", "influence", "theta", "cluster", "fe_hip", "fe2_hip")
 
 
 def _code_objects(run):
@@ -51,7 +51,8 @@ def regs(flt: str = "") -> int:
             sym = get("name")
             filt = shutil.which("c++filt")  # mangled names where no demangler is installed
             dem = subprocess.run([filt, sym], capture_output=True, text=True).stdout.strip() if filt else sym
-            dem = re.sub(r"^void sglm::(\(anonymous namespace\)::)?", "", dem).split("(")[0]
+            # (only a template's name carries its return type)
+            dem = re.sub(r"^(void )?sglm::(\(anonymous namespace\)::)?", "", dem).split("(")[0]
             rows.append((dem, get("vgpr_count"), blk.split()[0], get("sgpr_count"), get("private_segment_fixed_size"),
                          get("group_segment_fixed_size")))
 
