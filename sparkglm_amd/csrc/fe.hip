@@ -36,28 +36,15 @@ constexpr int FE_SUB = 8;  // rows per piece of the tile's segment sums
 static_assert(FE_NT % 64 == 0 && FE_NT % FE_SUB == 0, "whole waves, whole pieces");
 static_assert(FE_NT % RB == 0, "the tiles of n rows cover the ld = n rounded up to RB rows of the per-row outputs");
 
-// w and w z of one row in the reference operation order (pass_row_ref / pass_row_ref_x / pass_row_ref_nb
-// without their unit deviance, which the pass itself sums): from the same primitives, as influence_row.
+// w and w z of one row in the reference operation order: the pass's reference rows (rowmath.hpp row_core, the
+// links and the variance selected at run time) without their unit deviance, which the pass itself sums.
 struct FeWZ {
   double w, wz;
 };
 __device__ __noinline__ FeWZ fe_row(int fam, int lnk, int mode, double eta, double y, double m, double off, double pw,
                                     double mu0, double theta) {
-  const bool x = noncanonical_pair(fam, lnk);  // the links selected by link (every negative binomial pair)
-  double mu;
-  if (mode == MODE_IRLS) {
-    mu = x ? unlink_fn_x(lnk, eta) : unlink_fn(fam, lnk, eta, m);
-  } else {
-    eta = x ? link_fn_x(lnk, mu0) : link_fn(fam, lnk, mu0, m);  // offset ignored at init
-    mu = mode == MODE_INIT_SINGLE ? mu0 : (x ? unlink_fn_x(lnk, eta) : unlink_fn(fam, lnk, eta, m));
-  }
-  const double g = x ? lprime_fn_x(lnk, mu) : lprime_fn(fam, lnk, mu, m);
-  const double v = fam == FAM_NEGBIN ? nb_variance(mu, theta) : variance_fn(fam, mu, m);
-  FeWZ r;
-  r.w = pw * (1.0 / (v * (g * g)));
-  const double z = (eta + ((y + (-1.0 * mu)) * g)) + (-1.0 * off);
-  r.wz = r.w * z;
-  return r;
+  const RowCore c = row_core(noncanonical_pair(fam, lnk), fam == FAM_NEGBIN, fam, lnk, mode, eta, m, pw, mu0, theta);
+  return FeWZ{c.w, working_wz(c.w, c.eta, y, c.mu, c.g, off)};
 }
 
 __global__ void __launch_bounds__(FE_NT) fe_weights_kernel(FeArgs a) {

@@ -12,6 +12,7 @@
 #include "kernels.hpp"
 #include "procx.hpp"
 #include "rowmath.hpp"
+#include "waitcnt.hpp"
 
 namespace sglm {
 
@@ -195,13 +196,6 @@ struct TilesK1<P16, WV, false> {
   static constexpr int NT = LO + HI + 2;
   static constexpr int seg_of(int k) { return k <= LO ? 0 : 1; }
 };
-
-// s_waitcnt vmcnt(N) with expcnt / lgkmcnt left open (gfx9 encoding).
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
 
 // Workgroup barrier that orders LDS traffic but leaves LDS-DMA loads in flight.
 __device__ __forceinline__ void lds_barrier() {
@@ -424,7 +418,7 @@ __device__ __forceinline__ void pass_body(double* lds, const PassArgs& a, int wv
         // MFMA-only wave: after KA k-steps, publish that its part of block blk+1 has landed
         if (has_gram) gram_steps<P16, WV, KA>(lds, cur & 1, cur & 1, lane, 0, acc, xz);
         if (has_next) {
-          wait_vmcnt<0>();
+          wait_vm<0>();
           if (lane == 0) __hip_atomic_fetch_add(flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         if (has_gram) gram_steps<P16, WV, RB / 4 - KA>(lds, cur & 1, cur & 1, lane, KA, acc, xz);
@@ -443,8 +437,8 @@ __device__ __forceinline__ void pass_body(double* lds, const PassArgs& a, int wv
       // single wave: it stages, waits and computes everything itself
       if (has_gram) gram_steps<P16, WV, K1>(lds, cur & 1, cur & 1, lane, 0, acc, xz);
       if (has_next) {
-        if (blk + 1 == b0 && b0 + 1 < b1) wait_vmcnt<G::QMAX + G::VMAX>();
-        else wait_vmcnt<0>();
+        if (blk + 1 == b0 && b0 + 1 < b1) wait_vm<G::QMAX + G::VMAX>();
+        else wait_vm<0>();
         row_stage<P16, FAM, LNK>(lds, cur ^ 1, cur ^ 1, a, blk + 1, wv, lane, s_dev, s_aux);
       }
       if (has_gram) gram_steps<P16, WV, RB / 4 - K1>(lds, cur & 1, cur & 1, lane, K1, acc, xz);
@@ -959,11 +953,11 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
   // wait until this wave's DMA of a block has landed while `later` blocks staged after it may fly
   auto wait_landed = [&](int64_t later) {
     if constexpr (NB >= 4)
-      if (later >= 3) return wait_vmcnt<3 * PER>();
+      if (later >= 3) return wait_vm<3 * PER>();
     if constexpr (NB >= 3)
-      if (later >= 2) return wait_vmcnt<2 * PER>();
-    if (later >= 1) return wait_vmcnt<PER>();
-    wait_vmcnt<0>();
+      if (later >= 2) return wait_vm<2 * PER>();
+    if (later >= 1) return wait_vm<PER>();
+    wait_vm<0>();
   };
   // No block barrier: LDS counters order the ring of NBUF buffers.
   //   flag      : +1 per row wave when its LDS-DMA part of a block has landed (4 per block); every row
@@ -1068,7 +1062,7 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
     }
   } else {
     if constexpr (GDMA && issuer) {  // the prologue's blocks
-      wait_vmcnt<0>();
+      wait_vm<0>();
 #pragma unroll
       for (int k = 0; k < NB; ++k)
         if (b0 + k < b1) bump(landed(k));
@@ -1092,7 +1086,7 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
           st.lap(8);
           stage(cur, blk + NB);
           st.lap(9);
-          wait_vmcnt<0>();
+          wait_vm<0>();
           bump(landed(cur));
           st.lap(10);
         }

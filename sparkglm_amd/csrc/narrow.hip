@@ -34,6 +34,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "rowmath.hpp"
+#include "waitcnt.hpp"
 
 namespace sglm {
 
@@ -115,12 +116,6 @@ static_assert(VmCount<4>::younger(1, 1) == 4 * 16 / 8 + 2 && VmCount<1>::younger
 
 template <int NRB>
 __device__ __forceinline__ constexpr int swz(int c) { return NRB == 16 ? 2 * ((c >> 1) & 7) : 2 * (c & 15); }
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
 
 __device__ __forceinline__ double xor16_sum(double v) {
   const auto a = __builtin_amdgcn_permlane16_swap(__double2loint(v), __double2loint(v), false, false);

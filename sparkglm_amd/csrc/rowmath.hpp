@@ -134,8 +134,7 @@ __device__ __forceinline__ double lprime_fn(int fam, int lnk, double mu, double 
 
 // The extension families' links by the link alone (R's make.link: identity, log, inverse, sqrt) -- the
 // non-canonical pairs (common.hpp noncanonical_pair).  link_fn / unlink_fn / lprime_fn above select by
-// family and serve the binomial links and the canonical pairs only; they and the functions built on them
-// stay as they are, so that the canonical instantiations' code does not move.
+// family and serve the binomial links and the canonical pairs only.
 __device__ __forceinline__ double link_fn_x(int lnk, double mu) {
   if (lnk == LNK_IDENTITY) return mu;
   if (lnk == LNK_LOG) return log(mu);
@@ -221,59 +220,9 @@ __device__ __forceinline__ double unit_dev(int fam, double y, double mu, double 
   return pw * (-(log(y / mu) - (y - mu) / mu));
 }
 
-// The reference operation order (zwCreateBinomial GLM.scala:359-395, devBinomial :162-170)
-// for every row the fast paths below do not take: init modes, m != 1, probit / cloglog, and
-// rows outside the fast paths' ranges.  Out of line: its libm calls' constants would otherwise
-// be hoisted into the pass kernels' main loops and take registers from the Gram accumulators.
-struct RowWZ {
-  double w, wz, dev;
-};
-__device__ __noinline__ RowWZ pass_row_ref(int fam, int lnk, int mode, double eta, double y, double m, double off,
-                                           double pw, double mu0) {
-  double mu;
-  if (mode == MODE_IRLS) {
-    mu = unlink_fn(fam, lnk, eta, m);
-  } else {
-    eta = link_fn(fam, lnk, mu0, m);  // offset ignored at init (GLM.scala:264-270)
-    mu = (mode == MODE_INIT_SINGLE) ? mu0 : unlink_fn(fam, lnk, eta, m);
-  }
-  const double g = lprime_fn(fam, lnk, mu, m);
-  const double v = variance_fn(fam, mu, m);
-  RowWZ r;
-  r.w = pw * (1.0 / (v * (g * g)));
-  const double z = (eta + ((y + (-1.0 * mu)) * g)) + (-1.0 * off);
-  r.wz = r.w * z;
-  // fitMultipleBinomial re-derives mu = unlink(link(ybar)) only inside zwCreateBinomial; its
-  // null deviance is taken at mu0 = ybar itself (GLM.scala:424-444)
-  r.dev = unit_dev(fam, y, mode == MODE_IRLS ? mu : mu0, m, pw);
-  return r;
-}
-// pass_row_ref for the non-canonical pairs: the same operation order with the links selected by link,
-// and the validity of the row (link_row_valid) carried as a NaN unit deviance.  An invalid row yields
-// NaN / Inf arithmetic only -- no index depends on mu.
-__device__ __noinline__ RowWZ pass_row_ref_x(int fam, int lnk, int mode, double eta, double y, double m, double off,
-                                             double pw, double mu0) {
-  double mu;
-  if (mode == MODE_IRLS) {
-    mu = unlink_fn_x(lnk, eta);
-  } else {
-    eta = link_fn_x(lnk, mu0);
-    mu = (mode == MODE_INIT_SINGLE) ? mu0 : unlink_fn_x(lnk, eta);
-  }
-  const double g = lprime_fn_x(lnk, mu);
-  const double v = variance_fn(fam, mu, m);
-  RowWZ r;
-  r.w = pw * (1.0 / (v * (g * g)));
-  const double z = (eta + ((y + (-1.0 * mu)) * g)) + (-1.0 * off);
-  r.wz = r.w * z;
-  r.dev = link_row_valid(fam, lnk, eta, mu) ? unit_dev(fam, y, mode == MODE_IRLS ? mu : mu0, m, pw) : NAN;
-  return r;
-}
-
 // ---- negative binomial with a fixed theta (MASS::negative.binomial(theta)) ----
 // V = mu + mu^2 / theta; unit deviance y log(max(y, 1) / mu) - (y + theta) log((y + theta) / (mu + theta)) (family
-// factor 2); the log-density of R's dnbinom(y, theta, mu = mu).  New functions beside the four families': those
-// (variance_fn, unit_dev, pass_row_ref_x ...) stay as they are, so that their instantiations' code does not move.
+// factor 2); the log-density of R's dnbinom(y, theta, mu = mu).
 __device__ __forceinline__ double nb_variance(double mu, double theta) { return mu + (mu * mu) / theta; }
 __device__ __forceinline__ double nb_unit_dev(double y, double mu, double pw, double theta) {
   return pw * ((y * log(fmax(y, 1.0) / mu)) - ((y + theta) * log((y + theta) / (mu + theta))));
@@ -282,24 +231,76 @@ __device__ __forceinline__ double nb_loglik_row(double y, double mu, double thet
   return ((((lgamma(theta + y) - lgamma(theta)) - lgamma(y + 1.0)) + theta * log(theta)) +
           y * log(mu + (y == 0.0 ? 1.0 : 0.0))) - (theta + y) * log(theta + mu);
 }
-// pass_row_ref_x's operation order with the negative binomial variance and deviance; the row's validity is the
-// poisson rows' rule (link_row_valid: mu finite and > 0, sqrt needs eta > 0), carried as a NaN unit deviance.
-__device__ __noinline__ RowWZ pass_row_ref_nb(int lnk, int mode, double eta, double y, double off, double pw,
-                                              double mu0, double theta) {
+
+// The reference operation order (zwCreateBinomial GLM.scala:359-395) of every row the fast paths below do
+// not take -- init modes, m != 1, probit / cloglog, the non-canonical pairs, the negative binomial, rows
+// outside the fast paths' ranges.  row_core is its one spelling in the pass: mu from eta (IRLS) or from mu0
+// (the init modes: eta = link(mu0), the offset ignored, GLM.scala:264-270), g', V and the working weight.
+// by_link (link_by_link: the links selected by link) and nb (the negative binomial variance at theta) are
+// compile-time constants (CT<>) in the pass's rows, whose instantiations then hold one set of links each, and
+// run-time bools in the diagnostics and fixed-effects rows (influence_row, fe.hip fe_row), which serve every
+// (family, link) from one function.
+template <bool V>
+struct CT {
+  constexpr operator bool() const { return V; }
+};
+struct RowCore {
+  double eta, mu, g, v, w;
+};
+template <class BYLINK, class NB>
+__device__ __forceinline__ RowCore row_core(BYLINK by_link, NB nb, int fam, int lnk, int mode, double eta, double m,
+                                            double pw, double mu0, double theta) {
   double mu;
   if (mode == MODE_IRLS) {
-    mu = unlink_fn_x(lnk, eta);
+    mu = by_link ? unlink_fn_x(lnk, eta) : unlink_fn(fam, lnk, eta, m);
   } else {
-    eta = link_fn_x(lnk, mu0);
-    mu = (mode == MODE_INIT_SINGLE) ? mu0 : unlink_fn_x(lnk, eta);
+    eta = by_link ? link_fn_x(lnk, mu0) : link_fn(fam, lnk, mu0, m);
+    mu = (mode == MODE_INIT_SINGLE) ? mu0 : (by_link ? unlink_fn_x(lnk, eta) : unlink_fn(fam, lnk, eta, m));
   }
-  const double g = lprime_fn_x(lnk, mu);
-  const double v = nb_variance(mu, theta);
-  RowWZ r;
-  r.w = pw * (1.0 / (v * (g * g)));
+  const double g = by_link ? lprime_fn_x(lnk, mu) : lprime_fn(fam, lnk, mu, m);
+  const double v = nb ? nb_variance(mu, theta) : variance_fn(fam, mu, m);
+  return RowCore{eta, mu, g, v, pw * (1.0 / (v * (g * g)))};
+}
+// w z, z = eta + (y - mu) g' - offset (GLM.scala:289-290, 370-371)
+__device__ __forceinline__ double working_wz(double w, double eta, double y, double mu, double g, double off) {
   const double z = (eta + ((y + (-1.0 * mu)) * g)) + (-1.0 * off);
-  r.wz = r.w * z;
-  r.dev = link_row_valid(FAM_NEGBIN, lnk, eta, mu) ? nb_unit_dev(y, mode == MODE_IRLS ? mu : mu0, pw, theta) : NAN;
+  return w * z;
+}
+
+// The pass's reference rows: the core plus the unit deviance (devBinomial :162-170).  Out of line: their libm
+// calls' constants would otherwise be hoisted into the pass kernels' main loops and take registers from the
+// Gram accumulators.
+struct RowWZ {
+  double w, wz, dev;
+};
+__device__ __forceinline__ RowWZ row_wz(const RowCore& c, double y, double off) {
+  return RowWZ{c.w, working_wz(c.w, c.eta, y, c.mu, c.g, off), 0.0};
+}
+// fitMultipleBinomial re-derives mu = unlink(link(ybar)) only inside zwCreateBinomial; its null deviance is
+// taken at mu0 = ybar itself (GLM.scala:424-444)
+__device__ __noinline__ RowWZ pass_row_ref(int fam, int lnk, int mode, double eta, double y, double m, double off,
+                                           double pw, double mu0) {
+  const RowCore c = row_core(CT<false>{}, CT<false>{}, fam, lnk, mode, eta, m, pw, mu0, 0.0);
+  RowWZ r = row_wz(c, y, off);
+  r.dev = unit_dev(fam, y, mode == MODE_IRLS ? c.mu : mu0, m, pw);
+  return r;
+}
+// The non-canonical pairs: the validity of the row (link_row_valid) is carried as a NaN unit deviance.  An
+// invalid row yields NaN / Inf arithmetic only -- no index depends on mu.
+__device__ __noinline__ RowWZ pass_row_ref_x(int fam, int lnk, int mode, double eta, double y, double m, double off,
+                                             double pw, double mu0) {
+  const RowCore c = row_core(CT<true>{}, CT<false>{}, fam, lnk, mode, eta, m, pw, mu0, 0.0);
+  RowWZ r = row_wz(c, y, off);
+  r.dev = link_row_valid(fam, lnk, c.eta, c.mu) ? unit_dev(fam, y, mode == MODE_IRLS ? c.mu : mu0, m, pw) : NAN;
+  return r;
+}
+// The negative binomial: its variance and deviance; the row's validity is the poisson rows' rule
+// (link_row_valid: mu finite and > 0, sqrt needs eta > 0).
+__device__ __noinline__ RowWZ pass_row_ref_nb(int lnk, int mode, double eta, double y, double off, double pw,
+                                              double mu0, double theta) {
+  const RowCore c = row_core(CT<true>{}, CT<true>{}, FAM_NEGBIN, lnk, mode, eta, 1.0, pw, mu0, theta);
+  RowWZ r = row_wz(c, y, off);
+  r.dev = link_row_valid(FAM_NEGBIN, lnk, c.eta, c.mu) ? nb_unit_dev(y, mode == MODE_IRLS ? c.mu : mu0, pw, theta) : NAN;
   return r;
 }
 
@@ -340,6 +341,111 @@ __device__ __forceinline__ void pass_row_init(const double* c, double y, double 
   s_aux += pw;
 }
 
+// ---- the inline fast paths: one function per (family, link), shared by the pass (pass_row), the pass
+// with in-pass final statistics (pass_row_stats, STATS) and stats_kernel (stats_row) ----
+// Each sums w, w z, the unit deviance and sum pw; with STATS also pearsonCalc and the family's loglik
+// ingredients at the same mu, from the same exp / reciprocal / log.  Its SGLM_*_FAST condition is the range
+// its forms hold in; other rows take the reference order.  (Macros: the conditions then join the callers'
+// short-circuit chains as if spelled there -- as functions they compiled to other branch structures in
+// the pass kernels.)
+
+// Logit, m = 1: the reference's expressions (GLM.scala:190-204, 125-129, 162-170, 289-290)
+// in an algebraically identical form with one exp, one division and one log1p:
+//   t = 1/(1+e), e = exp(-eta):  mu = t,  V = e t^2,  g' = 1/V,  w = V,  w*z = V (eta - off) + (y - mu)
+//   dev row = y log(1/mu) + (1-y) log(1/(1-mu)) = log1p(e) + (1-y) eta
+// Inside |eta| < 8 both forms agree to ~1e-13 relative per row (1 - mu >= 3e-4, no
+// cancellation); outside it, and for m != 1, the reference operation order applies.
+// u = 1 + e lies in (1, 2982): t = 1/u by rcp_pos, and log1p(e) = log(u) + (e - (u - 1))/u
+// (the rounding of u corrected to first order, as libm's log1p does).
+// STATS: Breeze's Binomial(1, mu).logProbabilityOf(k) = k log mu + (1-k) log(1-mu) with log mu = -log1p(e),
+// log(1-mu) = -eta - log1p(e); |eta| < 8 keeps mu off 0 and 1 (no special cases, k in {0, 1}).
+#define SGLM_LOGIT_FAST(eta, y) (fabs(eta) < 8.0 && (y) >= 0.0 && (y) <= 1.0)
+template <bool STATS>
+__device__ __forceinline__ void logit_row(double eta, double y, double off, double pw, bool small_exp, double& w,
+                                          double& wz, double& s_dev, double& s_aux, double& s_pear, double& s_ll) {
+  const double e = small_exp ? exp_small(-eta) : exp(-eta);
+  const double u = 1.0 + e;
+  const double t = rcp_pos(u);
+  const double v = e * t * t;
+  w = pw * v;
+  wz = pw * (v * (eta - off) + (y - t));
+  const double L = fma(e - (u - 1.0), t, log_pos(u));  // log1p(e) = -log(mu)
+  s_dev += pw * (L + (1.0 - y) * eta);
+  s_aux += pw;
+  if constexpr (STATS) {
+    const double r = y - t;
+    s_pear += pw * (r * r) * rcp_pos(v);
+    s_ll += pw * ((int)y == 1 ? -L : -L - eta);
+  }
+}
+
+// y log y - y eta of a count row (Poisson, negative binomial): y log y from the narrow kernel's LDS table of
+// k log k for the integer counts k < POIS_TAB (poisson_ylogy_table), so that those rows need no log; other
+// rows (no table, non-integer or large y) take log_pos.
+__device__ __forceinline__ double ylogy_minus_yeta(const double* ylogy, double y, double eta) {
+  if (ylogy && y < (double)POIS_TAB && y == floor(y)) return ylogy[(int)y] - y * eta;
+  return y > 0.0 ? y * (log_pos(y) - eta) : 0.0;
+}
+
+// Poisson / log (R's poisson()): mu = exp(eta), g' = 1/mu, V = mu, so
+//   w = 1/(V g'^2) = mu,  w*z = mu (eta - off) + (y - mu),
+//   dev row = y log(y/mu) - (y - mu) = (y log y - y eta) - (y - mu)
+// -- one exp and one log (or a table look-up), no divisions; the reference operation order
+// agrees to a few ulp per row, and it still runs where exp could overflow.  The deviance stays
+// a per-row sum of terms of the size of the row's own deviance -- what GLM.scala:452's absolute tol
+// on the change needs (a round-3 form summed -y eta - (y - mu) per row and added sum y log y once
+// per pass: with counts ~1e3 over 1e8 rows its terms reached ~1e12 in total and their rounding,
+// ~1e-4, swamped tol 1e-6).
+// STATS: pearsonCalc (R's variance V = mu) and the mu-dependent part of R's dpois
+// log-density, y log mu - mu with log mu = eta.  The per-row constant -lgamma(y + 1) does not depend on the
+// fit: the initial pass sums pw lgamma(y + 1) once into S_AUX2 (init_stats_const) and the engine subtracts it.
+#define SGLM_POISSON_LOG_FAST(eta, y) (fabs(eta) < 700.0 && (y) >= 0.0 && (y) < 1e300)
+template <bool STATS>
+__device__ __forceinline__ void poisson_log_row(double eta, double y, double off, double pw, bool small_exp,
+                                                const double* ylogy, double& w, double& wz, double& s_dev,
+                                                double& s_aux, double& s_pear, double& s_ll) {
+  const double mu = small_exp ? exp_small(eta) : exp(eta);
+  w = pw * mu;
+  wz = pw * (mu * (eta - off) + (y - mu));
+  s_dev += pw * (ylogy_minus_yeta(ylogy, y, eta) - (y - mu));
+  s_aux += pw;
+  if constexpr (STATS) {
+    const double r = y - mu;
+    s_pear += pw * (r * r) * rcp_pos(mu);
+    s_ll += pw * (y * eta - mu);
+  }
+}
+
+// Gamma / inverse (R's Gamma()): mu = 1/eta, g' = -1/mu^2, V = mu^2, so
+//   w = mu^2,  w*z = mu^2 (eta - off) - (y - mu),
+//   dev row = -(log(y/mu) - (y - mu)/mu) = -(log(y eta) - (y eta - 1))
+// -- one reciprocal and one log instead of four divisions and a log (the range checks keep
+// eta, y and y eta normal and finite for rcp_pos / log_pos).
+// STATS: pearsonCalc (V = mu^2: (y - mu)^2 / mu^2 = (y - mu)^2 eta^2) and R's Gamma loglik ingredients
+// sum pw y / mu = sum pw y eta (s_aux0) and sum pw log mu = sum pw log y - sum pw log(y eta) (the pass sums
+// the second term, s_lye, which its deviance already evaluates; the fit-constant sum pw log y -- also S_LL
+// itself -- comes from the initial pass, init_stats_const).
+#define SGLM_GAMMA_INVERSE_FAST(eta, y) ((eta) > 1e-150 && (eta) < 1e150 && (y) > 1e-150 && (y) < 1e150)
+template <bool STATS>
+__device__ __forceinline__ void gamma_inverse_row(double eta, double y, double off, double pw, double& w, double& wz,
+                                                  double& s_dev, double& s_aux, double& s_pear, double& s_aux0,
+                                                  double& s_lye) {
+  const double mu = rcp_pos(eta);
+  const double mu2 = mu * mu;
+  const double ye = y * eta;
+  w = pw * mu2;
+  wz = pw * (mu2 * (eta - off) - (y - mu));
+  const double L = log_pos(ye);
+  s_dev += pw * (-(L - (ye - 1.0)));
+  s_aux += pw;
+  if constexpr (STATS) {
+    const double r = y - mu;
+    s_pear += pw * (r * r) * (eta * eta);
+    s_aux0 += pw * ye;
+    s_lye += pw * L;
+  }
+}
+
 // The row stage of the fused pass (zwCreateBinomial, GLM.scala:359-395 / the single-
 // partition loop body GLM.scala:282-301): w and w*z for the Gramian, and the deviance.
 // LM gram mode: w = 1, z = y, and the sums of y and of rows (LM.scala:142-155, 167).
@@ -348,69 +454,24 @@ __device__ __forceinline__ void pass_row_init(const double* c, double y, double 
 // measured it -1 % at p <= 32 and +4 % at p = 64 on that round's narrow kernel; round 5's rework of
 // the narrow pass (row stage at raised issue priority, block pairs at p > 32) set it for every width
 // without a separate p = 64 A/B of this choice.  The fused / wide kernels leave it off (neutral).
-// ylogy (the narrow kernel's Poisson IRLS passes): an LDS table of k log k for the integer counts
-// k < POIS_TAB (poisson_ylogy_table), so that those rows need no log: the Poisson unit deviance
-// y log(y / mu) - (y - mu) = (y log y - y eta) - (y - mu) with y log y looked up.  The deviance stays
-// a per-row sum of terms of the size of the row's own deviance -- what GLM.scala:452's absolute tol
-// on the change needs (a round-3 form summed -y eta - (y - mu) per row and added sum y log y once
-// per pass: with counts ~1e3 over 1e8 rows its terms reached ~1e12 in total and their rounding,
-// ~1e-4, swamped tol 1e-6).  Other rows (non-integer or large y) take log_pos.
+// ylogy: the narrow kernel's IRLS passes' table of the counts' y log y (ylogy_minus_yeta).
 __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta, double y, double m, double off,
                                          double pw, double mu0, double ybar, bool has_m, double& w, double& wz,
                                          double& s_dev, double& s_aux, bool small_exp = false,
                                          bool init_fast = false, const double* ylogy = nullptr, int rt_link = 0,
                                          double theta = 0.0) {
   (void)ybar;
-  if (fam == FAM_BINOMIAL && lnk == LNK_LOGIT && mode == MODE_IRLS && !has_m && fabs(eta) < 8.0 && y >= 0.0 &&
-      y <= 1.0) {
-    // Logit, m = 1: the reference's expressions (GLM.scala:190-204, 125-129, 162-170, 289-290)
-    // in an algebraically identical form with one exp, one division and one log1p:
-    //   t = 1/(1+e), e = exp(-eta):  mu = t,  V = e t^2,  g' = 1/V,  w = V,  w*z = V (eta - off) + (y - mu)
-    //   dev row = y log(1/mu) + (1-y) log(1/(1-mu)) = log1p(e) + (1-y) eta
-    // Inside |eta| < 8 both forms agree to ~1e-13 relative per row (1 - mu >= 3e-4, no
-    // cancellation); outside it, and for m != 1, the reference operation order below applies.
-    // u = 1 + e lies in (1, 2982): t = 1/u by rcp_pos, and log1p(e) = log(u) + (e - (u - 1))/u
-    // (the rounding of u corrected to first order, as libm's log1p does).
-    const double e = small_exp ? exp_small(-eta) : exp(-eta);
-    const double u = 1.0 + e;
-    const double t = rcp_pos(u);
-    const double v = e * t * t;
-    w = pw * v;
-    wz = pw * (v * (eta - off) + (y - t));
-    s_dev += pw * (fma(e - (u - 1.0), t, log_pos(u)) + (1.0 - y) * eta);
-    s_aux += pw;
+  double nil;  // the statistics sums of the fast paths: not formed here (STATS = false)
+  if (fam == FAM_BINOMIAL && lnk == LNK_LOGIT && mode == MODE_IRLS && !has_m && SGLM_LOGIT_FAST(eta, y)) {
+    logit_row<false>(eta, y, off, pw, small_exp, w, wz, s_dev, s_aux, nil, nil);
     return;
   }
-  if (fam == FAM_POISSON && lnk == LNK_LOG && mode == MODE_IRLS && fabs(eta) < 700.0 && y >= 0.0 && y < 1e300) {
-    // Poisson / log (R's poisson()): mu = exp(eta), g' = 1/mu, V = mu, so
-    //   w = 1/(V g'^2) = mu,  w*z = mu (eta - off) + (y - mu),
-    //   dev row = y log(y/mu) - (y - mu) with log(y/mu) = log(y) - eta
-    // -- one exp and one log (or a table look-up), no divisions; the reference operation order
-    // (below) agrees to a few ulp per row, and it still runs where exp could overflow.
-    const double mu = small_exp ? exp_small(eta) : exp(eta);
-    w = pw * mu;
-    wz = pw * (mu * (eta - off) + (y - mu));
-    double d0;
-    if (ylogy && y < (double)POIS_TAB && y == floor(y)) d0 = ylogy[(int)y] - y * eta;
-    else d0 = y > 0.0 ? y * (log_pos(y) - eta) : 0.0;
-    s_dev += pw * (d0 - (y - mu));
-    s_aux += pw;
+  if (fam == FAM_POISSON && lnk == LNK_LOG && mode == MODE_IRLS && SGLM_POISSON_LOG_FAST(eta, y)) {
+    poisson_log_row<false>(eta, y, off, pw, small_exp, ylogy, w, wz, s_dev, s_aux, nil, nil);
     return;
   }
-  if (fam == FAM_GAMMA && lnk == LNK_INVERSE && mode == MODE_IRLS && eta > 1e-150 && eta < 1e150 && y > 1e-150 &&
-      y < 1e150) {
-    // Gamma / inverse (R's Gamma()): mu = 1/eta, g' = -1/mu^2, V = mu^2, so
-    //   w = mu^2,  w*z = mu^2 (eta - off) - (y - mu),
-    //   dev row = -(log(y/mu) - (y - mu)/mu) = -(log(y eta) - (y eta - 1))
-    // -- one reciprocal and one log instead of four divisions and a log (the range checks keep
-    // eta, y and y eta normal and finite for rcp_pos / log_pos).
-    const double mu = rcp_pos(eta);
-    const double mu2 = mu * mu;
-    const double ye = y * eta;
-    w = pw * mu2;
-    wz = pw * (mu2 * (eta - off) - (y - mu));
-    s_dev += pw * (-(log_pos(ye) - (ye - 1.0)));
-    s_aux += pw;
+  if (fam == FAM_GAMMA && lnk == LNK_INVERSE && mode == MODE_IRLS && SGLM_GAMMA_INVERSE_FAST(eta, y)) {
+    gamma_inverse_row<false>(eta, y, off, pw, w, wz, s_dev, s_aux, nil, nil, nil);
     return;
   }
   if (fam == FAM_GAMMA && lnk == LNK_LOG && mode == MODE_IRLS && fabs(eta) < 300.0 && y > 1e-150 && y < 1e150) {
@@ -445,9 +506,7 @@ __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta,
     const double wt = mu * t;
     w = pw * wt;
     wz = pw * (wt * (eta - off) + (y - mu) * t);
-    double d0;
-    if (ylogy && y < (double)POIS_TAB && y == floor(y)) d0 = ylogy[(int)y] - y * eta;
-    else d0 = y > 0.0 ? y * (log_pos(y) - eta) : 0.0;
+    const double d0 = ylogy_minus_yeta(ylogy, y, eta);
     const double yt = y + theta;
     s_dev += pw * (d0 - yt * log_pos(yt * r));
     s_aux += pw;
@@ -463,7 +522,7 @@ __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta,
   if (init_fast && fam == FAM_BINOMIAL && mode != MODE_IRLS && mode != MODE_LM_GRAM && !has_m && y >= 0.0 &&
       y <= 1.0) {
     // (init_fast: set by the narrow kernel's non-IRLS instantiation only, whose loop the
-    // invariants are hoisted out of; the fused kernels take them from LDS, init_const below.)
+    // invariants are hoisted out of; the fused kernels take them from LDS, pass_row_init.)
     const InitConst c = init_const(fam, lnk, mode, mu0);
     pass_row_init(c.v, y, off, pw, w, wz, s_dev, s_aux);
     return;
@@ -478,30 +537,42 @@ __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta,
   s_aux += pw;
 }
 
-// Logit with m = 1, in-pass final statistics (PassArgs::stats_in_pass): the IRLS row stage of
-// pass_row plus stats_row's pearsonCalc / llBinomial terms at the same mu, sharing one exp, one
-// reciprocal and one log -- the pass then needs no eta store and no stats_kernel pass.  Rows
-// outside the fast range take both reference-order functions.
-__device__ __forceinline__ void pass_row_logit_stats(double eta, double y, double off, double pw, double& w, double& wz,
-                                                     double& s_dev, double& s_aux, double& s_pear, double& s_ll,
-                                                     double& s_bad, bool small_exp);
-
-// The reference operation order of the final statistics (pearsonCalc GLM.scala:90-101,
-// llBinomial :132-143, devBinomial :162-170, the R families' loglik ingredients), out of line
-// like pass_row_ref: rows the inline fast path of stats_row does not take.
+// The reference operation order of the final statistics (pearsonCalc GLM.scala:90-101, devBinomial
+// :162-170), out of line like pass_row_ref: rows the inline fast path of stats_row does not take.
+// stats_core is its one spelling -- mu (returned), V, the unit deviance, Pearson and sum pw into a zeroed
+// acc -- with row_core's BYLINK / NB; the family log-likelihood terms follow in each function.
+// init modes (a fit that stops before its first solve): the statistics at mu0 itself, as
+// pearsonCalc / llBinomial see the broadcast ybar (GLM.scala:424-426, 465-466)
+template <bool BYLINK, bool NB>
+__device__ __forceinline__ double stats_core(RowAcc& acc, int fam, int lnk, int mode, double eta, double y, double m,
+                                             double pw, double mu0, double theta) {
+#pragma unroll
+  for (int k = 0; k < NS; ++k) acc.s[k] = 0.0;
+  const double mu = (mode == MODE_IRLS) ? (BYLINK ? unlink_fn_x(lnk, eta) : unlink_fn(fam, lnk, eta, m)) : mu0;
+  const double v = NB ? nb_variance(mu, theta) : variance_fn(fam, mu, m);
+  const double r = y + (-1.0 * mu);
+  acc.s[S_DEV] += NB ? nb_unit_dev(y, mu, pw, theta) : unit_dev(fam, y, mu, m, pw);
+  acc.s[S_PEARSON] += pw * (r * r) / v;
+  acc.s[S_SUMW] += pw;
+  return mu;
+}
+// the R families' loglik ingredients (gaussian, poisson, gamma)
+__device__ __forceinline__ void ext_loglik_terms(RowAcc& acc, int fam, double y, double mu, double pw) {
+  if (fam == FAM_GAUSSIAN) {
+    acc.s[S_LL] += log(pw);
+  } else if (fam == FAM_POISSON) {
+    acc.s[S_LL] += pw * (y * log(mu) - mu - lgamma(y + 1.0));
+  } else {
+    acc.s[S_LL] += pw * log(y);
+    acc.s[S_AUX0] += pw * (y / mu);
+    acc.s[S_AUX1] += pw * log(mu);
+  }
+}
+// the binomial links and the canonical pairs: llBinomial (GLM.scala:132-143)
 __device__ __noinline__ RowAcc stats_row_ref(int fam, int lnk, int mode, double eta, double y, double m, double pw,
                                              double mu0, bool has_m) {
   RowAcc acc;
-#pragma unroll
-  for (int k = 0; k < NS; ++k) acc.s[k] = 0.0;
-  // init modes (a fit that stops before its first solve): the statistics at mu0 itself, as
-  // pearsonCalc / llBinomial see the broadcast ybar (GLM.scala:424-426, 465-466)
-  const double mu = (mode == MODE_IRLS) ? unlink_fn(fam, lnk, eta, m) : mu0;
-  const double v = variance_fn(fam, mu, m);
-  const double r = y + (-1.0 * mu);
-  acc.s[S_DEV] += unit_dev(fam, y, mu, m, pw);
-  acc.s[S_PEARSON] += pw * (r * r) / v;
-  acc.s[S_SUMW] += pw;
+  const double mu = stats_core<false, false>(acc, fam, lnk, mode, eta, y, m, pw, mu0, 0.0);
   if (fam == FAM_BINOMIAL) {
     double bad = 0.0, ll;
     if (has_m) {
@@ -515,54 +586,24 @@ __device__ __noinline__ RowAcc stats_row_ref(int fam, int lnk, int mode, double 
     }
     acc.s[S_LL] += pw * ll;
     acc.s[S_BAD] += bad;
-  } else if (fam == FAM_GAUSSIAN) {
-    acc.s[S_LL] += log(pw);
-  } else if (fam == FAM_POISSON) {
-    acc.s[S_LL] += pw * (y * log(mu) - mu - lgamma(y + 1.0));
   } else {
-    acc.s[S_LL] += pw * log(y);
-    acc.s[S_AUX0] += pw * (y / mu);
-    acc.s[S_AUX1] += pw * log(mu);
+    ext_loglik_terms(acc, fam, y, mu, pw);
   }
   return acc;
 }
-
-// stats_row_ref for the non-canonical pairs (extension families only): mu by the link.
+// the non-canonical pairs (extension families only): mu by the link
 __device__ __noinline__ RowAcc stats_row_ref_x(int fam, int lnk, int mode, double eta, double y, double pw,
                                                double mu0) {
   RowAcc acc;
-#pragma unroll
-  for (int k = 0; k < NS; ++k) acc.s[k] = 0.0;
-  const double mu = (mode == MODE_IRLS) ? unlink_fn_x(lnk, eta) : mu0;
-  const double v = variance_fn(fam, mu, 1.0);
-  const double r = y + (-1.0 * mu);
-  acc.s[S_DEV] += unit_dev(fam, y, mu, 1.0, pw);
-  acc.s[S_PEARSON] += pw * (r * r) / v;
-  acc.s[S_SUMW] += pw;
-  if (fam == FAM_GAUSSIAN) {
-    acc.s[S_LL] += log(pw);
-  } else if (fam == FAM_POISSON) {
-    acc.s[S_LL] += pw * (y * log(mu) - mu - lgamma(y + 1.0));
-  } else {
-    acc.s[S_LL] += pw * log(y);
-    acc.s[S_AUX0] += pw * (y / mu);
-    acc.s[S_AUX1] += pw * log(mu);
-  }
+  const double mu = stats_core<true, false>(acc, fam, lnk, mode, eta, y, 1.0, pw, mu0, 0.0);
+  ext_loglik_terms(acc, fam, y, mu, pw);
   return acc;
 }
-
-// stats_row_ref_x for the negative binomial: S_LL is the whole log-likelihood sum pw dnbinom(y, theta, mu, log).
+// the negative binomial: S_LL is the whole log-likelihood sum pw dnbinom(y, theta, mu, log)
 __device__ __noinline__ RowAcc stats_row_ref_nb(int lnk, int mode, double eta, double y, double pw, double mu0,
                                                 double theta) {
   RowAcc acc;
-#pragma unroll
-  for (int k = 0; k < NS; ++k) acc.s[k] = 0.0;
-  const double mu = (mode == MODE_IRLS) ? unlink_fn_x(lnk, eta) : mu0;
-  const double v = nb_variance(mu, theta);
-  const double r = y + (-1.0 * mu);
-  acc.s[S_DEV] += nb_unit_dev(y, mu, pw, theta);
-  acc.s[S_PEARSON] += pw * (r * r) / v;
-  acc.s[S_SUMW] += pw;
+  const double mu = stats_core<true, true>(acc, FAM_NEGBIN, lnk, mode, eta, y, 1.0, pw, mu0, theta);
   acc.s[S_LL] += pw * nb_loglik_row(y, mu, theta);
   return acc;
 }
@@ -580,22 +621,9 @@ __device__ __forceinline__ void stats_row(int fam, int lnk, int mode, double eta
     acc.s[S_SUMW] += 1.0;
     return;
   }
-  if (fam == FAM_BINOMIAL && lnk == LNK_LOGIT && mode == MODE_IRLS && !has_m && fabs(eta) < 8.0 && y >= 0.0 &&
-      y <= 1.0) {
-    // Logit, m = 1, the pass's fast-path forms (pass_row): mu = t = 1/(1+e), e = exp(-eta),
-    // V = mu(1 - mu) = e t^2, unit deviance log1p(e) + (1-y) eta, and Breeze's
-    // Binomial(1, mu).logProbabilityOf(k) = k log mu + (1-k) log(1-mu) with log mu = -log1p(e),
-    // log(1-mu) = -eta - log1p(e); |eta| < 8 keeps mu off 0 and 1 (no special cases, k in {0, 1}).
-    const double e = exp_small(-eta);
-    const double u = 1.0 + e;
-    const double t = rcp_pos(u);
-    const double L = fma(e - (u - 1.0), t, log_pos(u));
-    const double v = e * t * t;
-    const double r = y - t;
-    acc.s[S_DEV] += pw * (L + (1.0 - y) * eta);
-    acc.s[S_PEARSON] += pw * (r * r) * rcp_pos(v);
-    acc.s[S_SUMW] += pw;
-    acc.s[S_LL] += pw * ((int)y == 1 ? -L : -L - eta);
+  if (fam == FAM_BINOMIAL && lnk == LNK_LOGIT && mode == MODE_IRLS && !has_m && SGLM_LOGIT_FAST(eta, y)) {
+    double w, wz;  // not used here
+    logit_row<true>(eta, y, 0.0, pw, true, w, wz, acc.s[S_DEV], acc.s[S_SUMW], acc.s[S_PEARSON], acc.s[S_LL]);
     return;
   }
   const RowAcc r = stats_row_ref(fam, lnk, mode, eta, y, m, pw, mu0, has_m);
@@ -630,96 +658,39 @@ __device__ __noinline__ RowStats stats_row_fallback(int fam, int lnk, double eta
   return o;
 }
 
-__device__ __forceinline__ void pass_row_logit_stats(double eta, double y, double off, double pw, double& w, double& wz,
-                                                     double& s_dev, double& s_aux, double& s_pear, double& s_ll,
-                                                     double& s_bad, bool small_exp) {
-  if (fabs(eta) < 8.0 && y >= 0.0 && y <= 1.0) {
-    const double e = small_exp ? exp_small(-eta) : exp(-eta);
-    const double u = 1.0 + e;
-    const double t = rcp_pos(u);
-    const double v = e * t * t;
-    const double L = fma(e - (u - 1.0), t, log_pos(u));  // log1p(e) = -log(mu)
-    w = pw * v;
-    wz = pw * (v * (eta - off) + (y - t));
-    s_dev += pw * (L + (1.0 - y) * eta);
-    s_aux += pw;
-    const double r = y - t;
-    s_pear += pw * (r * r) * rcp_pos(v);
-    s_ll += pw * ((int)y == 1 ? -L : -L - eta);
-    return;
+// In-pass final statistics (PassArgs::stats_in_pass; common.hpp stats_in_pass_family): the IRLS row stage
+// of pass_row plus the final statistics' terms at the same mu -- the pass then needs no eta store and no
+// stats_kernel pass.  Three family-specific accumulators (s2, s3, s4) that the kernel stores into the slots
+// StatsSlots names: logit (Pearson, loglik, bad), Poisson (Pearson, loglik part, -), Gamma (Pearson, AUX0,
+// sum pw log(y eta) -> AUX1 on the host).  Rows outside the fast range take stats_row_fallback.
+template <int FAM>
+struct StatsSlots {
+  static constexpr int S2 = S_PEARSON;
+  static constexpr int S3 = FAM == FAM_GAMMA ? S_AUX0 : S_LL;
+  static constexpr int S4 = FAM == FAM_GAMMA ? S_AUX1 : (FAM == FAM_BINOMIAL ? S_BAD : -1);
+};
+template <int FAM>
+__device__ __forceinline__ void pass_row_stats(double eta, double y, double off, double pw, double& w, double& wz,
+                                               double& s_dev, double& s_aux, double& s2, double& s3, double& s4,
+                                               bool small_exp, const double* ylogy = nullptr) {
+  static_assert(FAM == FAM_BINOMIAL || FAM == FAM_POISSON || FAM == FAM_GAMMA, "stats_in_pass_family");
+  constexpr int LNK = FAM == FAM_BINOMIAL ? LNK_LOGIT : (FAM == FAM_POISSON ? LNK_LOG : LNK_INVERSE);
+  if constexpr (FAM == FAM_BINOMIAL) {
+    if (SGLM_LOGIT_FAST(eta, y)) return logit_row<true>(eta, y, off, pw, small_exp, w, wz, s_dev, s_aux, s2, s3);
+  } else if constexpr (FAM == FAM_POISSON) {
+    if (SGLM_POISSON_LOG_FAST(eta, y))
+      return poisson_log_row<true>(eta, y, off, pw, small_exp, ylogy, w, wz, s_dev, s_aux, s2, s3);
+  } else {
+    if (SGLM_GAMMA_INVERSE_FAST(eta, y)) return gamma_inverse_row<true>(eta, y, off, pw, w, wz, s_dev, s_aux, s2, s3, s4);
   }
-  const RowStats r = stats_row_fallback(FAM_BINOMIAL, LNK_LOGIT, eta, y, off, pw);
-  w = r.w;
-  wz = r.wz;
-  s_dev += r.dev;
-  s_aux += pw;
-  s_pear += r.s2;
-  s_ll += r.s3;
-  s_bad += r.s4;
-}
-
-// Poisson / log, in-pass final statistics: pass_row's fast path plus pearsonCalc (R's variance
-// V = mu) and the mu-dependent part of R's dpois log-density, y log mu - mu with
-// log mu = eta.  The per-row constant -lgamma(y + 1) does not depend on the fit: the initial pass
-// sums pw lgamma(y + 1) once into S_AUX2 (init_stats_const) and the engine subtracts it.
-// Slots: s2 = Pearson, s3 = loglik part, s4 unused.
-__device__ __forceinline__ void pass_row_poisson_stats(double eta, double y, double off, double pw, double& w,
-                                                       double& wz, double& s_dev, double& s_aux, double& s2,
-                                                       double& s3, bool small_exp, const double* ylogy) {
-  if (fabs(eta) < 700.0 && y >= 0.0 && y < 1e300) {
-    const double mu = small_exp ? exp_small(eta) : exp(eta);
-    w = pw * mu;
-    wz = pw * (mu * (eta - off) + (y - mu));
-    double d0;  // pass_row's Poisson unit deviance
-    if (ylogy && y < (double)POIS_TAB && y == floor(y)) d0 = ylogy[(int)y] - y * eta;
-    else d0 = y > 0.0 ? y * (log_pos(y) - eta) : 0.0;
-    s_dev += pw * (d0 - (y - mu));
-    s_aux += pw;
-    const double r = y - mu;
-    s2 += pw * (r * r) * rcp_pos(mu);
-    s3 += pw * (y * eta - mu);
-    return;
-  }
-  const RowStats r = stats_row_fallback(FAM_POISSON, LNK_LOG, eta, y, off, pw);
+  const RowStats r = stats_row_fallback(FAM, LNK, eta, y, off, pw);
   w = r.w;
   wz = r.wz;
   s_dev += r.dev;
   s_aux += pw;
   s2 += r.s2;
   s3 += r.s3;
-}
-
-// Gamma / inverse, in-pass final statistics: pass_row's fast path plus pearsonCalc (V = mu^2:
-// (y - mu)^2 / mu^2 = (y - mu)^2 eta^2) and R's Gamma loglik ingredients sum pw y / mu = sum pw y eta
-// (S_AUX0) and sum pw log mu = sum pw log y - sum pw log(y eta) (S_AUX1: the pass sums the second
-// term, which its deviance already evaluates; the fit-constant sum pw log y -- also S_LL itself --
-// comes from the initial pass, init_stats_const).  Slots: s2 = Pearson, s3 = AUX0, s4 = log(y eta).
-__device__ __forceinline__ void pass_row_gamma_stats(double eta, double y, double off, double pw, double& w,
-                                                     double& wz, double& s_dev, double& s_aux, double& s2, double& s3,
-                                                     double& s4) {
-  if (eta > 1e-150 && eta < 1e150 && y > 1e-150 && y < 1e150) {
-    const double mu = rcp_pos(eta);
-    const double mu2 = mu * mu;
-    const double ye = y * eta;
-    const double L = log_pos(ye);
-    w = pw * mu2;
-    wz = pw * (mu2 * (eta - off) - (y - mu));
-    s_dev += pw * (-(L - (ye - 1.0)));
-    s_aux += pw;
-    const double r = y - mu;
-    s2 += pw * (r * r) * (eta * eta);
-    s3 += pw * ye;
-    s4 += pw * L;
-    return;
-  }
-  const RowStats r = stats_row_fallback(FAM_GAMMA, LNK_INVERSE, eta, y, off, pw);
-  w = r.w;
-  wz = r.wz;
-  s_dev += r.dev;
-  s_aux += pw;
-  s2 += r.s2;
-  s3 += r.s3;
-  s4 += r.s4;
+  if constexpr (StatsSlots<FAM>::S4 >= 0) s4 += r.s4;
 }
 
 // The per-fit constants of the in-pass statistics, summed by the initial pass into S_AUX2:
@@ -746,7 +717,7 @@ __device__ __forceinline__ void poisson_init_table(double* tab, double mu0, int 
   tab[k] = (y > 0.0 ? y * log(y / mu0) : 0.0) - (y - mu0);
   tab[POIS_TAB + k] = lgamma(y + 1.0);
 }
-// The IRLS passes' table (pass_row ylogy): k log k, 0 at k = 0.
+// The IRLS passes' table (ylogy_minus_yeta): k log k, 0 at k = 0.
 __device__ __forceinline__ void poisson_ylogy_table(double* tab, int k) {
   const double y = (double)k;
   tab[k] = y > 0.0 ? y * log(y) : 0.0;
@@ -767,7 +738,7 @@ __device__ __forceinline__ bool poisson_init_row(const double* c, const double* 
 }
 
 // Per-row diagnostics at eta (influence.hip): the pass's working weight w = pw / (V g'^2)
-// (pass_row_ref's expression, 0 where pw = 0), the Pearson residual (y - mu) sqrt(pw / V) that Cook's
+// (row_core's, 0 where pw = 0), the Pearson residual (y - mu) sqrt(pw / V) that Cook's
 // distance needs, and the residual of the requested type on the engine's count scale
 // (mu = unlink(eta, m)): response y - mu, working (y - mu) g'(mu), Pearson, or deviance
 // sign(y - mu) sqrt(factor * unit_dev) with the family factor the host applies to the deviance sum
@@ -780,18 +751,17 @@ struct InflRow {
 };
 __device__ __noinline__ InflRow influence_row(int fam, int lnk, int rtype, double eta, double y, double m, double pw,
                                               double theta) {
-  const bool x = noncanonical_pair(fam, lnk);  // the links selected by link (link_fn_x ...)
-  const double mu = x ? unlink_fn_x(lnk, eta) : unlink_fn(fam, lnk, eta, m);
-  const double g = x ? lprime_fn_x(lnk, mu) : lprime_fn(fam, lnk, mu, m);
-  const double v = fam == FAM_NEGBIN ? nb_variance(mu, theta) : variance_fn(fam, mu, m);
+  // (noncanonical_pair: the links selected by link -- every negative binomial pair)
+  const RowCore c = row_core(noncanonical_pair(fam, lnk), fam == FAM_NEGBIN, fam, lnk, MODE_IRLS, eta, m, pw, 0.0, theta);
+  const double mu = c.mu;
   const double e = y + (-1.0 * mu);
   InflRow r;
-  r.w = pw * (1.0 / (v * (g * g)));
-  r.rp = e * sqrt(pw / v);
+  r.w = c.w;
+  r.rp = e * sqrt(pw / c.v);
   if (rtype == RESID_RESPONSE) {
     r.resid = e;
   } else if (rtype == RESID_WORKING) {
-    r.resid = e * g;
+    r.resid = e * c.g;
   } else if (rtype == RESID_PEARSON) {
     r.resid = r.rp;
   } else {
@@ -803,26 +773,8 @@ __device__ __noinline__ InflRow influence_row(int fam, int lnk, int rtype, doubl
   return r;
 }
 
-// Dispatch of the in-pass statistics rows: three family-specific accumulators (s2, s3, s4) that
-// the kernel stores into the slots stats_slots() names.
-template <int FAM>
-__device__ __forceinline__ void pass_row_stats(double eta, double y, double off, double pw, double& w, double& wz,
-                                               double& s_dev, double& s_aux, double& s2, double& s3, double& s4,
-                                               bool small_exp, const double* ylogy = nullptr) {
-  if constexpr (FAM == FAM_BINOMIAL)
-    pass_row_logit_stats(eta, y, off, pw, w, wz, s_dev, s_aux, s2, s3, s4, small_exp);
-  else if constexpr (FAM == FAM_POISSON)
-    pass_row_poisson_stats(eta, y, off, pw, w, wz, s_dev, s_aux, s2, s3, small_exp, ylogy);
-  else
-    pass_row_gamma_stats(eta, y, off, pw, w, wz, s_dev, s_aux, s2, s3, s4);
-}
-// slots of (s2, s3, s4): logit (Pearson, loglik, bad), Poisson (Pearson, loglik part, -),
-// Gamma (Pearson, AUX0, sum pw log(y eta) -> AUX1 on the host)
-template <int FAM>
-struct StatsSlots {
-  static constexpr int S2 = S_PEARSON;
-  static constexpr int S3 = FAM == FAM_GAMMA ? S_AUX0 : S_LL;
-  static constexpr int S4 = FAM == FAM_GAMMA ? S_AUX1 : (FAM == FAM_BINOMIAL ? S_BAD : -1);
-};
+#undef SGLM_LOGIT_FAST
+#undef SGLM_POISSON_LOG_FAST
+#undef SGLM_GAMMA_INVERSE_FAST
 
 }  // namespace sglm

@@ -25,6 +25,7 @@
 #include "kernels.hpp"
 #include "procx.hpp"
 #include "rowmath.hpp"
+#include "waitcnt.hpp"
 
 namespace sglm {
 
@@ -33,13 +34,6 @@ typedef double dv2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
 
 namespace {
-
-// s_waitcnt vmcnt(N) with expcnt / lgkmcnt left open (gfx9 encoding).
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
 
 __device__ __forceinline__ void lds_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 

@@ -301,10 +301,12 @@ class Engine:
         L.check(call(cov.ctypes.data_as(L.dp), None if meat is None else meat.ctypes.data_as(L.dp)), name)
         return (cov, meat) if return_meat else cov
 
-    def _beta(self, beta):
+    def _beta(self, beta, p=None):
+        """beta as a contiguous vector of p (default: the resident design's) coefficients."""
+        p = self.p if p is None else p
         b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
-        if b.shape[0] != self.p:
-            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
+        if b.shape[0] != p:
+            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {p} columns, "
                                              f"beta {b.shape[0]} rows")
         return b
 
@@ -409,10 +411,7 @@ class Engine:
         if X.ndim != 2:
             raise L.IllegalArgumentException("requirement failed: X must be a matrix")
         n, p = X.shape
-        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
-        if b.shape[0] != p:
-            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {p} columns, "
-                                             f"beta {b.shape[0]} rows")
+        b = self._beta(beta, p)
         offset, m = _vec(offset, n), _vec(m, n)
         out = np.empty(n)
         L.check(self._lib.sglm_predict_new(self._h, L.ptr(X), n, p, max(n, 1), L.ptr(b), L.ptr(offset), L.ptr(m),
@@ -423,10 +422,7 @@ class Engine:
     def vcov(self, beta, family="binomial", link="logit"):
         """Unscaled covariance inv(X'WX) at beta (p x p): one pass and the fit's solve rule."""
         o = glm_opts(family, link)
-        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
-        if b.shape[0] != self.p:
-            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
-                                             f"beta {b.shape[0]} rows")
+        b = self._beta(beta)
         cov = np.zeros((self.p, self.p), order="F")
         L.check(self._lib.sglm_vcov(self._h, C.byref(o), L.ptr(b), cov.ctypes.data_as(L.dp)), "sglm_vcov")
         return cov
@@ -439,10 +435,7 @@ class Engine:
             raise L.IllegalArgumentException(f"requirement failed: resid must be one of {sorted(L.RESID_TYPES)}, "
                                              f"got {resid!r}")
         o = glm_opts(family, link)
-        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
-        if b.shape[0] != self.p:
-            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
-                                             f"beta {b.shape[0]} rows")
+        b = self._beta(beta)
         hat, res, cooks = np.empty(self.n), np.empty(self.n), np.empty(self.n)
         sh = C.c_double()
         L.check(self._lib.sglm_influence(self._h, C.byref(o), L.ptr(b), L.RESID_TYPES[resid], float(dispersion),
@@ -485,10 +478,7 @@ class Engine:
             raise L.IllegalArgumentException(f"requirement failed: type must be one of {sorted(L.HC_TYPES)}, "
                                              f"got {type!r}")
         o = glm_opts(family, link)
-        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
-        if b.shape[0] != self.p:
-            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
-                                             f"beta {b.shape[0]} rows")
+        b = self._beta(beta)
         return self._cov_meat(return_meat, "sglm_vcov_robust", lambda cov, meat: self._lib.sglm_vcov_robust(
             self._h, C.byref(o), L.ptr(b), L.HC_TYPES[type], cov, meat))
 
@@ -523,10 +513,7 @@ class Engine:
         the pair (V, M)."""
         _cluster_type(type)
         o = glm_opts(family, link)
-        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
-        if b.shape[0] != self.p:
-            raise L.IllegalArgumentException(f"requirement failed: Dimension mismatch: X has {self.p} columns, "
-                                             f"beta {b.shape[0]} rows")
+        b = self._beta(beta)
         return self._cov_meat(return_meat, "sglm_vcov_cluster", lambda cov, meat: self._lib.sglm_vcov_cluster(
             self._h, C.byref(o), L.ptr(b), L.HC_TYPES[type], int(bool(cadjust)), cov, meat))
 
