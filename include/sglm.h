@@ -72,7 +72,9 @@ extern "C" {
                               (with sglm_nb_opts / sglm_nb_result), sglm_fit_glm_fe (with sglm_fe_info),
                               sglm_fe_pass, sglm_vcov_fe, sglm_get_fe_ms, sglm_set_fe2, sglm_fe2_plan,
                               sglm_fit_glm_fe2 (with sglm_fe2_opts / sglm_fe2_info), sglm_fe2_pass,
-                              sglm_vcov_fe2, sglm_get_fe2_ms; (new values only:) SGLM_SQRT and
+                              sglm_vcov_fe2, sglm_get_fe2_ms, sglm_fit_glm_gee (with sglm_gee_opts /
+                              sglm_gee_info, enum sglm_corstr), sglm_gee_pass, sglm_vcov_gee,
+                              sglm_get_gee_ms; (new values only:) SGLM_SQRT and
                               the non-canonical (family, link) pairs of enum sglm_link's table,
                               SGLM_NEGBIN and its three pairs */
 
@@ -620,6 +622,54 @@ int sglm_vcov_fe2(sglm_engine *h, const sglm_glm_opts *opts, const sglm_fe2_opts
 /* Kernel times of the last two-way step, ms [5]: weights, factor-1 sums, factor-2 sums, sweeps, cross product
  * (HIP events; -1 before any call). */
 int sglm_get_fe2_ms(sglm_engine *h, double *ms);
+
+/* ---- GEE fits: the population-averaged GLM with an exchangeable working correlation over the cluster factor
+ * of sglm_set_clusters (Liang & Zeger; geepack::geeglm(corstr = "exchangeable"), Stata xtgee, statsmodels GEE) ----
+ * With d_i = sqrt(w_i) (w the IRLS working weight), R_g = (1 - rho) I + rho 11' has the inverse
+ * (I - c_g 11') / (1 - rho), c_g = rho / (1 - rho + n_g rho), so one step's normal equations are
+ *   A = (X'WX - sum_g c_g s_g s_g') / (1 - rho),   b = (X'Wz - sum_g c_g s_g t_g) / (1 - rho),
+ *   s_g = sum_{i in g} d_i x_i,  t_g = sum_{i in g} d_i z_i
+ * -- the fixed-effects downdate with sqrt(w) for w and c_g for 1 / W_g.  Per row e_i = d_i (y_i - mu_i) g'(mu_i)
+ * (the Pearson residual up to the sign of g'), per group n_g (rows of positive prior weight), E_g = sum e_i,
+ * Q_g = sum e_i^2; with N = sum n_g the moment estimates are (statsmodels / gee, ddof p)
+ *   phi = sum Q_g / (N - p),   rho = [sum (E_g^2 - Q_g) / 2] / [(sum n_g (n_g - 1) / 2 - p) phi].
+ * A step at beta: the pass at beta, the group sums (all-reduced), rho(beta) and phi(beta), A and b, the solve.
+ * The initial-mode pass uses rho = 0.  SGLM_COR_INDEPENDENCE is rho = 0 throughout: every iterate is
+ * sglm_fit_glm's, bitwise.  Scope, collectives and determinism: sglm_fit_glm_fe's.  SGLM_EINVAL before the first
+ * pass without clusters, when sum n_g (n_g - 1) / 2 <= p or N <= p, and for a fixed rho with rho >= 1 or
+ * 1 - rho + n_max rho <= 0; an estimated rho that leaves that range is SGLM_EINVAL naming the iteration. */
+enum sglm_corstr { SGLM_COR_INDEPENDENCE = 0, SGLM_COR_EXCHANGEABLE = 1 };
+typedef struct {
+  int corstr;      /* enum sglm_corstr */
+  int fix_rho;     /* != 0: use rho, do not estimate it (Stata corr(fixed)) */
+  double rho;
+} sglm_gee_opts;
+typedef struct {
+  double rho, phi; /* at the returned coefficients (a fixed rho: that value) */
+  double N;        /* rows of positive prior weight */
+  int32_t G_eff;   /* groups with such a row */
+  int32_t n_max;   /* the largest n_g */
+  double rows_ms, sum_ms, combine_ms, gram_ms; /* as sglm_get_gee_ms, of the last step */
+} sglm_gee_info;
+/* The fit: start, stop rule, dev_trace, iter, null_deviance, pearson and loglik are sglm_fit_glm's;
+ * std_err = sqrt(diag(inv(A))) of the last solve, unscaled (the model-based one; sglm_vcov_gee has the robust
+ * covariance).  gee NULL: exchangeable, rho estimated.  info may be NULL. */
+int sglm_fit_glm_gee(sglm_engine *h, const sglm_glm_opts *opts, const sglm_gee_opts *gee, sglm_preglm *out,
+                     sglm_gee_info *info);
+/* The test-level step at any beta: A [p*p] col-major, b [p], group [G*(p+4)] = s [G x p] col-major | t | n | E | Q,
+ * moments [5] = sum E_g^2, sum Q_g, sum n_g (n_g - 1) / 2, N, n_max, scalars [8], *rho_used (gee->rho with
+ * fix_rho, else rho(beta)); any output may be NULL.  beta == NULL selects opts' initial mode with rho = 0. */
+int sglm_gee_pass(sglm_engine *h, const sglm_glm_opts *opts, const sglm_gee_opts *gee, const double *beta, double *A,
+                  double *b, double *group, double *moments, double *scalars, double *rho_used);
+/* The covariance of beta at (beta, rho).  robust == 0: phi(beta) inv(A), the naive / model-based one.
+ * robust != 0: inv(A) M inv(A), M = U'U, U_g = (sum_{i in g} d_i e_i x_i - c_g E_g s_g) / (1 - rho) (phi cancels);
+ * cadjust: a further G / (G - 1).  Independence: rho is read as 0 and the robust covariance is
+ * sglm_vcov_cluster(SGLM_HC0, cadjust).  meat [p*p] may be NULL (robust == 0: zeros). */
+int sglm_vcov_gee(sglm_engine *h, const sglm_glm_opts *opts, const sglm_gee_opts *gee, const double *beta, double rho,
+                  int robust, int cadjust, double *cov, double *meat);
+/* Kernel times of the last GEE step, ms [4]: rows, segment sums, combine, the Gram pass over the group sums
+ * (HIP events; -1 before any call). */
+int sglm_get_gee_ms(sglm_engine *h, double *ms);
 
 int sglm_get_stats(sglm_engine *h, sglm_stats *out);
 /* The kernel an engine would run a pass of an n x p shard with (enum sglm_pass_kernel, -1 on bad

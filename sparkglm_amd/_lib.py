@@ -43,6 +43,7 @@ EXPORTS = [
     "sglm_fit_glm_nb",
     "sglm_fit_glm_fe", "sglm_fe_pass", "sglm_vcov_fe", "sglm_get_fe_ms",
     "sglm_set_fe2", "sglm_fe2_plan", "sglm_fit_glm_fe2", "sglm_fe2_pass", "sglm_vcov_fe2", "sglm_get_fe2_ms",
+    "sglm_fit_glm_gee", "sglm_gee_pass", "sglm_vcov_gee", "sglm_get_gee_ms",
 ]
 PREDICT_LINK, PREDICT_RESPONSE = 0, 1
 RESID_TYPES = {"response": 0, "working": 1, "pearson": 2, "deviance": 3}  # enum sglm_resid_type
@@ -84,6 +85,19 @@ class Fe2Info(C.Structure):
     _fields_ = [("G_eff", C.c_int32), ("H_eff", C.c_int32), ("ncomp", C.c_int32), ("sweeps_last", C.c_int32),
                 ("sweeps_total", C.c_int64), ("df_residual", C.c_double), ("weights_ms", C.c_double),
                 ("sum1_ms", C.c_double), ("sum2_ms", C.c_double), ("sweep_ms", C.c_double), ("cross_ms", C.c_double)]
+
+
+CORSTRS = {"independence": 0, "exchangeable": 1}  # enum sglm_corstr
+
+
+class GeeOpts(C.Structure):
+    _fields_ = [("corstr", C.c_int), ("fix_rho", C.c_int), ("rho", C.c_double)]
+
+
+class GeeInfo(C.Structure):
+    _fields_ = [("rho", C.c_double), ("phi", C.c_double), ("N", C.c_double), ("G_eff", C.c_int32),
+                ("n_max", C.c_int32), ("rows_ms", C.c_double), ("sum_ms", C.c_double), ("combine_ms", C.c_double),
+                ("gram_ms", C.c_double)]
 
 
 class PreLM(C.Structure):
@@ -241,6 +255,12 @@ def load():
         "sglm_vcov_fe2": ([h, C.POINTER(GlmOpts), C.POINTER(Fe2Opts), dp, dp, dp, C.c_int, C.c_int, C.c_int, dp, dp],
                           C.c_int),
         "sglm_get_fe2_ms": ([h, dp], C.c_int),
+        "sglm_fit_glm_gee": ([h, C.POINTER(GlmOpts), C.POINTER(GeeOpts), C.POINTER(PreGLM), C.POINTER(GeeInfo)],
+                             C.c_int),
+        "sglm_gee_pass": ([h, C.POINTER(GlmOpts), C.POINTER(GeeOpts), dp, dp, dp, dp, dp, dp, dp], C.c_int),
+        "sglm_vcov_gee": ([h, C.POINTER(GlmOpts), C.POINTER(GeeOpts), dp, C.c_double, C.c_int, C.c_int, dp, dp],
+                          C.c_int),
+        "sglm_get_gee_ms": ([h, dp], C.c_int),
         "sglm_cluster_plan": ([C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int64),
                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
     }

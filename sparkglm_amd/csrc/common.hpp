@@ -318,6 +318,49 @@ struct FeGroupArgs {
   double* y;
 };
 
+// GEE fits with an exchangeable working correlation over the cluster factor (gee.hip; gee.cpp).
+// gee_rows_kernel: fe_weights_kernel's tiling; one value per row into `d` and four sums per segment into
+// Q [nseg][GEE_NQ] = sum d z | rows of positive prior weight | sum e | sum e^2, by kind:
+//   GEE_STEP   d_i = sqrt(w_i)                    at eta (mode MODE_IRLS) or at mu0 (the init modes)
+//   GEE_SCORE  d_i e_i = w_i (y_i - mu_i) g'(mu_i)  (the four sums are GEE_STEP's)
+//   GEE_COUNT  nothing; only the row counts are summed (no eta is read): the refusals before the first pass
+// e_i = d_i (y_i - mu_i) g'(mu_i), z_i the working response without the offset (rowmath.hpp working_wz).
+enum GeeKind : int { GEE_STEP = 0, GEE_SCORE = 1, GEE_COUNT = 2 };
+constexpr int GEE_NQ = 4;
+struct GeeArgs {
+  const double* y;
+  const double* eta;         // eta of the last pass (offset included); not read in the init modes
+  const double* m;           // may be null
+  const double* off;         // may be null
+  const double* prior;       // may be null
+  int64_t n, ld;             // rows; d is written up to ld (zeros past n)
+  int family, link, mode, kind;
+  double mu0, theta;
+  const int64_t* seg_start;  // the segments of sglm_set_clusters (ClusterArgs)
+  const int64_t* tile_seg;
+  int64_t ntiles;
+  double* d;                 // [ld]; null: not stored (GEE_COUNT)
+  double* Q;                 // [nseg][GEE_NQ]
+};
+// The group sums as one buffer (one all-reduce): s [ld x p] col-major | t | n | E | Q, ld = G rounded up to 32.
+// gee_moments_kernel: per-block partials [grid][NS] of GeeMoment over the G rows (M_NMAX a maximum).
+// gee_scale_kernel: c_g = rho / (1 - rho + n_g rho); the design X [ld x p] and response y [ld] of the Gram
+// pass over the groups --
+//   meat = 0: x_g = sqrt(|c_g|) s_g, y_g = sqrt(|c_g|) t_g       (sign(c_g) = sign(rho): applied on the host)
+//   meat = 1: x_g = (S1_g - c_g E_g s_g) / (1 - rho), y_g = 0; S1 from `grp`, s | n | E from `grp_s`
+// rows with n_g = 0: exact zeros.
+enum GeeMoment : int { M_E2 = 0, M_Q = 1, M_PAIRS = 2, M_N = 3, M_NMAX = 4, M_GEFF = 5, GEE_NM = 6 };
+struct GeeGroupArgs {
+  const double* grp;
+  const double* grp_s;
+  int64_t G, ld;
+  int p, meat;
+  double rho;
+  double* X;
+  double* y;
+  double* partials;          // gee_moments_kernel: [grid][NS]
+};
+
 // Two-way fixed effects: a second absorbed factor beside the cluster factor (fe2.hip; fe2.cpp).
 // Factor 2's rows are listed per level in ascending order (a stable counting sort by code) and each level's
 // list is cut into chunks of FE2_CHUNK positions; the chunks, already ordered by level, feed combine_kernel.

@@ -1,5 +1,5 @@
 // engine.hpp -- the HIP engine behind the C ABI: what its host translation units share.
-// Private to engine.cpp, negbin.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp, fe.cpp and ingest.cpp; never included
+// Private to engine.cpp, negbin.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp, fe.cpp, gee.cpp and ingest.cpp; never included
 // by a .hip file.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -291,6 +291,17 @@ struct sglm_engine : public sglm::Backend {
   // kernel times of the last FE step: weights, segment sums, combine, Gram over the group sums (-1: none yet)
   double fe_ms[4] = {-1.0, -1.0, -1.0, -1.0};
 
+  // ---- GEE with an exchangeable working correlation over the cluster factor (gee.hip; gee.cpp):
+  // sglm_fit_glm_gee / sglm_gee_pass / sglm_vcov_gee.  Buffers of its own, so the fixed-effects sums keep theirs.
+  double *dgq = nullptr, *dgqp = nullptr;         // per-segment scalar sums [nseg][GEE_NQ]; their combine scratch
+  // the group sums s | t | n | E | Q (common.hpp GeeGroupArgs), summed over shards and ranks in place; dgg2: the
+  // step's sums kept while sglm_vcov_gee forms the score-weighted ones; dgm: moment partials [GEE_MOMENT_BLOCKS][NS] | out [NS]
+  double *dgg = nullptr, *dgg2 = nullptr, *dgm = nullptr;
+  bool gee_stale = true;                          // dgg may hold other shards' sums: zero it before the combine
+  hipEvent_t evg[2] = {nullptr, nullptr};
+  // kernel times of the last GEE step: rows, segment sums, combine, Gram over the group sums (-1: none yet)
+  double gee_ms[4] = {-1.0, -1.0, -1.0, -1.0};
+
   // ---- two-way fixed effects (fe2.hip; fe2.cpp): the second factor of sglm_set_fe2, its row lists, the
   // level matrices of the sweeps and their scratch; dropped with the clusters ----
   struct Fe2State;
@@ -430,9 +441,18 @@ struct sglm_engine : public sglm::Backend {
   // va, vb: where the kernel stores the two per-row values it sums (common.hpp FeArgs), or null
   int fe_sums_local(int kind, int mode, int family, int link, double mu0, double* va = nullptr, double* vb = nullptr);
   int fe_sync();
+  // the shared tail of fe_sums_local / gee_sums_local: segment sums of u x and the scalar columns through the combine
+  int group_combine_local(bool rows, const double* Q, double* Qp, int ncol, double* grp);
 
   // ---- fe2.cpp ----
   void free_fe2();
+
+  // ---- gee.cpp ----
+  void free_gee();
+  int gee_prepare();
+  int64_t gee_len() const { return cl_inner->n_pad * (p + sglm::GEE_NQ); }  // doubles of s | t | n | E | Q, padding included
+  // the row values of `kind` (common.hpp GeeKind) and this shard's group sums into dgg: enqueued on the stream
+  int gee_sums_local(int kind, int mode, int family, int link, double mu0);
 };
 
 namespace sglm {
@@ -449,9 +469,10 @@ inline int check_handle(sglm_engine* h) {
 // The number of clusters every shard (and every rank: one small all-reduce) declared; SGLM_EINVAL
 // on every rank when they differ or none are set.
 int cluster_count(sglm_engine* h, int32_t* G);
-// The cluster sums S (fe: the group sums S | t | W, sglm_engine::dfg) summed in place over the handle's
-// shards or ranks; every rank (a group: shard 0) ends with bitwise the same sums.
-int sum_cluster_scores(sglm_engine* h, bool fe = false);
+// The cluster sums S (SUM_FE: the group sums S | t | W, sglm_engine::dfg; SUM_GEE: s | t | n | E | Q, dgg) summed
+// in place over the handle's shards or ranks; every rank (a group: shard 0) ends with bitwise the same sums.
+enum GroupSumBuffer : int { SUM_CLUSTER = 0, SUM_FE = 1, SUM_GEE = 2 };
+int sum_cluster_scores(sglm_engine* h, int which = SUM_CLUSTER);
 // The combine tree's plan.  An open range is a destination row of S and the positions [lo, hi) it owns in the
 // level's input (ascending, contiguous).  A range is cut into chunks of CLUSTER_CHUNK positions.  One chunk: it is
 // summed into S and the range is done.  Several: each is summed into a row of the scratch, and those rows are
@@ -479,7 +500,11 @@ int clustered_finish(int hc_type, double nrows, int64_t p, int64_t absorbed, int
 
 // ---- fe.cpp: what the two-way fixed-effects fits (fe2.cpp) share with the one-way ones ----
 // what every fixed-effects entry point requires, before any launch; the buffers of a step
-int fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G);
+// (which: SUM_FE, or SUM_GEE for the GEE fits' buffers and wording)
+int fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G, int which = SUM_FE);
+// after every shard's local sums of a step were enqueued (fe_sums_local / gee_sums_local): synchronise, take the
+// kernel times (fe_ms / gee_ms; rows: the segment sums and the combine too), sum over shards and ranks
+int group_sums_finish(sglm_engine* h, int which, bool rows);
 // While it lives every IRLS pass of the handle's shards stores eta; at its end the passes read the shards'
 // own offsets again.
 struct FeScope {

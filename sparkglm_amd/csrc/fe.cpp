@@ -98,7 +98,6 @@ int sglm_engine::fe_offset_local() {
 // The row values of `kind` (common.hpp FeKind) and this shard's group sums into dfg: enqueued on the stream
 int sglm_engine::fe_sums_local(int kind, int mode, int family, int link, double mu0, double* va, double* vb) {
   HIPCHK(hipSetDevice(device));
-  const int64_t ld = cl_inner->n_pad;
   // as S of the cluster-robust covariance: the combine rewrites the rows of the groups that have a segment
   // here and no others, so the buffer is cleared after every cross-shard sum that landed in it
   if (fe_stale) {
@@ -127,7 +126,15 @@ int sglm_engine::fe_sums_local(int kind, int mode, int family, int link, double 
   a.va = va;
   a.vb = vb;
   HIPCHK(launch_fe_weights(a, fe_grid(ncu, cl_ntiles), st, evf[0], evf[1]));
-  const bool rows = kind != FE_CHECK;  // the sums of w x (u x) as well
+  // the sums of w x (u x) as well, then the per-segment scalars: two columns, t | W
+  return group_combine_local(kind != FE_CHECK, dfq, dfqp, 2, dfg);
+}
+
+// The tail of a step's local sums (fixed effects: dfg; GEE: dgg): with `rows` the segment sums of u x (u: domega)
+// through the combine tree into the first p columns of grp, then the ncol per-segment scalars Q through the same
+// tree into the columns after them (evcl[2] to evcl[3] spans both trees)
+int sglm_engine::group_combine_local(bool rows, const double* Q, double* Qp, int ncol, double* grp) {
+  const int64_t ld = cl_inner->n_pad;
   if (rows) {
     ClusterArgs c{};
     c.X = dX;
@@ -135,15 +142,14 @@ int sglm_engine::fe_sums_local(int kind, int mode, int family, int link, double 
     c.p = (int)p;
     c.n = n;
     c.u = domega;
-    c.seg_start = a.seg_start;
-    c.tile_seg = a.tile_seg;
+    c.seg_start = seg_start();
+    c.tile_seg = tile_seg();
     c.ntiles = cl_ntiles;
     c.R = dR;
     HIPCHK(launch_cluster_sum(c, cluster_sum_grid(ncu, n, (int)p), st, evcl[0], evcl[1]));
-    if (int rc = combine_clusters(dR, dP, (int)p, dfg, ld, evcl[2], nullptr)) return rc;
+    if (int rc = combine_clusters(dR, dP, (int)p, grp, ld, evcl[2], nullptr)) return rc;
   }
-  // the per-segment scalars through the same tree: two columns, t | W (evcl[2] to evcl[3] spans both trees)
-  return combine_clusters(dfq, dfqp, 2, dfg + ld * p, ld, nullptr, rows ? evcl[3] : nullptr);
+  return combine_clusters(Q, Qp, ncol, grp + ld * p, ld, nullptr, rows ? evcl[3] : nullptr);
 }
 
 int sglm_engine::fe_sync() {
@@ -153,14 +159,14 @@ int sglm_engine::fe_sync() {
 }
 
 // what every entry point requires, before any launch; collective (cluster_count)
-int sglm::fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G) {
+int sglm::fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G, int which) {
   if (!opts || !family_link_valid(opts->family, opts->link)) {
     set_error("requirement failed: opts with a supported family/link");
     return SGLM_EINVAL;
   }
   if (int rc = check_handle(h)) return rc;
   if (int rc = check_ready(h)) return rc;
-  if (int rc = require_fused_or_narrow(h, "a fixed-effects fit needs")) return rc;
+  if (int rc = require_fused_or_narrow(h, which == SUM_GEE ? "a GEE fit needs" : "a fixed-effects fit needs")) return rc;
   if (int rc = h->theta_check(opts->family)) return rc;
   if (h->group() && h->group_aborted) {
     set_error("the multi-device handle's RCCL group was aborted by an earlier failure; create a new handle");
@@ -168,48 +174,68 @@ int sglm::fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G) {
   }
   if (int rc = cluster_count(h, G)) return rc;
   for (sglm_engine* s : h->shards())
-    if (int rc = s->fe_prepare()) return rc;
+    if (int rc = which == SUM_GEE ? s->gee_prepare() : s->fe_prepare()) return rc;
   return SGLM_OK;
 }
 
 namespace {
 
+// what the fixed-effects and the GEE steps keep apart: the row kernel's events, the kernel times, the stale mark
+struct GroupSide {
+  hipEvent_t* ev;
+  double* ms;
+  bool* stale;
+};
+GroupSide group_side(sglm_engine* s, int which) {
+  return which == SUM_GEE ? GroupSide{s->evg, s->gee_ms, &s->gee_stale} : GroupSide{s->evf, s->fe_ms, &s->fe_stale};
+}
+
 // kernel times of the step just synchronised: the slowest shard
-int fe_times(sglm_engine* h, bool rows) {
+int group_times(sglm_engine* h, int which, bool rows) {
   const std::vector<sglm_engine*>& shards = h->shards();
   for (sglm_engine* s : shards) {
+    const GroupSide g = group_side(s, which);
     HIPCHK(hipSetDevice(s->device));
     float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, s->evf[0], s->evf[1]));
-    s->fe_ms[0] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, g.ev[0], g.ev[1]));
+    g.ms[0] = ms;
     if (!rows) continue;
     HIPCHK(hipEventElapsedTime(&ms, s->evcl[0], s->evcl[1]));
-    s->fe_ms[1] = ms;
-    s->fe_ms[2] = 0.0;
+    g.ms[1] = ms;
+    g.ms[2] = 0.0;
     if (!s->cl_levels.empty()) {  // (no level, no combine launch: its events were not recorded)
       HIPCHK(hipEventElapsedTime(&ms, s->evcl[2], s->evcl[3]));
-      s->fe_ms[2] = ms;
+      g.ms[2] = ms;
     }
   }
+  double* out = group_side(h, which).ms;
   for (int k = 0; k < 3; ++k)
-    for (const sglm_engine* s : shards) h->fe_ms[k] = s == shards[0] ? s->fe_ms[k] : std::max(h->fe_ms[k], s->fe_ms[k]);
+    for (sglm_engine* s : shards) {
+      const double v = group_side(s, which).ms[k];
+      out[k] = s == shards[0] ? v : std::max(out[k], v);
+    }
   return SGLM_OK;
 }
 
 }  // namespace
 
-// The group sums of `kind` over every shard and rank: shard 0 of every rank ends with bitwise the same dfg
-int sglm::fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0, double* va, double* vb) {
+// After every shard's local sums were enqueued: synchronise, take the kernel times, and sum over shards and ranks
+int sglm::group_sums_finish(sglm_engine* h, int which, bool rows) {
   const std::vector<sglm_engine*>& shards = h->shards();
-  for (sglm_engine* s : shards)  // (va, vb: one shard's rows -- the two-way fits, which ask for them, have one)
-    if (int rc = s->fe_sums_local(kind, mode, family, link, mu0, va, vb)) return rc;
   for (sglm_engine* s : shards)
     if (int rc = s->fe_sync()) return rc;
-  if (int rc = fe_times(h, kind != FE_CHECK)) return rc;
-  // the sum over shards or ranks lands in dfg itself, which this shard's next combine only partly rewrites
+  if (int rc = group_times(h, which, rows)) return rc;
+  // the sum over shards or ranks lands in the buffer itself, which this shard's next combine only partly rewrites
   if (h->group() || h->comm.kind != 0)
-    for (sglm_engine* s : shards) s->fe_stale = true;
-  return sum_cluster_scores(h, true);
+    for (sglm_engine* s : shards) *group_side(s, which).stale = true;
+  return sum_cluster_scores(h, which);
+}
+
+// The group sums of `kind` over every shard and rank: shard 0 of every rank ends with bitwise the same dfg
+int sglm::fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0, double* va, double* vb) {
+  for (sglm_engine* s : h->shards())  // (va, vb: one shard's rows -- the two-way fits, which ask for them, have one)
+    if (int rc = s->fe_sums_local(kind, mode, family, link, mu0, va, vb)) return rc;
+  return group_sums_finish(h, SUM_FE, kind != FE_CHECK);
 }
 
 int sglm::absorbed_error(int64_t j) {

@@ -16,6 +16,7 @@ void sglm_engine::free_clusters(bool inner_too) {
   dev_free({&dR, &dP});
   free_fe();
   free_fe2();
+  free_gee();
   cl_levels.clear();
   cl_G = 0;
   cl_nseg = cl_ntiles = 0;
@@ -241,11 +242,11 @@ int sglm_engine::cluster_sync() {
 // S summed over the handle's shards or ranks, a plain sum that leaves every rank (a group: shard 0)
 // with bitwise the same S: the group's RCCL all-reduce or its host sum in shard order, the engine's
 // RCCL communicator, or the caller's all-reduce on device or host buffers.
-int sglm::sum_cluster_scores(sglm_engine* h, bool fe) {
+int sglm::sum_cluster_scores(sglm_engine* h, int which) {
   const std::vector<sglm_engine*>& shards = h->shards();
   sglm_engine* s0 = shards[0];
-  const int64_t len = fe ? s0->fe_len() : s0->cluster_len();
-  auto buf = [fe](sglm_engine* s) { return fe ? s->dfg : s->cl_inner->dX; };
+  const int64_t len = which == SUM_GEE ? s0->gee_len() : which == SUM_FE ? s0->fe_len() : s0->cluster_len();
+  auto buf = [which](sglm_engine* s) { return which == SUM_GEE ? s->dgg : which == SUM_FE ? s->dfg : s->cl_inner->dX; };
   if (h->group()) {
     const int D = (int)shards.size();
     if (!h->gcomms.empty()) {

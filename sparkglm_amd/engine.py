@@ -51,6 +51,18 @@ class FitFE:
 
 
 @dataclass
+class FitGEE:
+    """sglm_fit_glm_gee: the fit of beta (stderr: the model-based sqrt(diag(inv(A))), unscaled), rho and the scale
+    phi at the returned coefficients, the rows and the groups of positive prior weight, the largest group."""
+    fit: FitGLM
+    rho: float
+    phi: float
+    N: float
+    G_eff: int
+    n_max: int
+
+
+@dataclass
 class FitFE2:
     """sglm_fit_glm_fe2: the fit of beta, the effects alpha [G] and gamma [H] (NaN: a level without weight;
     gamma is 0 at the lowest factor-2 code of every component), the sweeps (last iteration, total), the levels
@@ -114,6 +126,16 @@ def glm_opts(family="binomial", link="logit", tol=1e-6, verbose=False, max_iter=
         raise L.IllegalArgumentException(f"requirement failed: unknown link {link!r}")
     return L.GlmOpts(L.FAMILIES[fam], L.LINKS[link], float(tol), int(bool(verbose)), int(max_iter),
                      L.INIT_MULTIPLE if init == "multiple" else L.INIT_SINGLE, int(npart))
+
+
+def gee_opts(corstr="exchangeable", rho=None):
+    """sglm_gee_opts: the working correlation and, with `rho` given, its fixed value."""
+    if corstr not in L.CORSTRS:
+        raise L.IllegalArgumentException(f"requirement failed: corstr must be one of {sorted(L.CORSTRS)}, "
+                                         f"got {corstr!r}")
+    if rho is not None and not (np.isfinite(rho) and rho < 1.0):
+        raise L.IllegalArgumentException(f"requirement failed: a fixed rho is finite and below 1 (got {rho!r})")
+    return L.GeeOpts(L.CORSTRS[corstr], int(rho is not None), 0.0 if rho is None else float(rho))
 
 
 class Engine:
@@ -584,6 +606,59 @@ class Engine:
         t = [C.c_double() for _ in range(4)]
         L.check(self._lib.sglm_get_fe_ms(self._h, *[C.byref(v) for v in t]), "sglm_get_fe_ms")
         return tuple(v.value for v in t)
+
+    # ---- GEE: an exchangeable working correlation over the factor of set_clusters ----
+    def fit_glm_gee(self, family="poisson", link="log", corstr="exchangeable", rho=None, tol=1e-6, verbose=False,
+                    max_iter=0, init="single", npart=0, max_trace=512) -> FitGEE:
+        """The population-averaged GLM by generalized estimating equations (sglm_fit_glm_gee;
+        geepack::geeglm): corstr "exchangeable" (rho estimated by moments at every step, or fixed at `rho`) or
+        "independence" (every iterate is fit_glm's).  fit.stderr is the model-based sqrt(diag(inv(A))), unscaled;
+        vcov_gee has the robust covariance."""
+        o = glm_opts(family, link, tol, verbose, max_iter, init, npart)
+        g = gee_opts(corstr, rho)
+        pre, fit = self._pre(max_trace)
+        info = L.GeeInfo()
+        L.check(self._lib.sglm_fit_glm_gee(self._h, C.byref(o), C.byref(g), C.byref(pre), C.byref(info)),
+                "sglm_fit_glm_gee")
+        return FitGEE(fit(), info.rho, info.phi, info.N, info.G_eff, info.n_max)
+
+    def gee_pass(self, beta=None, family="poisson", link="log", corstr="exchangeable", rho=None, init="single",
+                 sums=True):
+        """One GEE step at beta (sglm_gee_pass): dict(A, b, s [G x p], t, n, E, Q [G], moments [5] = sum E_g^2,
+        sum Q_g, sum n_g (n_g - 1) / 2, N, n_max; scalars, rho).  beta=None: the initial mode, rho = 0.
+        sums=False: without s, t, n, E, Q -- the G (p + 4) group sums are not copied to the host."""
+        o = glm_opts(family, link, init=init)
+        g = gee_opts(corstr, rho)
+        p, G = self.p, self._G()
+        A, b, s, mom = np.zeros((p, p), order="F"), np.zeros(p), np.zeros(L.NS), np.zeros(5)
+        grp = np.zeros(max(G, 1) * (p + 4)) if sums else None
+        used = C.c_double()
+        bb = None if beta is None else self._beta(beta)
+        L.check(self._lib.sglm_gee_pass(self._h, C.byref(o), C.byref(g), L.ptr(bb), A.ctypes.data_as(L.dp), L.ptr(b),
+                                        L.ptr(grp), L.ptr(mom), L.ptr(s), C.byref(used)), "sglm_gee_pass")
+        if not sums:
+            return dict(A=A, b=b, moments=mom, scalars=s, rho=used.value)
+        col = lambda k: grp[G * (p + k): G * (p + k + 1)].copy()
+        return dict(A=A, b=b, s=grp[: G * p].reshape((G, p), order="F"), t=col(0), n=col(1), E=col(2), Q=col(3),
+                    moments=mom, scalars=s, rho=used.value)
+
+    def vcov_gee(self, beta, rho, family="poisson", link="log", corstr="exchangeable", robust=True, cadjust=False,
+                 return_meat=False):
+        """The covariance of beta at (beta, rho) of a GEE fit (sglm_vcov_gee): robust, inv(A) M inv(A) with the
+        meat over the clusters (what geepack / Stata / statsmodels print; `cadjust` a further G / (G - 1)), or
+        with robust=False the model-based phi inv(A)."""
+        o = glm_opts(family, link)
+        g = gee_opts(corstr, None)
+        b = self._beta(beta)
+        return self._cov_meat(return_meat, "sglm_vcov_gee", lambda cov, meat: self._lib.sglm_vcov_gee(
+            self._h, C.byref(o), C.byref(g), L.ptr(b), float(rho), int(bool(robust)), int(bool(cadjust)), cov, meat))
+
+    def gee_ms(self):
+        """Kernel times (rows, segment sums, combine, the Gram pass over the group sums) of the last GEE step
+        (HIP events)."""
+        t = np.zeros(4)
+        L.check(self._lib.sglm_get_gee_ms(self._h, L.ptr(t)), "sglm_get_gee_ms")
+        return tuple(float(v) for v in t)
 
     # ---- two-way fixed effects: a second factor beside the one of set_clusters ----
     def set_fe2(self, ids, H=None):

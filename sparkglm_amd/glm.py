@@ -106,6 +106,12 @@ class GLMModel:
     fixef2: Optional[dict] = None
     fe_ncomp: int = 0
     fe_sweeps: Optional[tuple] = None
+    # GLM.fit_gee only: the working correlation ("exchangeable" | "independence"), its rho, the scale phi and the
+    # model-based standard errors sqrt(phi diag(inv(A))); stdErr holds the robust ones and aic is None
+    corstr: Optional[str] = None
+    rho: Optional[float] = None
+    scale: Optional[float] = None
+    naive_se: Optional[List[float]] = None
 
     def predict(self, newData: Frame, type: str = "response", offset: Optional[Frame] = None,
                 m: Optional[Frame] = None, device: int = 0, cov=None, dispersion: Optional[float] = None,
@@ -216,6 +222,17 @@ def _nb_summary(text: str, obj, lib) -> str:
     text, k = re.subn(r"^AIC: .*$", lambda _: aic + "\n" + th, text, count=1, flags=re.M)
     if k != 1:
         raise RuntimeError("sglm_glm_summary printed no 'AIC: ' line to carry the negative binomial's AIC and theta")
+    return text
+
+
+def _gee_summary(text: str, obj, lib) -> str:
+    """GLM.summary's text for a GLM.fit_gee model: there is no likelihood, so the AIC line gives way to the
+    working correlation and the scale (the anchor is sglm_glm_summary's own line, as in _nb_summary)."""
+    lines = (f"Correlation ({obj.corstr}): " + L.java_double_str(lib.sglm_sig_digits(float(obj.rho), 6)) +
+             "\nScale: " + L.java_double_str(lib.sglm_sig_digits(float(obj.scale), 6)))
+    text, k = re.subn(r"^AIC: .*$", lambda _: lines, text, count=1, flags=re.M)
+    if k != 1:
+        raise RuntimeError("sglm_glm_summary printed no 'AIC: ' line to replace with the GEE's correlation and scale")
     return text
 
 
@@ -492,6 +509,57 @@ class GLM:
         return obj
 
     @staticmethod
+    def _gee_engine(y, x, cluster, fam, lnk, offset, m, prior, theta, device, xnames=None) -> Engine:
+        _check_inputs(y, x)
+        for extra in (offset, m, prior):
+            if extra is not None:
+                _require(extra.count() == y.count(), "The two DataFrames must have the same number of rows")
+        eng = _engine(device)
+        if fam == "negbin":
+            _require(theta is not None, "family negbin needs theta")
+            eng.set_theta(theta)
+        eng.set_data((x if xnames is None else x.select(*xnames)).to_matrix(), y.to_vector(),
+                     None if m is None else m.to_vector(), None if offset is None else offset.to_vector(),
+                     None if prior is None else prior.to_vector())
+        _set_clusters(eng, cluster, y.count())
+        return eng
+
+    @staticmethod
+    def fit_gee(y: Frame, x: Frame, cluster: Frame, family: str = "poisson", link: str = "log",
+                corstr: str = "exchangeable", rho: Optional[float] = None, offset: Frame = None, m: Frame = None,
+                prior: Frame = None, tol: float = 1e-6, verbose: bool = False, theta: Optional[float] = None,
+                device: int = 0) -> GLMModel:
+        """Extension: the population-averaged fit by generalized estimating equations (Liang & Zeger;
+        geepack::geeglm(id = cluster, corstr =), Stata xtgee, statsmodels GEE).  `cluster` holds one column of
+        labels of any dtype; `corstr` "exchangeable" (rho estimated by moments, or fixed at `rho`) or
+        "independence".  The model carries `rho`, `scale` (phi), `corstr`, stdErr = the robust standard errors
+        (what those packages print), `naive_se` = sqrt(phi diag(inv(A))), and aic = None: there is no
+        likelihood.  GLM.vcov_gee, coeftest(gee=), summary and predict work on it."""
+        fam, lnk = ("negbin", link) if family.lower() == "negbin" else _engine_family_link(family, link)
+        eng = GLM._gee_engine(y, x, cluster, fam, lnk, offset, m, prior, theta, device)
+        r = eng.fit_glm_gee(fam, lnk, corstr=corstr, rho=rho, tol=tol, verbose=verbose)
+        V = eng.vcov_gee(r.fit.coefs, r.rho, fam, lnk, corstr=corstr)
+        obj = GLM.createObj(x, y, _to_pre(r.fit), family, link)
+        obj.naive_se = list(np.sqrt(r.phi) * r.fit.stderr)
+        obj.stdErr = list(np.sqrt(np.diag(V)))
+        obj.corstr, obj.rho, obj.scale, obj.aic = corstr, r.rho, r.phi, None
+        if fam == "negbin":
+            obj.theta = float(theta)
+        return obj
+
+    @staticmethod
+    def vcov_gee(obj: GLMModel, y: Frame, x: Frame, cluster: Frame, offset: Frame = None, m: Frame = None,
+                 prior: Frame = None, device: int = 0, robust: bool = True, cadjust: bool = False) -> np.ndarray:
+        """Extension: the covariance of a GLM.fit_gee model's coefficients on its estimation data at the
+        model's rho: robust (the sandwich over the clusters; `cadjust` a further G / (G - 1)), or with
+        robust=False the model-based phi inv(A).  Final either way."""
+        _require(getattr(obj, "corstr", None) is not None, "GLM.vcov_gee takes a GLM.fit_gee model")
+        fam, lnk = _model_family_link(obj)
+        eng = GLM._gee_engine(y, x, cluster, fam, lnk, offset, m, prior, obj.theta, device, obj.xnames)
+        beta = np.asarray(obj.coefs, dtype=np.float64).reshape(-1)
+        return eng.vcov_gee(beta, obj.rho, fam, lnk, corstr=obj.corstr, robust=robust, cadjust=cadjust)
+
+    @staticmethod
     def _fe_data(y, x, fe, family, link, offset, m, prior, drop_uninformative, quiet=False) -> FeData:
         """The arrays of a fixed-effects fit: the intercept removed, the labels coded, uninformative groups
         dropped."""
@@ -658,12 +726,22 @@ class GLM:
     @staticmethod
     def coeftest(obj: GLMModel, y: Frame, x: Frame, offset: Frame = None, m: Frame = None, prior: Frame = None,
                  device: int = 0, type: str = "HC3", cluster: Frame = None, cadjust: bool = True,
-                 fe: Frame = None, fe2: Frame = None) -> Frame:
+                 fe: Frame = None, fe2: Frame = None, gee: Frame = None) -> Frame:
         """Extension: lmtest::coeftest(fit, vcov. = vcovHC(fit, type)) -- name, estimate, robust
         standard error sqrt(diag V), z statistic and its two-sided normal p-value.  With `cluster` (one
         column of labels) the covariance is vcovCL(fit, cluster, type, cadjust) and `type` must be "HC0"
         or "HC1".  A GLM.fit_fe model takes its factor `fe` and is clustered on it by default (`type` "HC1"
-        unless "HC0" or "const" is given)."""
+        unless "HC0" or "const" is given).  A GLM.fit_gee model takes its cluster frame `gee`: z statistics on
+        the robust covariance (GLM.vcov_gee; `type` does not apply).  `cadjust` keeps this function's default, True
+        (vcovCL's), so the table's standard errors are sqrt(G / (G - 1)) times the model's stdErr, which
+        GLM.fit_gee and GLM.vcov_gee form without it as geepack and statsmodels do; cadjust=False gives stdErr."""
+        if gee is not None or getattr(obj, "corstr", None) is not None:
+            _require(gee is not None and getattr(obj, "corstr", None) is not None,
+                     "gee belongs to a GLM.fit_gee model, which needs it")
+            _require(cluster is None and fe is None, "a GEE model is clustered on its own factor gee")
+            V = GLM.vcov_gee(obj, y, x, gee, offset, m, prior, device, True, cadjust)
+            beta = np.asarray(obj.coefs, dtype=np.float64).reshape(-1)
+            return _coef_table(obj.xnames, beta, V, L.load().sglm_pval_normal)
         if fe is not None or getattr(obj, "fixef", None) is not None:
             _require(cluster is None, "a fixed-effects model is clustered on its own factor fe")
             t = type if type in ("const", "HC0", "HC1") else "HC1"
@@ -707,7 +785,9 @@ class GLM:
         lib.sglm_glm_summary(C.byref(s), len(obj.xnames), names, obj.yname.encode(), obj.family.encode(),
                              obj.link.encode(), buf, need)
         text = buf.value.decode()
-        if getattr(obj, "theta", None) is not None:  # GLM.fit_nb: theta, and the AIC that counts it when estimated
+        if getattr(obj, "corstr", None) is not None:  # GLM.fit_gee: no likelihood, the correlation and the scale
+            text = _gee_summary(text, obj, lib)
+        elif getattr(obj, "theta", None) is not None:  # GLM.fit_nb: theta, and the AIC that counts it when estimated
             text = _nb_summary(text, obj, lib)
         return text
 
