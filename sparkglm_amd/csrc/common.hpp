@@ -264,19 +264,28 @@ struct CombineArgs {
 };
 constexpr int CLUSTER_CHUNK = 64;  // rows one thread of the combine adds
 
-// Fixed-effects (within) IRLS over the cluster factor (fe.hip; fe.cpp).
-// fe_weights_kernel: one streaming read of the row vectors (never X), one value per row into `w` and two
-// sums per segment into Q [nseg][2], by kind:
+// The steps over the cluster factor: fixed-effects (within) IRLS (fe.hip; fe.cpp) and GEE with
+// an exchangeable working correlation (gee.hip; gee.cpp; K13).  Their row kernels share one tiling and one
+// argument block (segrows.hpp): one streaming read of the row vectors (never X), one value per row into `w` and
+// NQ sums per segment into Q [nseg][NQ], by kind.
+// fe_weights_kernel, NQ = 2:
 //   FE_WZ     w_i (the working weight) | sum w z, sum w     at eta (mode MODE_IRLS) or at mu0 (the init modes)
 //   FE_SCORE  u_i (the signed score)   | sum u,   0
 //   FE_CHECK  nothing                  | sum y,   sum (m - y)  (binomial; else the row count) over the rows of
 //                                        positive prior weight: the uninformative-group check
+// gee_rows_kernel, NQ = GEE_NQ: sum d z | rows of positive prior weight | sum e | sum e^2 --
+//   GEE_STEP   d_i = sqrt(w_i)                    at eta (mode MODE_IRLS) or at mu0 (the init modes)
+//   GEE_SCORE  d_i e_i = w_i (y_i - mu_i) g'(mu_i)  (the four sums are GEE_STEP's)
+//   GEE_COUNT  nothing; only the row counts are summed (no eta is read): the refusals before the first pass
+// e_i = d_i (y_i - mu_i) g'(mu_i), z_i the working response without the offset (rowmath.hpp working_wz).
 enum FeKind : int { FE_WZ = 0, FE_SCORE = 1, FE_CHECK = 2 };
-struct FeArgs {
+enum GeeKind : int { GEE_STEP = 0, GEE_SCORE = 1, GEE_COUNT = 2 };
+constexpr int GEE_NQ = 4;
+struct SegRowArgs {
   const double* y;
   const double* eta;         // eta of the last pass (offset included); not read in the init modes
   const double* m;           // may be null
-  const double* off;         // the effective offset o* = o + alpha_g (FE_WZ)
+  const double* off;         // FE: the effective offset o* = o + alpha_g; GEE: the rows' own, may be null
   const double* prior;       // may be null
   int64_t n, ld;             // rows; w is written up to ld (zeros past n)
   int family, link, mode, kind;
@@ -284,10 +293,10 @@ struct FeArgs {
   const int64_t* seg_start;  // the segments of sglm_set_clusters (ClusterArgs)
   const int64_t* tile_seg;
   int64_t ntiles;
-  double* w;                 // [ld]; null: not stored (FE_CHECK)
-  double* Q;                 // [nseg][2]
-  // the two values Q sums, per row [ld] (zeros past n and on rows of prior weight 0); null: not stored.
-  // va: w z | u | y; vb: w | 0 | m - y or 1.  The two-way fits sum them over factor 2's row lists.
+  double* w;                 // [ld]; null: not stored (FE_CHECK, GEE_COUNT)
+  double* Q;                 // [nseg][NQ]
+  // fe_weights_kernel: the two values Q sums, per row [ld] (zeros past n and on rows of prior weight 0); null:
+  // not stored.  va: w z | u | y; vb: w | 0 | m - y or 1.  The two-way fits sum them over factor 2's row lists.
   double* va;
   double* vb;
 };
@@ -301,61 +310,27 @@ struct FeOffsetArgs {
   int64_t ntiles, n, ld;
   double* out;               // [ld]
 };
-// The group sums as one buffer (one all-reduce): S [ld x p] col-major | t [ld] | W [ld], ld = G rounded up to 32.
+// The group sums as one buffer (one all-reduce), ld = G rounded up to 32, col-major: FE S [ld x p] | t | W; GEE
+// s [ld x p] | t | n | E | Q.  The kernels over its G rows share one argument block.
 // fe_alpha_kernel: alpha_g += (t_g - s_g' beta) / W_g where W_g > 0.
 // fe_scale_kernel: the design X [ld x p] and response y [ld] of the Gram pass over the groups --
 //   meat = 0: x_g = s_g / sqrt(W_g), y_g = t_g / sqrt(W_g)        (X'X = sum s s' / W, X'y = sum s t / W)
-//   meat = 1: x_g = S_g - U_g s_g / W_g, y_g = 0; S | U from `grp`, s | W from `grp_w`
+//   meat = 1: x_g = S_g - U_g s_g / W_g, y_g = 0; S | U from `grp`, s | W from `grp2`
 // rows with W_g = 0 (or not > 0): exact zeros.
-struct FeGroupArgs {
-  const double* grp;
-  const double* grp_w;
-  int64_t G, ld;
-  int p, meat;
-  const double* beta;        // device [p] (fe_alpha_kernel)
-  double* alpha;             // [G]
-  double* X;
-  double* y;
-};
-
-// GEE fits with an exchangeable working correlation over the cluster factor (gee.hip; gee.cpp).
-// gee_rows_kernel: fe_weights_kernel's tiling; one value per row into `d` and four sums per segment into
-// Q [nseg][GEE_NQ] = sum d z | rows of positive prior weight | sum e | sum e^2, by kind:
-//   GEE_STEP   d_i = sqrt(w_i)                    at eta (mode MODE_IRLS) or at mu0 (the init modes)
-//   GEE_SCORE  d_i e_i = w_i (y_i - mu_i) g'(mu_i)  (the four sums are GEE_STEP's)
-//   GEE_COUNT  nothing; only the row counts are summed (no eta is read): the refusals before the first pass
-// e_i = d_i (y_i - mu_i) g'(mu_i), z_i the working response without the offset (rowmath.hpp working_wz).
-enum GeeKind : int { GEE_STEP = 0, GEE_SCORE = 1, GEE_COUNT = 2 };
-constexpr int GEE_NQ = 4;
-struct GeeArgs {
-  const double* y;
-  const double* eta;         // eta of the last pass (offset included); not read in the init modes
-  const double* m;           // may be null
-  const double* off;         // may be null
-  const double* prior;       // may be null
-  int64_t n, ld;             // rows; d is written up to ld (zeros past n)
-  int family, link, mode, kind;
-  double mu0, theta;
-  const int64_t* seg_start;  // the segments of sglm_set_clusters (ClusterArgs)
-  const int64_t* tile_seg;
-  int64_t ntiles;
-  double* d;                 // [ld]; null: not stored (GEE_COUNT)
-  double* Q;                 // [nseg][GEE_NQ]
-};
-// The group sums as one buffer (one all-reduce): s [ld x p] col-major | t | n | E | Q, ld = G rounded up to 32.
 // gee_moments_kernel: per-block partials [grid][NS] of GeeMoment over the G rows (M_NMAX a maximum).
-// gee_scale_kernel: c_g = rho / (1 - rho + n_g rho); the design X [ld x p] and response y [ld] of the Gram
-// pass over the groups --
+// gee_scale_kernel: c_g = rho / (1 - rho + n_g rho); X and y of the Gram pass --
 //   meat = 0: x_g = sqrt(|c_g|) s_g, y_g = sqrt(|c_g|) t_g       (sign(c_g) = sign(rho): applied on the host)
-//   meat = 1: x_g = (S1_g - c_g E_g s_g) / (1 - rho), y_g = 0; S1 from `grp`, s | n | E from `grp_s`
+//   meat = 1: x_g = (S1_g - c_g E_g s_g) / (1 - rho), y_g = 0; S1 from `grp`, s | n | E from `grp2`
 // rows with n_g = 0: exact zeros.
 enum GeeMoment : int { M_E2 = 0, M_Q = 1, M_PAIRS = 2, M_N = 3, M_NMAX = 4, M_GEFF = 5, GEE_NM = 6 };
-struct GeeGroupArgs {
+struct GroupArgs {
   const double* grp;
-  const double* grp_s;
+  const double* grp2;        // the step's own sums beside the score-weighted ones in grp (the scale kernels)
   int64_t G, ld;
   int p, meat;
-  double rho;
+  double rho;                // gee_scale_kernel
+  const double* beta;        // device [p] (fe_alpha_kernel)
+  double* alpha;             // [G] (fe_alpha_kernel)
   double* X;
   double* y;
   double* partials;          // gee_moments_kernel: [grid][NS]
@@ -365,7 +340,7 @@ struct GeeGroupArgs {
 // Factor 2's rows are listed per level in ascending order (a stable counting sort by code) and each level's
 // list is cut into chunks of FE2_CHUNK positions; the chunks, already ordered by level, feed combine_kernel.
 constexpr int FE2_CHUNK = 128;
-// The per-row values it sums (w z and w; y and m - y for the check) are fe_weights_kernel's (FeArgs::va, vb).
+// The per-row values it sums (w z and w; y and m - y for the check) are fe_weights_kernel's (SegRowArgs::va, vb).
 // fe2_list_sum_kernel: R[k, j] = sum_{q in chunk k} v[row] X[row, j] (j < p), r0[row] (j = p), r1[row]
 // (j = p + 1), row = list[q], positions in ascending order.  p = 0: only the two row vectors are summed.
 struct Fe2ListSumArgs {

@@ -1,6 +1,8 @@
 // engine.hpp -- the HIP engine behind the C ABI: what its host translation units share.
-// Private to engine.cpp, negbin.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp, fe.cpp, gee.cpp and ingest.cpp; never included
-// by a .hip file.
+// Private to engine.cpp, negbin.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp, fe.cpp, fe2.cpp,
+// gee.cpp and ingest.cpp; never included by a .hip file.  The steps over the cluster factor (fixed effects, two-way,
+// GEE) share one state per step kind (sglm_engine::GroupSums) and one frame (fe.cpp: group_sums_local,
+// group_sums_finish, group_gram; StepBackend and drive_step_fit below).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -10,6 +12,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <functional>
 #include <initializer_list>
 #include <memory>
 #include <string>
@@ -282,25 +285,25 @@ struct sglm_engine : public sglm::Backend {
   int64_t cl_segcl_off = 0;                       // offset in dclidx of seg_cluster [nseg]
   const double* off_override = nullptr;           // while set, the pass reads its offset here (o* = o + alpha_g)
   double *dfo = nullptr, *dalpha = nullptr;       // o* [n_pad]; alpha [G]
-  double *dfq = nullptr, *dfqp = nullptr;         // per-segment scalar sums [nseg][2]; their combine scratch [cl_prow][2]
-  // the group sums S | t | W (common.hpp FeGroupArgs), summed over shards and ranks in place; dfg2: the
-  // w-weighted sums kept while sglm_vcov_fe forms the u-weighted ones
-  double *dfg = nullptr, *dfg2 = nullptr;
-  bool fe_stale = true;                           // dfg may hold other shards' sums: zero it before the combine
-  hipEvent_t evf[2] = {nullptr, nullptr};
-  // kernel times of the last FE step: weights, segment sums, combine, Gram over the group sums (-1: none yet)
-  double fe_ms[4] = {-1.0, -1.0, -1.0, -1.0};
+  // What a step over the cluster factor keeps on a shard, the fixed-effects and the GEE steps each their own (so
+  // the results of one stay bitwise what they were beside the other): nq scalar columns follow the p of the sums.
+  struct GroupSums {
+    int nq;                                       // fe: 2 (t | W); gee: GEE_NQ (t | n | E | Q)
+    double *q = nullptr, *qp = nullptr;           // per-segment scalar sums [nseg][nq]; their combine scratch [cl_prow][nq]
+    // the group sums [G rounded up to 32][p + nq] (common.hpp GroupArgs), summed over shards and ranks in place;
+    // g2: the step's sums kept while sglm_vcov_fe / sglm_vcov_gee form the score-weighted ones
+    double *g = nullptr, *g2 = nullptr;
+    bool stale = true;                            // g may hold other shards' sums: zero it before the combine
+    hipEvent_t ev[2] = {nullptr, nullptr};        // the row kernel
+    // kernel times of the last step: row kernel, segment sums, combine, Gram over the group sums (-1: none yet)
+    double ms[4] = {-1.0, -1.0, -1.0, -1.0};
+  };
+  GroupSums fe{2};
 
   // ---- GEE with an exchangeable working correlation over the cluster factor (gee.hip; gee.cpp):
-  // sglm_fit_glm_gee / sglm_gee_pass / sglm_vcov_gee.  Buffers of its own, so the fixed-effects sums keep theirs.
-  double *dgq = nullptr, *dgqp = nullptr;         // per-segment scalar sums [nseg][GEE_NQ]; their combine scratch
-  // the group sums s | t | n | E | Q (common.hpp GeeGroupArgs), summed over shards and ranks in place; dgg2: the
-  // step's sums kept while sglm_vcov_gee forms the score-weighted ones; dgm: moment partials [GEE_MOMENT_BLOCKS][NS] | out [NS]
-  double *dgg = nullptr, *dgg2 = nullptr, *dgm = nullptr;
-  bool gee_stale = true;                          // dgg may hold other shards' sums: zero it before the combine
-  hipEvent_t evg[2] = {nullptr, nullptr};
-  // kernel times of the last GEE step: rows, segment sums, combine, Gram over the group sums (-1: none yet)
-  double gee_ms[4] = {-1.0, -1.0, -1.0, -1.0};
+  // sglm_fit_glm_gee / sglm_gee_pass / sglm_vcov_gee.  dgm: moment partials [GEE_MOMENT_BLOCKS][NS] | out [NS]
+  GroupSums gee{sglm::GEE_NQ};
+  double* dgm = nullptr;
 
   // ---- two-way fixed effects (fe2.hip; fe2.cpp): the second factor of sglm_set_fe2, its row lists, the
   // level matrices of the sweeps and their scratch; dropped with the clusters ----
@@ -431,18 +434,26 @@ struct sglm_engine : public sglm::Backend {
   int cluster_sync();
   int64_t cluster_len() const { return cl_inner->n_pad * p; }  // doubles of S, padding included
 
-  // ---- fe.cpp ----
+  // ---- fe.cpp: the one-way fixed effects, and the group sums they share with the GEE fits ----
   void free_fe();
   int fe_prepare();
-  int64_t fe_len() const { return cl_inner->n_pad * (p + 2); }  // doubles of S | t | W, padding included
   // effects [L] to dst on this device; a NaN (a level without weight) is read as 0; null: zeros
   int set_effects(double* dst, const double* src, int64_t L);
   int fe_offset_local();
-  // va, vb: where the kernel stores the two per-row values it sums (common.hpp FeArgs), or null
+  // va, vb: where the kernel stores the two per-row values it sums (common.hpp SegRowArgs), or null
   int fe_sums_local(int kind, int mode, int family, int link, double mu0, double* va = nullptr, double* vb = nullptr);
   int fe_sync();
-  // the shared tail of fe_sums_local / gee_sums_local: segment sums of u x and the scalar columns through the combine
-  int group_combine_local(bool rows, const double* Q, double* Qp, int ncol, double* grp);
+  int64_t group_len(const GroupSums& gs) const { return cl_inner->n_pad * (p + gs.nq); }  // doubles of g, padding included
+  void free_group(GroupSums& gs);
+  int group_prepare(GroupSums& gs);  // the buffers of a step on this shard (kept until the clusters or the data change)
+  // The row values of a kind and this shard's group sums into gs.g, enqueued on the stream: the row kernel (`launch`
+  // of launch_fe_weights / launch_gee_rows, reading the offset `off`), with `rows` the segment sums of u x (u:
+  // domega) through the combine tree into the first p columns, then the kernel's nq per-segment scalars through
+  // the same tree into the columns after them (evcl[2] to evcl[3] spans both trees)
+  using RowLaunch = hipError_t (*)(const sglm::SegRowArgs&, int, hipStream_t, hipEvent_t, hipEvent_t);
+  int group_sums_local(GroupSums& gs, RowLaunch launch, bool rows, int kind, int mode, int family, int link, double mu0,
+                       const double* off, double* va, double* vb);
+  int keep_group_sums(GroupSums& gs);  // g into g2 (allocated when first asked for), enqueued
 
   // ---- fe2.cpp ----
   void free_fe2();
@@ -450,8 +461,7 @@ struct sglm_engine : public sglm::Backend {
   // ---- gee.cpp ----
   void free_gee();
   int gee_prepare();
-  int64_t gee_len() const { return cl_inner->n_pad * (p + sglm::GEE_NQ); }  // doubles of s | t | n | E | Q, padding included
-  // the row values of `kind` (common.hpp GeeKind) and this shard's group sums into dgg: enqueued on the stream
+  // the row values of `kind` (common.hpp GeeKind) and this shard's group sums into gee.g: enqueued on the stream
   int gee_sums_local(int kind, int mode, int family, int link, double mu0);
 };
 
@@ -469,10 +479,10 @@ inline int check_handle(sglm_engine* h) {
 // The number of clusters every shard (and every rank: one small all-reduce) declared; SGLM_EINVAL
 // on every rank when they differ or none are set.
 int cluster_count(sglm_engine* h, int32_t* G);
-// The cluster sums S (SUM_FE: the group sums S | t | W, sglm_engine::dfg; SUM_GEE: s | t | n | E | Q, dgg) summed
-// in place over the handle's shards or ranks; every rank (a group: shard 0) ends with bitwise the same sums.
-enum GroupSumBuffer : int { SUM_CLUSTER = 0, SUM_FE = 1, SUM_GEE = 2 };
-int sum_cluster_scores(sglm_engine* h, int which = SUM_CLUSTER);
+// A buffer of `len` doubles that every shard holds (buf(shard): the cluster sums S, cl_inner->dX and cluster_len();
+// a step's group sums, GroupSums::g and group_len()) summed in place over the handle's shards or ranks; every rank
+// (a group: shard 0) ends with bitwise the same sums.
+int sum_cluster_scores(sglm_engine* h, const std::function<double*(sglm_engine*)>& buf, int64_t len);
 // The combine tree's plan.  An open range is a destination row of S and the positions [lo, hi) it owns in the
 // level's input (ascending, contiguous).  A range is cut into chunks of CLUSTER_CHUNK positions.  One chunk: it is
 // summed into S and the range is done.  Several: each is summed into a row of the scratch, and those rows are
@@ -498,13 +508,34 @@ int clustered_finish(int hc_type, double nrows, int64_t p, int64_t absorbed, int
                      const std::vector<double>& C, const std::vector<double>& M, const char* at, double* cov,
                      double* meat);
 
-// ---- fe.cpp: what the two-way fixed-effects fits (fe2.cpp) share with the one-way ones ----
-// what every fixed-effects entry point requires, before any launch; the buffers of a step
-// (which: SUM_FE, or SUM_GEE for the GEE fits' buffers and wording)
-int fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G, int which = SUM_FE);
-// after every shard's local sums of a step were enqueued (fe_sums_local / gee_sums_local): synchronise, take the
-// kernel times (fe_ms / gee_ms; rows: the segment sums and the combine too), sum over shards and ranks
-int group_sums_finish(sglm_engine* h, int which, bool rows);
+// ---- fe.cpp: what the two-way fixed-effects fits (fe2.cpp) and the GEE fits (gee.cpp) share with the one-way ones ----
+// what every entry point of a step requires, before any launch, and the buffers of the step (`prepare`, on every
+// shard); `needs` opens the refusal of a handle off the fused / narrow path
+int fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G, const char* needs = "a fixed-effects fit needs",
+             int (sglm_engine::*prepare)() = &sglm_engine::fe_prepare);
+// which of a shard's sums a step works on: &sglm_engine::fe or &sglm_engine::gee
+using GroupSumsOf = sglm_engine::GroupSums sglm_engine::*;
+// after every shard's local sums of a step were enqueued (group_sums_local): synchronise, take the kernel times
+// (GroupSums::ms, the slowest shard; rows: the segment sums and the combine too), sum over shards and ranks
+int group_sums_finish(sglm_engine* h, GroupSumsOf gs, bool rows);
+// The group rows of shard 0 scaled into its internal engine (`scale`: launch_fe_scale / launch_gee_scale, at rho;
+// meat: the score-weighted sums in g beside the step's in g2) and that engine's LM Gram pass: packed [packed_len(p)]
+int group_gram(sglm_engine* h, GroupSumsOf gs, hipError_t (*scale)(const GroupArgs&, hipStream_t), bool meat, double rho,
+               double* packed);
+// A fit's Backend whose pass is a step over the handle (fixed effects, two-way, GEE): everything else is the handle's
+struct StepBackend : public Backend {
+  sglm_engine* h;
+  explicit StepBackend(sglm_engine* handle) : h(handle) {}
+  int64_t ncols() const override { return h->ncols(); }
+  int npart() const override { return h->npart(); }
+  int global_sums(double* out2) override { return h->global_sums(out2); }
+  int stats(int mode, const double* beta, double mu0, double ybar, int family, int link, double* s) override {
+    return h->stats(mode, beta, mu0, ybar, family, link, s);
+  }
+  std::unique_ptr<SolverIface> make_solver(int64_t p) override { return h->make_solver(p); }
+};
+// glm_drive over such a backend; the solves' time and path into the handle
+int drive_step_fit(StepBackend& be, const sglm_glm_opts& opts, sglm_preglm* out);
 // While it lives every IRLS pass of the handle's shards stores eta; at its end the passes read the shards'
 // own offsets again.
 struct FeScope {
@@ -519,7 +550,7 @@ struct FeScope {
     }
   }
 };
-// the group sums of `kind` (common.hpp FeKind) over the cluster factor into shard 0's dfg, synchronised;
+// the group sums of `kind` (common.hpp FeKind) over the cluster factor into shard 0's fe.g, synchronised;
 // va, vb as sglm_engine::fe_sums_local
 int fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0, double* va = nullptr,
                   double* vb = nullptr);

@@ -13,7 +13,11 @@
 // the fixed effects move by alpha += (t - s' beta+) / W (fe_alpha_kernel) at the start of the next pass,
 // when beta+ is known.
 //
-// What the two-way fits (fe2.cpp) share is here too: the frame of a step entry point (fe_step_mode,
+// What the two-way fits (fe2.cpp) and the GEE fits (gee.cpp) share is here too.  The host frame of a step over
+// the cluster factor, written once over the sglm_engine::GroupSums it works on (fe or gee): group_prepare /
+// free_group, group_sums_local (stale clear, row kernel, both combine trees), group_sums_finish (times, the sum
+// over shards and ranks), group_gram (scale launch, the internal engine's Gram pass), keep_group_sums, and
+// drive_step_fit over a StepBackend.  The frame of a step entry point (fe_check, fe_step_mode,
 // fe_unpack_step), the bread (fe_bread), the downloads and scans of level buffers, FeScope (engine.hpp).
 // The refusals and the finish of a clustered covariance are vcov_cluster.cpp's.
 #include <algorithm>
@@ -28,41 +32,52 @@ using namespace sglm;
 // A column whose within-group weighted sum of squares A_jj is below FE_ABSORBED_RATIO (engine.hpp) of X'WX_jj
 // is constant within every group (an intercept among them): absorbed by the fixed effects, A is singular.
 
-void sglm_engine::free_fe() {
-  dev_free({&dfo, &dalpha, &dfq, &dfqp, &dfg, &dfg2});
-  off_override = nullptr;
-  fe_stale = true;
-  for (hipEvent_t& e : evf) {
+void sglm_engine::free_group(GroupSums& gs) {
+  dev_free({&gs.q, &gs.qp, &gs.g, &gs.g2});
+  gs.stale = true;
+  for (hipEvent_t& e : gs.ev) {
     if (e) (void)hipEventDestroy(e);
     e = nullptr;
   }
 }
 
-// The buffers of a fixed-effects step on this shard (kept until the clusters or the data change)
-int sglm_engine::fe_prepare() {
+void sglm_engine::free_fe() {
+  dev_free({&dfo, &dalpha});
+  off_override = nullptr;
+  free_group(fe);
+}
+
+int sglm_engine::group_prepare(GroupSums& gs) {
   HIPCHK(hipSetDevice(device));
   if (int rc = check_loaded()) return rc;
   if (int rc = ensure_cl_inner()) return rc;
   if (int rc = grow(domega, omega_cap, n_pad, "hipMalloc(working weights)")) return rc;
   for (hipEvent_t& e : evcl)
     if (!e) HIPCHK(hipEventCreate(&e));
-  for (hipEvent_t& e : evf)
+  for (hipEvent_t& e : gs.ev)
     if (!e) HIPCHK(hipEventCreate(&e));
+  const size_t d = sizeof(double);
+  if (!gs.q)
+    if (int rc = dev_alloc(&gs.q, d * (size_t)std::max<int64_t>(gs.nq * cl_nseg, 1), "hipMalloc(segment scalar sums)"))
+      return rc;
+  if (!gs.qp && cl_prow > 0)
+    if (int rc = dev_alloc(&gs.qp, d * (size_t)(gs.nq * cl_prow), "hipMalloc(scalar combine scratch)")) return rc;
+  if (!gs.g) {
+    if (int rc = dev_alloc(&gs.g, d * (size_t)group_len(gs), "hipMalloc(group sums)")) return rc;
+    gs.stale = true;
+  }
+  return SGLM_OK;
+}
+
+// The buffers of a fixed-effects step on this shard
+int sglm_engine::fe_prepare() {
+  if (int rc = group_prepare(fe)) return rc;
   const size_t d = sizeof(double);
   if (!dfo)
     if (int rc = dev_alloc(&dfo, d * (size_t)n_pad, "hipMalloc(effective offset)")) return rc;
-  if (!dfq)
-    if (int rc = dev_alloc(&dfq, d * (size_t)std::max<int64_t>(2 * cl_nseg, 1), "hipMalloc(segment scalar sums)"))
-      return rc;
-  if (!dfqp && cl_prow > 0)
-    if (int rc = dev_alloc(&dfqp, d * (size_t)(2 * cl_prow), "hipMalloc(scalar combine scratch)")) return rc;
   if (!dalpha) {
     if (int rc = dev_alloc(&dalpha, d * (size_t)cl_G, "hipMalloc(fixed effects)")) return rc;
     HIPCHK(hipMemsetAsync(dalpha, 0, d * (size_t)cl_G, st));
-  }
-  if (!dfg) {
-    if (int rc = dev_alloc(&dfg, d * (size_t)fe_len(), "hipMalloc(group sums)")) return rc;
-    fe_stale = true;
   }
   return SGLM_OK;
 }
@@ -95,20 +110,20 @@ int sglm_engine::fe_offset_local() {
   return SGLM_OK;
 }
 
-// The row values of `kind` (common.hpp FeKind) and this shard's group sums into dfg: enqueued on the stream
-int sglm_engine::fe_sums_local(int kind, int mode, int family, int link, double mu0, double* va, double* vb) {
+int sglm_engine::group_sums_local(GroupSums& gs, RowLaunch launch, bool rows, int kind, int mode, int family, int link,
+                                  double mu0, const double* off, double* va, double* vb) {
   HIPCHK(hipSetDevice(device));
   // as S of the cluster-robust covariance: the combine rewrites the rows of the groups that have a segment
   // here and no others, so the buffer is cleared after every cross-shard sum that landed in it
-  if (fe_stale) {
-    HIPCHK(hipMemsetAsync(dfg, 0, sizeof(double) * (size_t)fe_len(), st));
-    fe_stale = false;
+  if (gs.stale) {
+    HIPCHK(hipMemsetAsync(gs.g, 0, sizeof(double) * (size_t)group_len(gs), st));
+    gs.stale = false;
   }
-  FeArgs a{};
+  SegRowArgs a{};
   a.y = dy;
   a.eta = deta;
   a.m = dm;
-  a.off = dfo;
+  a.off = off;
   a.prior = dprior;
   a.n = n;
   a.ld = n_pad;
@@ -121,19 +136,11 @@ int sglm_engine::fe_sums_local(int kind, int mode, int family, int link, double 
   a.seg_start = seg_start();
   a.tile_seg = tile_seg();
   a.ntiles = cl_ntiles;
-  a.w = kind == FE_CHECK ? nullptr : domega;
-  a.Q = dfq;
+  a.w = rows ? domega : nullptr;
+  a.Q = gs.q;
   a.va = va;
   a.vb = vb;
-  HIPCHK(launch_fe_weights(a, fe_grid(ncu, cl_ntiles), st, evf[0], evf[1]));
-  // the sums of w x (u x) as well, then the per-segment scalars: two columns, t | W
-  return group_combine_local(kind != FE_CHECK, dfq, dfqp, 2, dfg);
-}
-
-// The tail of a step's local sums (fixed effects: dfg; GEE: dgg): with `rows` the segment sums of u x (u: domega)
-// through the combine tree into the first p columns of grp, then the ncol per-segment scalars Q through the same
-// tree into the columns after them (evcl[2] to evcl[3] spans both trees)
-int sglm_engine::group_combine_local(bool rows, const double* Q, double* Qp, int ncol, double* grp) {
+  HIPCHK(launch(a, fe_grid(ncu, cl_ntiles), st, gs.ev[0], gs.ev[1]));
   const int64_t ld = cl_inner->n_pad;
   if (rows) {
     ClusterArgs c{};
@@ -147,9 +154,24 @@ int sglm_engine::group_combine_local(bool rows, const double* Q, double* Qp, int
     c.ntiles = cl_ntiles;
     c.R = dR;
     HIPCHK(launch_cluster_sum(c, cluster_sum_grid(ncu, n, (int)p), st, evcl[0], evcl[1]));
-    if (int rc = combine_clusters(dR, dP, (int)p, grp, ld, evcl[2], nullptr)) return rc;
+    if (int rc = combine_clusters(dR, dP, (int)p, gs.g, ld, evcl[2], nullptr)) return rc;
   }
-  return combine_clusters(Q, Qp, ncol, grp + ld * p, ld, nullptr, rows ? evcl[3] : nullptr);
+  return combine_clusters(gs.q, gs.qp, gs.nq, gs.g + ld * p, ld, nullptr, rows ? evcl[3] : nullptr);
+}
+
+// The row values of `kind` (common.hpp FeKind: w or u into domega; at the effective offset) and the sums of w x
+// (u x), t | W into fe.g
+int sglm_engine::fe_sums_local(int kind, int mode, int family, int link, double mu0, double* va, double* vb) {
+  return group_sums_local(fe, launch_fe_weights, kind != FE_CHECK, kind, mode, family, link, mu0, dfo, va, vb);
+}
+
+int sglm_engine::keep_group_sums(GroupSums& gs) {
+  HIPCHK(hipSetDevice(device));
+  const size_t bytes = sizeof(double) * (size_t)group_len(gs);
+  if (!gs.g2)
+    if (int rc = dev_alloc(&gs.g2, bytes, "hipMalloc(group sums)")) return rc;
+  HIPCHK(hipMemcpyAsync(gs.g2, gs.g, bytes, hipMemcpyDeviceToDevice, st));
+  return SGLM_OK;
 }
 
 int sglm_engine::fe_sync() {
@@ -159,14 +181,15 @@ int sglm_engine::fe_sync() {
 }
 
 // what every entry point requires, before any launch; collective (cluster_count)
-int sglm::fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G, int which) {
+int sglm::fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G, const char* needs,
+                   int (sglm_engine::*prepare)()) {
   if (!opts || !family_link_valid(opts->family, opts->link)) {
     set_error("requirement failed: opts with a supported family/link");
     return SGLM_EINVAL;
   }
   if (int rc = check_handle(h)) return rc;
   if (int rc = check_ready(h)) return rc;
-  if (int rc = require_fused_or_narrow(h, which == SUM_GEE ? "a GEE fit needs" : "a fixed-effects fit needs")) return rc;
+  if (int rc = require_fused_or_narrow(h, needs)) return rc;
   if (int rc = h->theta_check(opts->family)) return rc;
   if (h->group() && h->group_aborted) {
     set_error("the multi-device handle's RCCL group was aborted by an earlier failure; create a new handle");
@@ -174,44 +197,34 @@ int sglm::fe_check(sglm_engine* h, const sglm_glm_opts* opts, int32_t* G, int wh
   }
   if (int rc = cluster_count(h, G)) return rc;
   for (sglm_engine* s : h->shards())
-    if (int rc = which == SUM_GEE ? s->gee_prepare() : s->fe_prepare()) return rc;
+    if (int rc = (s->*prepare)()) return rc;
   return SGLM_OK;
 }
 
 namespace {
 
-// what the fixed-effects and the GEE steps keep apart: the row kernel's events, the kernel times, the stale mark
-struct GroupSide {
-  hipEvent_t* ev;
-  double* ms;
-  bool* stale;
-};
-GroupSide group_side(sglm_engine* s, int which) {
-  return which == SUM_GEE ? GroupSide{s->evg, s->gee_ms, &s->gee_stale} : GroupSide{s->evf, s->fe_ms, &s->fe_stale};
-}
-
 // kernel times of the step just synchronised: the slowest shard
-int group_times(sglm_engine* h, int which, bool rows) {
+int group_times(sglm_engine* h, GroupSumsOf gs, bool rows) {
   const std::vector<sglm_engine*>& shards = h->shards();
   for (sglm_engine* s : shards) {
-    const GroupSide g = group_side(s, which);
+    double* sms = (s->*gs).ms;
     HIPCHK(hipSetDevice(s->device));
     float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, g.ev[0], g.ev[1]));
-    g.ms[0] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, (s->*gs).ev[0], (s->*gs).ev[1]));
+    sms[0] = ms;
     if (!rows) continue;
     HIPCHK(hipEventElapsedTime(&ms, s->evcl[0], s->evcl[1]));
-    g.ms[1] = ms;
-    g.ms[2] = 0.0;
+    sms[1] = ms;
+    sms[2] = 0.0;
     if (!s->cl_levels.empty()) {  // (no level, no combine launch: its events were not recorded)
       HIPCHK(hipEventElapsedTime(&ms, s->evcl[2], s->evcl[3]));
-      g.ms[2] = ms;
+      sms[2] = ms;
     }
   }
-  double* out = group_side(h, which).ms;
+  double* out = (h->*gs).ms;
   for (int k = 0; k < 3; ++k)
     for (sglm_engine* s : shards) {
-      const double v = group_side(s, which).ms[k];
+      const double v = (s->*gs).ms[k];
       out[k] = s == shards[0] ? v : std::max(out[k], v);
     }
   return SGLM_OK;
@@ -219,23 +232,52 @@ int group_times(sglm_engine* h, int which, bool rows) {
 
 }  // namespace
 
-// After every shard's local sums were enqueued: synchronise, take the kernel times, and sum over shards and ranks
-int sglm::group_sums_finish(sglm_engine* h, int which, bool rows) {
+int sglm::group_sums_finish(sglm_engine* h, GroupSumsOf gs, bool rows) {
   const std::vector<sglm_engine*>& shards = h->shards();
   for (sglm_engine* s : shards)
     if (int rc = s->fe_sync()) return rc;
-  if (int rc = group_times(h, which, rows)) return rc;
+  if (int rc = group_times(h, gs, rows)) return rc;
   // the sum over shards or ranks lands in the buffer itself, which this shard's next combine only partly rewrites
   if (h->group() || h->comm.kind != 0)
-    for (sglm_engine* s : shards) *group_side(s, which).stale = true;
-  return sum_cluster_scores(h, which);
+    for (sglm_engine* s : shards) (s->*gs).stale = true;
+  return sum_cluster_scores(h, [gs](sglm_engine* s) { return (s->*gs).g; }, shards[0]->group_len(shards[0]->*gs));
 }
 
-// The group sums of `kind` over every shard and rank: shard 0 of every rank ends with bitwise the same dfg
+int sglm::group_gram(sglm_engine* h, GroupSumsOf gs, hipError_t (*scale)(const GroupArgs&, hipStream_t), bool meat,
+                     double rho, double* packed) {
+  sglm_engine* s0 = h->shards()[0];
+  sglm_engine* in = s0->cl_inner;
+  HIPCHK(hipSetDevice(s0->device));
+  GroupArgs a{};
+  a.grp = (s0->*gs).g;
+  a.grp2 = meat ? (s0->*gs).g2 : (s0->*gs).g;
+  a.G = s0->cl_G;
+  a.ld = in->n_pad;
+  a.p = (int)s0->p;
+  a.meat = meat ? 1 : 0;
+  a.rho = rho;
+  a.X = in->dX;
+  a.y = in->dy;
+  HIPCHK(scale(a, s0->st));
+  HIPCHK(hipStreamSynchronize(s0->st));  // the internal engine's pass runs on its own stream
+  s0->cl_S_stale = true;                 // the cluster-robust covariance's S lives in the same design
+  if (int rc = in->pass(MODE_LM_GRAM, nullptr, 0.0, 0.0, FAM_GAUSSIAN, LNK_IDENTITY, packed)) return rc;
+  (h->*gs).ms[3] = in->last_pass_ms;
+  return SGLM_OK;
+}
+
+int sglm::drive_step_fit(StepBackend& be, const sglm_glm_opts& opts, sglm_preglm* out) {
+  if (int rc = glm_drive(be, opts, out)) return rc;
+  be.h->solve_ms += be.solve_ms;
+  be.h->solve_path = be.solve_path;
+  return SGLM_OK;
+}
+
+// The group sums of `kind` over every shard and rank: shard 0 of every rank ends with bitwise the same fe.g
 int sglm::fe_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0, double* va, double* vb) {
   for (sglm_engine* s : h->shards())  // (va, vb: one shard's rows -- the two-way fits, which ask for them, have one)
     if (int rc = s->fe_sums_local(kind, mode, family, link, mu0, va, vb)) return rc;
-  return group_sums_finish(h, SUM_FE, kind != FE_CHECK);
+  return group_sums_finish(h, &sglm_engine::fe, kind != FE_CHECK);
 }
 
 int sglm::absorbed_error(int64_t j) {
@@ -323,8 +365,8 @@ int fe_alpha_step(sglm_engine* h, const double* beta) {
   const int64_t p = s0->p;
   std::memcpy(s0->hbeta, beta, sizeof(double) * p);
   HIPCHK(hipMemcpyAsync(s0->dbeta, s0->hbeta, sizeof(double) * p, hipMemcpyHostToDevice, s0->st));
-  FeGroupArgs a{};
-  a.grp = s0->dfg;
+  GroupArgs a{};
+  a.grp = s0->fe.g;
   a.G = s0->cl_G;
   a.ld = s0->cl_inner->n_pad;
   a.p = (int)p;
@@ -341,28 +383,6 @@ int fe_alpha_step(sglm_engine* h, const double* beta) {
   return SGLM_OK;
 }
 
-// The group rows scaled into the internal engine of shard 0 and its LM Gram pass: packed [packed_len(p)]
-int fe_group_gram(sglm_engine* h, bool meat, double* packed) {
-  sglm_engine* s0 = h->shards()[0];
-  sglm_engine* in = s0->cl_inner;
-  HIPCHK(hipSetDevice(s0->device));
-  FeGroupArgs a{};
-  a.grp = s0->dfg;
-  a.grp_w = s0->dfg2;
-  a.G = s0->cl_G;
-  a.ld = in->n_pad;
-  a.p = (int)s0->p;
-  a.meat = meat ? 1 : 0;
-  a.X = in->dX;
-  a.y = in->dy;
-  HIPCHK(launch_fe_scale(a, s0->st));
-  HIPCHK(hipStreamSynchronize(s0->st));  // the internal engine's pass runs on its own stream
-  s0->cl_S_stale = true;                 // the cluster-robust covariance's S lives in the same design
-  if (int rc = in->pass(MODE_LM_GRAM, nullptr, 0.0, 0.0, FAM_GAUSSIAN, LNK_IDENTITY, packed)) return rc;
-  h->fe_ms[3] = in->last_pass_ms;
-  return SGLM_OK;
-}
-
 // One step at the shards' (alpha, o*): packed = lower tri A | b | the pass's scalars, all-reduced
 int fe_step(sglm_engine* h, int family, int link, int mode, const double* beta, double mu0, bool check_absorbed,
             double* packed) {
@@ -370,7 +390,7 @@ int fe_step(sglm_engine* h, int family, int link, int mode, const double* beta, 
   if (int rc = h->pass(mode, beta, mu0, 0.0, family, link, packed)) return rc;
   if (int rc = fe_group_sums(h, FE_WZ, mode, family, link, mu0)) return rc;
   std::vector<double> down((size_t)packed_len(p));
-  if (int rc = fe_group_gram(h, false, down.data())) return rc;
+  if (int rc = group_gram(h, &sglm_engine::fe, launch_fe_scale, false, 0.0, down.data())) return rc;
   for (int64_t j = 0; j < p; ++j) {
     const int64_t jj = j * (j + 1) / 2 + j;
     if (check_absorbed && packed[jj] > 0.0 && !(packed[jj] - down[(size_t)jj] > FE_ABSORBED_RATIO * packed[jj]))
@@ -395,17 +415,13 @@ int fe_set_alpha_all(sglm_engine* h, const double* alpha) {
 // columns [col0, col0 + ncol) of shard 0's group sums, the first G rows of each, to the host
 int fe_download(sglm_engine* h, int64_t col0, int64_t ncol, double* out) {
   sglm_engine* s0 = h->shards()[0];
-  return download_cols(s0, s0->dfg, s0->cl_inner->n_pad, s0->cl_G, col0, ncol, out);
+  return download_cols(s0, s0->fe.g, s0->cl_inner->n_pad, s0->cl_G, col0, ncol, out);
 }
 
 // The fit's Backend: glm_drive's pass is the fixed-effects step; no deviance-only passes (every pass's sums
 // move alpha), no in-pass statistics (the passes store eta for the weights kernel).
-struct FeBackend : public Backend {
-  sglm_engine* h;
-  explicit FeBackend(sglm_engine* handle) : h(handle) {}
-  int64_t ncols() const override { return h->ncols(); }
-  int npart() const override { return h->npart(); }
-  int global_sums(double* out2) override { return h->global_sums(out2); }
+struct FeBackend : public StepBackend {
+  using StepBackend::StepBackend;
   int pass(int mode, const double* beta, double mu0, double ybar, int family, int link, double* packed) override {
     (void)ybar;
     if (beta)
@@ -413,10 +429,6 @@ struct FeBackend : public Backend {
     if (int rc = fe_offsets(h)) return rc;
     return fe_step(h, family, link, mode, beta, mu0, true, packed);
   }
-  int stats(int mode, const double* beta, double mu0, double ybar, int family, int link, double* s) override {
-    return h->stats(mode, beta, mu0, ybar, family, link, s);
-  }
-  std::unique_ptr<SolverIface> make_solver(int64_t p) override { return h->make_solver(p); }
 };
 
 // Groups without a finite alpha: the rows of positive prior weight all have y = 0 (or all y = m)
@@ -448,9 +460,7 @@ int sglm_fit_glm_fe(sglm_engine* h, const sglm_glm_opts* opts, sglm_preglm* out,
   if (int rc = fe_set_alpha_all(h, nullptr)) return rc;
   if (int rc = fe_uninformative(h, opts->family, opts->link, G)) return rc;
   FeBackend be(h);
-  if (int rc = glm_drive(be, *opts, out)) return rc;
-  h->solve_ms += be.solve_ms;
-  h->solve_path = be.solve_path;
+  if (int rc = drive_step_fit(be, *opts, out)) return rc;
   // alpha of the last pass (at out->coefs) and the W of that pass: a group without weight has no alpha
   std::vector<double> W((size_t)G);
   sglm_engine* s0 = h->shards()[0];
@@ -461,10 +471,10 @@ int sglm_fit_glm_fe(sglm_engine* h, const sglm_glm_opts* opts, sglm_preglm* out,
   if (info) {
     info->G_eff = geff;
     info->df_residual = out->nrow - (double)h->ncols() - (double)geff;
-    info->weights_ms = h->fe_ms[0];
-    info->sum_ms = h->fe_ms[1];
-    info->combine_ms = h->fe_ms[2];
-    info->gram_ms = h->fe_ms[3];
+    info->weights_ms = h->fe.ms[0];
+    info->sum_ms = h->fe.ms[1];
+    info->combine_ms = h->fe.ms[2];
+    info->gram_ms = h->fe.ms[3];
   }
   return SGLM_OK;
 }
@@ -502,7 +512,6 @@ int sglm_vcov_fe(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, 
     if (int rc = check_cadjust(cadjust, G)) return rc;
   FeScope scope(h);
   const int64_t p = h->ncols();
-  sglm_engine* s0 = h->shards()[0];
   if (int rc = fe_set_alpha_all(h, alpha)) return rc;
   if (int rc = fe_offsets(h)) return rc;
   std::vector<double> packed((size_t)packed_len(p)), C, M((size_t)(p * p)), x((size_t)p);
@@ -510,17 +519,13 @@ int sglm_vcov_fe(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, 
   const char* singular = "breeze.linalg.MatrixSingularException: the within-group X'WX is singular";
   if (int rc = fe_bread(h, packed.data(), singular, C)) return rc;
   if (!cluster) return fe_plain_cov(C, cov, meat);
-  // the w-weighted sums s | W stay in dfg2 while the u-weighted ones S | U are formed in dfg
-  HIPCHK(hipSetDevice(s0->device));
-  if (!s0->dfg2)
-    if (int rc = sglm_engine::dev_alloc(&s0->dfg2, sizeof(double) * (size_t)s0->fe_len(), "hipMalloc(group sums)"))
-      return rc;
-  HIPCHK(hipMemcpyAsync(s0->dfg2, s0->dfg, sizeof(double) * (size_t)s0->fe_len(), hipMemcpyDeviceToDevice, s0->st));
+  // the w-weighted sums s | W stay in g2 while the u-weighted ones S | U are formed in g
+  if (int rc = h->shards()[0]->keep_group_sums(h->shards()[0]->fe)) return rc;
   std::vector<double> W((size_t)G);
   if (int rc = fe_download(h, p + 1, 1, W.data())) return rc;
   const int32_t geff = count_weighted(W, nullptr);
   if (int rc = fe_group_sums(h, FE_SCORE, MODE_IRLS, opts->family, opts->link, 0.0)) return rc;
-  if (int rc = fe_group_gram(h, true, packed.data())) return rc;
+  if (int rc = group_gram(h, &sglm_engine::fe, launch_fe_scale, true, 0.0, packed.data())) return rc;
   unpack_gram(packed.data(), p, M.data(), x.data());
   double nrows = (double)(h->group() ? h->g_n : h->n);  // every row of every shard, weight 0 included
   if (hc_type == SGLM_HC1 && !h->group())
@@ -534,10 +539,10 @@ int sglm_get_fe_ms(sglm_engine* h, double* weights_ms, double* sum_ms, double* c
     set_error("requirement failed: weights_ms, sum_ms, combine_ms, gram_ms");
     return SGLM_EINVAL;
   }
-  *weights_ms = h->fe_ms[0];
-  *sum_ms = h->fe_ms[1];
-  *combine_ms = h->fe_ms[2];
-  *gram_ms = h->fe_ms[3];
+  *weights_ms = h->fe.ms[0];
+  *sum_ms = h->fe.ms[1];
+  *combine_ms = h->fe.ms[2];
+  *gram_ms = h->fe.ms[3];
   return SGLM_OK;
 }
 

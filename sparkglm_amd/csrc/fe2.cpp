@@ -349,7 +349,7 @@ int gather2(sglm_engine* s, const double* v) {
 int update_levels(sglm_engine* s, int f) {
   Fe2* F = s->fe2;
   Fe2UpdateArgs u{};
-  u.S = f ? F->dS2 : s->dfg;
+  u.S = f ? F->dS2 : s->fe.g;
   u.T = f ? F->dT2 : F->dT1;
   u.ldS = f ? F->ld2 : F->ld1;
   u.L = f ? F->H : s->cl_G;
@@ -362,7 +362,7 @@ int update_levels(sglm_engine* s, int f) {
   return SGLM_OK;
 }
 
-// The sweeps from the Y on the device, at the w in domega and the sums in dfg / dS2
+// The sweeps from the Y on the device, at the w in domega and the sums in fe.g / dS2
 int run_sweeps(sglm_engine* s, const sglm_fe2_opts* o, int iter, int* sweeps) {
   Fe2* F = s->fe2;
   const double tol = default_tol(o);
@@ -445,7 +445,7 @@ int fe2_step(sglm_engine* h, const sglm_fe2_opts* o, int family, int link, int m
   const int64_t p = h->p;
   if (int rc = offsets(h)) return rc;
   if (int rc = h->pass(mode, beta, mu0, 0.0, family, link, packed)) return rc;
-  // w in domega, w z in dwz, S1 | t1 | W1 in dfg
+  // w in domega, w z in dwz, S1 | t1 | W1 in fe.g
   if (int rc = fe_group_sums(h, FE_WZ, mode, family, link, mu0, F->dwz)) return rc;
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipEventRecord(F->ev[0], h->st));
@@ -456,7 +456,7 @@ int fe2_step(sglm_engine* h, const sglm_fe2_opts* o, int family, int link, int m
   HIPCHK(hipEventRecord(F->ev[3], h->st));
   HIPCHK(hipEventRecord(F->ev[4], h->st));
   Fe2CrossArgs c{};
-  c.S[0] = h->dfg;
+  c.S[0] = h->fe.g;
   c.S[1] = F->dS2;
   c.ldS[0] = F->ld1;
   c.ldS[1] = F->ld2;
@@ -477,8 +477,8 @@ int fe2_step(sglm_engine* h, const sglm_fe2_opts* o, int family, int link, int m
   std::vector<double> D((size_t)(PR * PC));
   HIPCHK(hipMemcpyAsync(D.data(), F->dcross, sizeof(double) * D.size(), hipMemcpyDeviceToHost, h->st));
   HIPCHK(hipStreamSynchronize(h->st));
-  h->fe2_ms[0] = h->fe_ms[0];
-  h->fe2_ms[1] = h->fe_ms[1] + h->fe_ms[2];
+  h->fe2_ms[0] = h->fe.ms[0];
+  h->fe2_ms[1] = h->fe.ms[1] + h->fe.ms[2];
   h->fe2_ms[2] = elapsed(F->ev[0], F->ev[1]);
   h->fe2_ms[3] = elapsed(F->ev[2], F->ev[3]);
   h->fe2_ms[4] = elapsed(F->ev[4], F->ev[5]);
@@ -509,7 +509,7 @@ int effects_step(sglm_engine* h, const double* beta) {
     a.ldy = F->ldy;
     a.L = f ? F->H : h->cl_G;
     a.p = (int)p;
-    a.W = f ? F->dS2 + (p + 1) * F->ld2 : h->dfg + (p + 1) * F->ld1;
+    a.W = f ? F->dS2 + (p + 1) * F->ld2 : h->fe.g + (p + 1) * F->ld1;
     a.beta = h->dbeta;
     a.eff = f ? F->dgamma : h->dalpha;
     HIPCHK(launch_fe2_effect(a, h->st));
@@ -540,22 +540,18 @@ int zero_Y(sglm_engine* h) {
 int count_levels(sglm_engine* h, int32_t* geff, int32_t* heff, double* alpha = nullptr, double* gamma = nullptr) {
   Fe2* F = h->fe2;
   std::vector<double> W1((size_t)h->cl_G), W2((size_t)F->H);
-  if (int rc = download_cols(h, h->dfg, F->ld1, h->cl_G, h->p + 1, 1, W1.data())) return rc;
+  if (int rc = download_cols(h, h->fe.g, F->ld1, h->cl_G, h->p + 1, 1, W1.data())) return rc;
   if (int rc = download_cols(h, F->dS2, F->ld2, F->H, h->p + 1, 1, W2.data())) return rc;
   *geff = count_weighted(W1, alpha);
   *heff = count_weighted(W2, gamma);
   return SGLM_OK;
 }
 
-struct Fe2Backend : public Backend {
-  sglm_engine* h;
+struct Fe2Backend : public StepBackend {
   const sglm_fe2_opts* o;
   int iter = 0, sweeps_last = 0;
   int64_t sweeps_total = 0;
-  Fe2Backend(sglm_engine* handle, const sglm_fe2_opts* opts) : h(handle), o(opts) {}
-  int64_t ncols() const override { return h->ncols(); }
-  int npart() const override { return h->npart(); }
-  int global_sums(double* out2) override { return h->global_sums(out2); }
+  Fe2Backend(sglm_engine* handle, const sglm_fe2_opts* opts) : StepBackend(handle), o(opts) {}
   int pass(int mode, const double* beta, double mu0, double ybar, int family, int link, double* packed) override {
     (void)ybar;
     if (beta)
@@ -565,10 +561,6 @@ struct Fe2Backend : public Backend {
     iter += 1;
     return SGLM_OK;
   }
-  int stats(int mode, const double* beta, double mu0, double ybar, int family, int link, double* s) override {
-    return h->stats(mode, beta, mu0, ybar, family, link, s);
-  }
-  std::unique_ptr<SolverIface> make_solver(int64_t p) override { return h->make_solver(p); }
 };
 
 // Levels without a finite effect: the rows of positive prior weight all have y = 0 (or all y = m), either factor
@@ -581,7 +573,7 @@ int uninformative2(sglm_engine* h, int family, int link) {
     std::vector<double> ab((size_t)(2 * L));
     if (f == 0) {  // y and m - y (or 1) of every row into dwz and domega on the way
       if (int rc = fe_group_sums(h, FE_CHECK, MODE_IRLS, family, link, 0.0, F->dwz, h->domega)) return rc;
-      if (int rc = download_cols(h, h->dfg, F->ld1, L, p, 2, ab.data())) return rc;
+      if (int rc = download_cols(h, h->fe.g, F->ld1, L, p, 2, ab.data())) return rc;
     } else {
       HIPCHK(hipSetDevice(h->device));
       if (int rc = list_sums(h, 0, nullptr, F->dwz, h->domega, F->dT2)) return rc;  // (p + 1 >= 2 columns)
@@ -664,9 +656,7 @@ int sglm_fit_glm_fe2(sglm_engine* h, const sglm_glm_opts* opts, const sglm_fe2_o
   if (int rc = zero_Y(h)) return rc;
   if (int rc = uninformative2(h, opts->family, opts->link)) return rc;
   Fe2Backend be(h, fe2);
-  if (int rc = glm_drive(be, *opts, out)) return rc;
-  h->solve_ms += be.solve_ms;
-  h->solve_path = be.solve_path;
+  if (int rc = drive_step_fit(be, *opts, out)) return rc;
   // the effects of the last pass (at out->coefs) and the weights of that pass: a level without weight has none
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipMemcpy(alpha, h->dalpha, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost));
@@ -709,7 +699,7 @@ int sglm_fe2_pass(sglm_engine* h, const sglm_glm_opts* opts, const sglm_fe2_opts
   fe_unpack_step(packed.data(), p, A, b, scalars);
   if (sweeps) *sweeps = k;
   if (group1)
-    if (int rc = download_cols(h, h->dfg, F->ld1, G, 0, p + 2, group1)) return rc;
+    if (int rc = download_cols(h, h->fe.g, F->ld1, G, 0, p + 2, group1)) return rc;
   if (group2)
     if (int rc = download_cols(h, F->dS2, F->ld2, H, 0, p + 2, group2)) return rc;
   if (Y) {
@@ -753,13 +743,13 @@ int sglm_vcov_fe2(sglm_engine* h, const sglm_glm_opts* opts, const sglm_fe2_opts
   if (!cluster) return fe_plain_cov(C, cov, meat);
   int32_t geff = 0, heff = 0;
   if (int rc = count_levels(h, &geff, &heff)) return rc;
-  // the u-weighted sums S | U over factor 1 into dfg (u in domega), then sum_{i in g} u_i c_{h(i)} into T1
+  // the u-weighted sums S | U over factor 1 into fe.g (u in domega), then sum_{i in g} u_i c_{h(i)} into T1
   if (int rc = fe_group_sums(h, FE_SCORE, MODE_IRLS, opts->family, opts->link, 0.0)) return rc;
   HIPCHK(hipSetDevice(h->device));
   if (int rc = gather1(h, h->domega)) return rc;
   sglm_engine* in = h->cl_inner;
   Fe2MeatArgs m{};
-  m.Su = h->dfg;
+  m.Su = h->fe.g;
   m.Tu = F->dT1;
   m.Y1 = F->dY1;
   m.G = G;

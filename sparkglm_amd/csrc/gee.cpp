@@ -20,70 +20,22 @@
 using namespace sglm;
 
 void sglm_engine::free_gee() {
-  dev_free({&dgq, &dgqp, &dgg, &dgg2, &dgm});
-  gee_stale = true;
-  for (hipEvent_t& e : evg) {
-    if (e) (void)hipEventDestroy(e);
-    e = nullptr;
-  }
+  dev_free({&dgm});
+  free_group(gee);
 }
 
-// The buffers of a GEE step on this shard (kept until the clusters or the data change)
+// The buffers of a GEE step on this shard
 int sglm_engine::gee_prepare() {
-  HIPCHK(hipSetDevice(device));
-  if (int rc = check_loaded()) return rc;
-  if (int rc = ensure_cl_inner()) return rc;
-  if (int rc = grow(domega, omega_cap, n_pad, "hipMalloc(working weights)")) return rc;
-  for (hipEvent_t& e : evcl)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  for (hipEvent_t& e : evg)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  const size_t d = sizeof(double);
-  if (!dgq)
-    if (int rc = dev_alloc(&dgq, d * (size_t)std::max<int64_t>(GEE_NQ * cl_nseg, 1), "hipMalloc(segment scalar sums)"))
-      return rc;
-  if (!dgqp && cl_prow > 0)
-    if (int rc = dev_alloc(&dgqp, d * (size_t)(GEE_NQ * cl_prow), "hipMalloc(scalar combine scratch)")) return rc;
+  if (int rc = group_prepare(gee)) return rc;
   if (!dgm)
-    if (int rc = dev_alloc(&dgm, d * (size_t)((GEE_MOMENT_BLOCKS + 1) * NS), "hipMalloc(moment partials)")) return rc;
-  if (!dgg) {
-    if (int rc = dev_alloc(&dgg, d * (size_t)gee_len(), "hipMalloc(group sums)")) return rc;
-    gee_stale = true;
-  }
+    if (int rc = dev_alloc(&dgm, sizeof(double) * (size_t)((GEE_MOMENT_BLOCKS + 1) * NS), "hipMalloc(moment partials)"))
+      return rc;
   return SGLM_OK;
 }
 
+// d (GEE_SCORE: d e) into domega at the rows' own offset, and the sums of d x (d e x), t | n | E | Q into gee.g
 int sglm_engine::gee_sums_local(int kind, int mode, int family, int link, double mu0) {
-  HIPCHK(hipSetDevice(device));
-  // as fe_sums_local: the combine rewrites the rows of the groups that have a segment here and no others, so the
-  // buffer is cleared after every cross-shard sum that landed in it
-  if (gee_stale) {
-    HIPCHK(hipMemsetAsync(dgg, 0, sizeof(double) * (size_t)gee_len(), st));
-    gee_stale = false;
-  }
-  const bool rows = kind != GEE_COUNT;  // the sums of d x (d e x) as well
-  GeeArgs a{};
-  a.y = dy;
-  a.eta = deta;
-  a.m = dm;
-  a.off = doff;
-  a.prior = dprior;
-  a.n = n;
-  a.ld = n_pad;
-  a.family = family;
-  a.link = link;
-  a.mode = mode;
-  a.kind = kind;
-  a.mu0 = mu0;
-  a.theta = theta;
-  a.seg_start = seg_start();
-  a.tile_seg = tile_seg();
-  a.ntiles = cl_ntiles;
-  a.d = rows ? domega : nullptr;
-  a.Q = dgq;
-  HIPCHK(launch_gee_rows(a, fe_grid(ncu, cl_ntiles), st, evg[0], evg[1]));
-  // the sums of d x (d e x) as well, then the per-segment scalars: four columns, t | n | E | Q
-  return group_combine_local(rows, dgq, dgqp, GEE_NQ, dgg);
+  return group_sums_local(gee, launch_gee_rows, kind != GEE_COUNT, kind, mode, family, link, mu0, doff, nullptr, nullptr);
 }
 
 namespace {
@@ -122,19 +74,19 @@ int rho_error(const char* what, double rho, double n_max, int iter) {
   return SGLM_EINVAL;
 }
 
-// The group sums of `kind` over every shard and rank: shard 0 of every rank ends with bitwise the same dgg
+// The group sums of `kind` over every shard and rank: shard 0 of every rank ends with bitwise the same gee.g
 int gee_group_sums(sglm_engine* h, int kind, int mode, int family, int link, double mu0) {
   for (sglm_engine* s : h->shards())
     if (int rc = s->gee_sums_local(kind, mode, family, link, mu0)) return rc;
-  return group_sums_finish(h, SUM_GEE, kind != GEE_COUNT);
+  return group_sums_finish(h, &sglm_engine::gee, kind != GEE_COUNT);
 }
 
 // The moments of shard 0's all-reduced group buffer: NS doubles to the host, no G-sized download
 int gee_moments(sglm_engine* h, double* m) {
   sglm_engine* s0 = h->shards()[0];
   HIPCHK(hipSetDevice(s0->device));
-  GeeGroupArgs a{};
-  a.grp = s0->dgg;
+  GroupArgs a{};
+  a.grp = s0->gee.g;
   a.G = s0->cl_G;
   a.ld = s0->cl_inner->n_pad;
   a.p = (int)s0->p;
@@ -171,29 +123,6 @@ int gee_counts(sglm_engine* h, const sglm_glm_opts* opts, GeeState* g) {
   return SGLM_OK;
 }
 
-// The group rows scaled into the internal engine of shard 0 and its LM Gram pass: packed [packed_len(p)]
-int gee_group_gram(sglm_engine* h, bool meat, double rho, double* packed) {
-  sglm_engine* s0 = h->shards()[0];
-  sglm_engine* in = s0->cl_inner;
-  HIPCHK(hipSetDevice(s0->device));
-  GeeGroupArgs a{};
-  a.grp = s0->dgg;
-  a.grp_s = meat ? s0->dgg2 : s0->dgg;
-  a.G = s0->cl_G;
-  a.ld = in->n_pad;
-  a.p = (int)s0->p;
-  a.meat = meat ? 1 : 0;
-  a.rho = rho;
-  a.X = in->dX;
-  a.y = in->dy;
-  HIPCHK(launch_gee_scale(a, s0->st));
-  HIPCHK(hipStreamSynchronize(s0->st));  // the internal engine's pass runs on its own stream
-  s0->cl_S_stale = true;                 // the cluster-robust covariance's S lives in the same design
-  if (int rc = in->pass(MODE_LM_GRAM, nullptr, 0.0, 0.0, FAM_GAUSSIAN, LNK_IDENTITY, packed)) return rc;
-  h->gee_ms[3] = in->last_pass_ms;
-  return SGLM_OK;
-}
-
 // One step: packed = lower tri A | b | the pass's scalars, all-reduced; g->rho_used and g->m of this step.
 // sums: form the group sums and the moments even where the step does not need them (the initial mode and
 // independence, whose A and b are the pass's own).  iter: named by the refusal of an invalid estimate.
@@ -212,7 +141,7 @@ int gee_step(sglm_engine* h, int family, int link, int mode, const double* beta,
   g->rho_used = rho;
   if (rho == 0.0) return SGLM_OK;
   std::vector<double> dn((size_t)packed_len(p));
-  if (int rc = gee_group_gram(h, false, rho, dn.data())) return rc;
+  if (int rc = group_gram(h, &sglm_engine::gee, launch_gee_scale, false, rho, dn.data())) return rc;
   const double omr = 1.0 - rho;
   if (rho > 0.0)
     for (int64_t k = 0; k < tri_count(p) + p; ++k) packed[k] = (packed[k] - dn[(size_t)k]) / omr;
@@ -223,23 +152,15 @@ int gee_step(sglm_engine* h, int family, int link, int mode, const double* beta,
 
 // The fit's Backend: glm_drive's pass is the GEE step; no deviance-only passes, no in-pass statistics (the
 // passes store eta for the rows kernel).
-struct GeeBackend : public Backend {
-  sglm_engine* h;
+struct GeeBackend : public StepBackend {
   GeeState* g;
   int iter = 0;
-  GeeBackend(sglm_engine* handle, GeeState* state) : h(handle), g(state) {}
-  int64_t ncols() const override { return h->ncols(); }
-  int npart() const override { return h->npart(); }
-  int global_sums(double* out2) override { return h->global_sums(out2); }
+  GeeBackend(sglm_engine* handle, GeeState* state) : StepBackend(handle), g(state) {}
   int pass(int mode, const double* beta, double mu0, double ybar, int family, int link, double* packed) override {
     (void)ybar;
     if (mode == MODE_IRLS) iter += 1;
     return gee_step(h, family, link, mode, beta, mu0, g, false, iter, packed);
   }
-  int stats(int mode, const double* beta, double mu0, double ybar, int family, int link, double* s) override {
-    return h->stats(mode, beta, mu0, ybar, family, link, s);
-  }
-  std::unique_ptr<SolverIface> make_solver(int64_t p) override { return h->make_solver(p); }
 };
 
 const char* GEE_SINGULAR = "breeze.linalg.MatrixSingularException: the GEE step's X' inv(R) X is singular";
@@ -257,13 +178,11 @@ int sglm_fit_glm_gee(sglm_engine* h, const sglm_glm_opts* opts, const sglm_gee_o
   GeeState g;
   if (int rc = gee_read_opts(gee, &g)) return rc;
   int32_t G = 0;
-  if (int rc = fe_check(h, opts, &G, SUM_GEE)) return rc;
+  if (int rc = fe_check(h, opts, &G, "a GEE fit needs", &sglm_engine::gee_prepare)) return rc;
   FeScope scope(h);
   if (int rc = gee_counts(h, opts, &g)) return rc;
   GeeBackend be(h, &g);
-  if (int rc = glm_drive(be, *opts, out)) return rc;
-  h->solve_ms += be.solve_ms;
-  h->solve_path = be.solve_path;
+  if (int rc = drive_step_fit(be, *opts, out)) return rc;
   // rho and phi at the returned coefficients: one eta-storing pass without Gram, the rows kernel, the moments
   const int64_t p = h->ncols();
   std::vector<double> packed((size_t)packed_len(p));
@@ -276,10 +195,10 @@ int sglm_fit_glm_gee(sglm_engine* h, const sglm_glm_opts* opts, const sglm_gee_o
     info->N = g.m[M_N];
     info->G_eff = (int32_t)g.m[M_GEFF];
     info->n_max = (int32_t)g.m[M_NMAX];
-    info->rows_ms = h->gee_ms[0];
-    info->sum_ms = h->gee_ms[1];
-    info->combine_ms = h->gee_ms[2];
-    info->gram_ms = h->gee_ms[3];
+    info->rows_ms = h->gee.ms[0];
+    info->sum_ms = h->gee.ms[1];
+    info->combine_ms = h->gee.ms[2];
+    info->gram_ms = h->gee.ms[3];
   }
   return SGLM_OK;
 }
@@ -289,7 +208,7 @@ int sglm_gee_pass(sglm_engine* h, const sglm_glm_opts* opts, const sglm_gee_opts
   GeeState g;
   if (int rc = gee_read_opts(gee, &g)) return rc;
   int32_t G = 0;
-  if (int rc = fe_check(h, opts, &G, SUM_GEE)) return rc;
+  if (int rc = fe_check(h, opts, &G, "a GEE fit needs", &sglm_engine::gee_prepare)) return rc;
   FeScope scope(h);
   if (int rc = gee_counts(h, opts, &g)) return rc;
   const int64_t p = h->ncols();
@@ -301,7 +220,7 @@ int sglm_gee_pass(sglm_engine* h, const sglm_glm_opts* opts, const sglm_gee_opts
   fe_unpack_step(packed.data(), p, A, b, scalars);
   if (group) {
     sglm_engine* s0 = h->shards()[0];
-    if (int rc = download_cols(s0, s0->dgg, s0->cl_inner->n_pad, s0->cl_G, 0, p + GEE_NQ, group)) return rc;
+    if (int rc = download_cols(s0, s0->gee.g, s0->cl_inner->n_pad, s0->cl_G, 0, p + GEE_NQ, group)) return rc;
   }
   if (moments) std::memcpy(moments, g.m, sizeof(double) * 5);
   if (rho_used) *rho_used = g.rho_used;
@@ -324,13 +243,12 @@ int sglm_vcov_gee(sglm_engine* h, const sglm_glm_opts* opts, const sglm_gee_opts
     return SGLM_EINVAL;
   }
   int32_t G = 0;
-  if (int rc = fe_check(h, opts, &G, SUM_GEE)) return rc;
+  if (int rc = fe_check(h, opts, &G, "a GEE fit needs", &sglm_engine::gee_prepare)) return rc;
   if (robust)
     if (int rc = check_cadjust(cadjust, G)) return rc;
   FeScope scope(h);
   if (int rc = gee_counts(h, opts, &g)) return rc;
   const int64_t p = h->ncols();
-  sglm_engine* s0 = h->shards()[0];
   std::vector<double> packed((size_t)packed_len(p)), C, M((size_t)(p * p)), x((size_t)p);
   if (int rc = gee_step(h, opts->family, opts->link, MODE_IRLS, beta, 0.0, &g, true, -1, packed.data())) return rc;
   const double phi = phi_of(g.m, p);
@@ -354,14 +272,10 @@ int sglm_vcov_gee(sglm_engine* h, const sglm_glm_opts* opts, const sglm_gee_opts
               "family's range at beta)");
     return SGLM_EINVAL;
   }
-  // the step's sums s | t | n | E | Q stay in dgg2 while the score-weighted ones S1 are formed in dgg
-  HIPCHK(hipSetDevice(s0->device));
-  if (!s0->dgg2)
-    if (int rc = sglm_engine::dev_alloc(&s0->dgg2, sizeof(double) * (size_t)s0->gee_len(), "hipMalloc(group sums)"))
-      return rc;
-  HIPCHK(hipMemcpyAsync(s0->dgg2, s0->dgg, sizeof(double) * (size_t)s0->gee_len(), hipMemcpyDeviceToDevice, s0->st));
+  // the step's sums s | t | n | E | Q stay in g2 while the score-weighted ones S1 are formed in g
+  if (int rc = h->shards()[0]->keep_group_sums(h->shards()[0]->gee)) return rc;
   if (int rc = gee_group_sums(h, GEE_SCORE, MODE_IRLS, opts->family, opts->link, 0.0)) return rc;
-  if (int rc = gee_group_gram(h, true, g.rho, packed.data())) return rc;
+  if (int rc = group_gram(h, &sglm_engine::gee, launch_gee_scale, true, g.rho, packed.data())) return rc;
   unpack_gram(packed.data(), p, M.data(), x.data());
   return clustered_finish(SGLM_HC0, 0.0, p, 0, G, cadjust, C, M, "beta", cov, meat);
 }
@@ -372,7 +286,7 @@ int sglm_get_gee_ms(sglm_engine* h, double* ms) {
     set_error("requirement failed: ms [4]");
     return SGLM_EINVAL;
   }
-  std::memcpy(ms, h->gee_ms, sizeof(double) * 4);
+  std::memcpy(ms, h->gee.ms, sizeof(double) * 4);
   return SGLM_OK;
 }
 

@@ -2,13 +2,10 @@
 // (gfx950; gee.cpp).  The design is read only by the pass and by cluster.hip's segment
 // sums; the kernels here stream the row vectors or the G group rows.
 //
-// gee_rows_kernel     fe.hip's fe_weights_kernel tiling: one workgroup of CLUSTER_TILE_ROWS threads per row
-//   tile, thread r = row r of the tile.  The row's d = sqrt(w), e = d (y - mu) g'(mu) and d z come from
-//   rowmath.hpp's reference-order row_core at the eta the pass stored; d (GEE_SCORE: d e, the signed score)
-//   is stored for the segment sums of d x, zeros on the padding rows and on rows of prior weight 0.  d z,
-//   1[pw > 0], e and e^2 are summed per segment in fe.hip's two fixed steps (pieces of 8 rows by the thread of
-//   their first row, then each segment's pieces by one thread, ascending) into Q [nseg][4].  No atomics; the
-//   order is a function of (ids, n) alone.
+// gee_rows_kernel     segrows.hpp's row kernel with the policy GeeRows.  The row's d = sqrt(w), e = d (y - mu)
+//   g'(mu) and d z come from rowmath.hpp's reference-order row_core at the eta the pass stored; d (GEE_SCORE: d e,
+//   the signed score) is stored for the segment sums of d x.  d z, 1[pw > 0], e and e^2 are summed per segment
+//   into Q [nseg][4] in the tile's two fixed steps.
 // gee_moments_kernel  the five moments of the all-reduced group buffer (and the count of groups with rows):
 //   thread t of block b adds the groups b 256 + t, + grid 256, ... in that order, the block adds its threads
 //   in a fixed tree, and the per-block partials go through reduce_stats_kernel (compensated); n_max, a
@@ -22,15 +19,12 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "rowmath.hpp"
+#include "segrows.hpp"
 
 namespace sglm {
 
 namespace {
 
-constexpr int GEE_NT = CLUSTER_TILE_ROWS;
-constexpr int GEE_SUB = 8;  // rows per piece of the tile's segment sums (fe.hip FE_SUB)
-static_assert(GEE_NT % 64 == 0 && GEE_NT % GEE_SUB == 0, "whole waves, whole pieces");
-static_assert(GEE_NT % RB == 0, "the tiles of n rows cover the ld = n rounded up to RB rows of the per-row output");
 static_assert(GEE_NM <= NS, "the moments travel in one block of NS scalars");
 
 // d = sqrt(w), d z and e = d (y - mu) g' of one row in the reference operation order (rowmath.hpp row_core)
@@ -44,77 +38,26 @@ __device__ __noinline__ GeeRow gee_row(int fam, int lnk, int mode, double eta, d
   return GeeRow{d, working_wz(d, c.eta, y, c.mu, c.g, off), d * ((y + (-1.0 * c.mu)) * c.g)};
 }
 
-__global__ void __launch_bounds__(GEE_NT) gee_rows_kernel(GeeArgs a) {
-  __shared__ double sv[GEE_NQ][GEE_NT];
-  __shared__ int head[GEE_NT];  // 1: the row starts a segment
-  const int r = threadIdx.x;
-  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-    const int64_t row0 = tile * GEE_NT, row = row0 + r;
-    double out = 0.0, v[GEE_NQ] = {0.0, 0.0, 0.0, 0.0};
-    if (row < a.n) {
-      const double pw = a.prior ? a.prior[row] : 1.0;
-      if (pw != 0.0) {  // a row of prior weight 0 contributes exact zeros whatever its y and eta
-        if (pw > 0.0) v[1] = 1.0;
-        if (a.kind != GEE_COUNT) {
-          const double eta = a.mode == MODE_IRLS ? a.eta[row] : 0.0;
-          const GeeRow g = gee_row(a.family, a.link, a.mode, eta, a.y[row], a.m ? a.m[row] : 1.0,
-                                   a.off ? a.off[row] : 0.0, pw, a.mu0, a.theta);
-          out = a.kind == GEE_SCORE ? g.d * g.e : g.d;
-          v[0] = g.dz;
-          v[2] = g.e;
-          v[3] = g.e * g.e;
-        }
-      }
-    }
-    if (a.d && row < a.ld) a.d[row] = out;  // (the tiles cover every row below ld: ld is n rounded up to RB rows)
-#pragma unroll
-    for (int q = 0; q < GEE_NQ; ++q) sv[q][r] = v[q];
-    head[r] = 0;
-    __syncthreads();
-    // the tile's segments in two fixed steps (fe.hip): pieces -- maximal runs of rows inside one segment and
-    // one block of GEE_SUB rows -- by the thread of their first row, then each segment's pieces by one thread
-    const int64_t k = a.tile_seg[tile] + r;
-    const bool owns = k < a.tile_seg[tile + 1];  // at most GEE_NT segments in a tile
-    int lo = 0, hi = 0;
-    if (owns) {
-      lo = (int)(a.seg_start[k] - row0);
-      hi = (int)(min(a.seg_start[k + 1], a.n) - row0);
-      head[lo] = 1;
-    }
-    __syncthreads();
-    const int nrow = (int)min((int64_t)GEE_NT, a.n - row0);
-    double pc[GEE_NQ] = {0.0, 0.0, 0.0, 0.0};
-    const bool first = r < nrow && (r % GEE_SUB == 0 || head[r]);
-    if (first) {
-      int i = r;
-      do {
-#pragma unroll
-        for (int q = 0; q < GEE_NQ; ++q) pc[q] += sv[q][i];
-        ++i;
-      } while (i < nrow && i % GEE_SUB != 0 && !head[i]);
-    }
-    __syncthreads();  // every piece has read sv
-    if (first) {
-#pragma unroll
-      for (int q = 0; q < GEE_NQ; ++q) sv[q][r] = pc[q];
-    }
-    __syncthreads();
-    if (owns) {
-      double s[GEE_NQ];
-#pragma unroll
-      for (int q = 0; q < GEE_NQ; ++q) s[q] = sv[q][lo];
-      for (int i = (lo / GEE_SUB + 1) * GEE_SUB; i < hi; i += GEE_SUB) {
-#pragma unroll
-        for (int q = 0; q < GEE_NQ; ++q) s[q] += sv[q][i];
-      }
-#pragma unroll
-      for (int q = 0; q < GEE_NQ; ++q) a.Q[GEE_NQ * k + q] = s[q];
-    }
-    __syncthreads();  // the sums have read sv
+// v = d z | 1[pw > 0] | e | e^2 (common.hpp GeeKind)
+struct GeeRows {
+  static constexpr int NQ = GEE_NQ;
+  static __device__ __forceinline__ double values(const SegRowArgs& a, int64_t row, double pw, double (&v)[NQ]) {
+    if (pw > 0.0) v[1] = 1.0;
+    if (a.kind == GEE_COUNT) return 0.0;
+    const double eta = a.mode == MODE_IRLS ? a.eta[row] : 0.0;
+    const GeeRow g = gee_row(a.family, a.link, a.mode, eta, a.y[row], a.m ? a.m[row] : 1.0,
+                             a.off ? a.off[row] : 0.0, pw, a.mu0, a.theta);
+    v[0] = g.dz;
+    v[2] = g.e;
+    v[3] = g.e * g.e;
+    return a.kind == GEE_SCORE ? g.d * g.e : g.d;
   }
-}
+  static __device__ __forceinline__ void store(const SegRowArgs&, int64_t, const double (&)[NQ]) {}
+};
 
-__global__ void __launch_bounds__(256) gee_moments_kernel(GeeGroupArgs a) {
+__global__ void __launch_bounds__(SEG_NT) gee_rows_kernel(SegRowArgs a) { segment_rows<GeeRows>(a); }
+
+__global__ void __launch_bounds__(256) gee_moments_kernel(GroupArgs a) {
   __shared__ double sm[GEE_NM][256];
   const int t = threadIdx.x;
   double v[GEE_NM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -159,18 +102,18 @@ __global__ void __launch_bounds__(256) gee_nmax_kernel(const double* part, int n
   if (t == 0) out[M_NMAX] = sm[0];
 }
 
-__global__ void __launch_bounds__(256) gee_scale_kernel(GeeGroupArgs a) {
+__global__ void __launch_bounds__(256) gee_scale_kernel(GroupArgs a) {
   const int64_t total = a.ld * (a.p + 1);
   const double omr = 1.0 - a.rho;
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
     const int64_t g = t % a.ld;
     const int j = (int)(t / a.ld);  // j = p: the response
-    const double n = a.grp_s[(int64_t)(a.p + 1) * a.ld + g];
+    const double n = a.grp2[(int64_t)(a.p + 1) * a.ld + g];
     double v = 0.0;
     if (n > 0.0) {
       const double c = a.rho / (omr + n * a.rho);
       if (a.meat) {
-        if (j < a.p) v = (a.grp[t] - (c * a.grp_s[(int64_t)(a.p + 2) * a.ld + g]) * a.grp_s[t]) / omr;
+        if (j < a.p) v = (a.grp[t] - (c * a.grp2[(int64_t)(a.p + 2) * a.ld + g]) * a.grp2[t]) / omr;
       } else {
         v = sqrt(fabs(c)) * a.grp[t];
       }
@@ -186,15 +129,15 @@ int gee_moment_grid(int64_t G) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((G + 255) / 256, GEE_MOMENT_BLOCKS));
 }
 
-hipError_t launch_gee_rows(const GeeArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-  if (grid < 1 || !a.Q || !a.seg_start || !a.tile_seg || (a.kind != GEE_COUNT && (!a.d || !a.y)) ||
+hipError_t launch_gee_rows(const SegRowArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  if (grid < 1 || !a.Q || !a.seg_start || !a.tile_seg || (a.kind != GEE_COUNT && (!a.w || !a.y)) ||
       (a.kind != GEE_COUNT && a.mode == MODE_IRLS && !a.eta))
     return hipErrorInvalidValue;
-  hipExtLaunchKernelGGL(gee_rows_kernel, dim3(grid), dim3(GEE_NT), 0, st, e0, e1, 0, a);
+  hipExtLaunchKernelGGL(gee_rows_kernel, dim3(grid), dim3(SEG_NT), 0, st, e0, e1, 0, a);
   return hipGetLastError();
 }
 
-hipError_t launch_gee_moments(const GeeGroupArgs& a, double* out, hipStream_t st) {
+hipError_t launch_gee_moments(const GroupArgs& a, double* out, hipStream_t st) {
   if (a.G < 1 || a.ld < a.G || !a.grp || !a.partials || !out) return hipErrorInvalidValue;
   const int grid = gee_moment_grid(a.G);
   hipLaunchKernelGGL(gee_moments_kernel, dim3(grid), dim3(256), 0, st, a);
@@ -204,8 +147,8 @@ hipError_t launch_gee_moments(const GeeGroupArgs& a, double* out, hipStream_t st
   return hipGetLastError();
 }
 
-hipError_t launch_gee_scale(const GeeGroupArgs& a, hipStream_t st) {
-  if (a.ld < 1 || !a.grp || !a.grp_s || !a.X || !a.y) return hipErrorInvalidValue;
+hipError_t launch_gee_scale(const GroupArgs& a, hipStream_t st) {
+  if (a.ld < 1 || !a.grp || !a.grp2 || !a.X || !a.y) return hipErrorInvalidValue;
   const int64_t blocks = (a.ld * (a.p + 1) + 255) / 256;
   hipLaunchKernelGGL(gee_scale_kernel, dim3((unsigned)std::min<int64_t>(blocks, 65536)), dim3(256), 0, st, a);
   return hipGetLastError();

@@ -86,19 +86,19 @@ hipError_t launch_cluster_combine(const CombineArgs& a, int ncu, hipStream_t st,
 // fixed-effects IRLS (fe.hip): per-row weights / scores and their per-segment sums, the effective offset,
 // the fixed-effect update and the scaling of the group sums for the Gram pass over them
 int fe_grid(int ncu, int64_t ntiles);
-hipError_t launch_fe_weights(const FeArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+hipError_t launch_fe_weights(const SegRowArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 hipError_t launch_fe_offset(const FeOffsetArgs& a, int grid, hipStream_t st);
-hipError_t launch_fe_alpha(const FeGroupArgs& a, hipStream_t st);
-hipError_t launch_fe_scale(const FeGroupArgs& a, hipStream_t st);
+hipError_t launch_fe_alpha(const GroupArgs& a, hipStream_t st);
+hipError_t launch_fe_scale(const GroupArgs& a, hipStream_t st);
 
 // GEE fits (gee.hip): sqrt(w) / the scores and the four per-segment scalar sums, the moments of the group
 // buffer (partials [grid][NS], then out [NS]: launch_reduce_stats' sums with M_NMAX replaced by the maximum),
 // the scaling of the group sums for the Gram pass over them
 constexpr int GEE_MOMENT_BLOCKS = 1024;  // at most; the grid is a function of G alone
 int gee_moment_grid(int64_t G);
-hipError_t launch_gee_rows(const GeeArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-hipError_t launch_gee_moments(const GeeGroupArgs& a, double* out, hipStream_t st);
-hipError_t launch_gee_scale(const GeeGroupArgs& a, hipStream_t st);
+hipError_t launch_gee_rows(const SegRowArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+hipError_t launch_gee_moments(const GroupArgs& a, double* out, hipStream_t st);
+hipError_t launch_gee_scale(const GroupArgs& a, hipStream_t st);
 
 // two-way fixed effects (fe2.hip): the sums over factor 2's row lists, the gathers of the sweeps, the level
 // update with its stop-rule maxima, the cross product S_X' Y, the offset and the effects

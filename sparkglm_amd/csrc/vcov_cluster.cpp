@@ -242,11 +242,9 @@ int sglm_engine::cluster_sync() {
 // S summed over the handle's shards or ranks, a plain sum that leaves every rank (a group: shard 0)
 // with bitwise the same S: the group's RCCL all-reduce or its host sum in shard order, the engine's
 // RCCL communicator, or the caller's all-reduce on device or host buffers.
-int sglm::sum_cluster_scores(sglm_engine* h, int which) {
+int sglm::sum_cluster_scores(sglm_engine* h, const std::function<double*(sglm_engine*)>& buf, int64_t len) {
   const std::vector<sglm_engine*>& shards = h->shards();
   sglm_engine* s0 = shards[0];
-  const int64_t len = which == SUM_GEE ? s0->gee_len() : which == SUM_FE ? s0->fe_len() : s0->cluster_len();
-  auto buf = [which](sglm_engine* s) { return which == SUM_GEE ? s->dgg : which == SUM_FE ? s->dfg : s->cl_inner->dX; };
   if (h->group()) {
     const int D = (int)shards.size();
     if (!h->gcomms.empty()) {
@@ -427,7 +425,7 @@ int sglm_vcov_cluster(sglm_engine* h, const sglm_glm_opts* opts, const double* b
   // then hold other shards' sums, which this shard's next combine would not rewrite
   if (h->group() || h->comm.kind != 0)
     for (sglm_engine* s : shards) s->cl_S_stale = true;
-  if (int rc = sum_cluster_scores(h)) return rc;
+  if (int rc = sum_cluster_scores(h, [](sglm_engine* s) { return s->cl_inner->dX; }, shards[0]->cluster_len())) return rc;
   // M = S'S: the LM Gram pass of the internal engine over S -- every rank from the identical S
   sglm_engine* in = shards[0]->cl_inner;
   std::vector<double> packed((size_t)packed_len(p));

@@ -9,8 +9,12 @@ binomial logit (both init modes; with m; with an offset and prior weights that i
 Poisson log on counts with fractional values and values >= 256 (the reference rows beside the fast path and
 the tables; offset, prior weights with zeros, both init modes) and sqrt, Gamma inverse and log, negative
 binomial log and sqrt at theta = 2.
-Diagnostics and fixed effects (p = 5 and 65, the two-way designs of tests/fe2_reference.py): fit_glm_fe,
-fit_glm_fe2, influence (every residual type), vcov_robust and vcov_cluster at the plain fit's coefficients.
+Diagnostics and the steps over the cluster factor (p = 5 and 65, the two-way designs of tests/fe2_reference.py,
+every family): fit_glm_fe, fit_glm_fe2, fit_glm_gee (exchangeable, rho fixed at 0.2, independence), fe_pass and
+gee_pass at 0.8 beta and in the initial mode (the GEE fits stop after GEE_ITERS iterations at the latest), vcov_fe, vcov_fe2 and vcov_gee (with their meats), influence (every
+residual type), vcov_robust and vcov_cluster at the plain fit's coefficients.  At p = 5 also the interleaved and
+shuffled id layouts of tests/fe_reference.py, and one Poisson case on a group handle of two shards on one device
+(the host sum over shards, the stale mark of the group sums).
 A case that raises is recorded by its message, which must then be the same in every build."""
 import os
 import subprocess
@@ -21,6 +25,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 30_011
+GEE_ITERS = 25
 
 
 def _fit_vec(f):
@@ -105,12 +110,54 @@ def _fit_cases():
 
 def _guard(res, key, run):
     """run() -> {suffix: array}; an exception is recorded by its message."""
+    print("RUN", key, flush=True)
     try:
         for k, v in run().items():
             res[f"{key}:{k}"] = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
     except Exception as e:  # noqa: BLE001 -- the message is the result
         res[f"{key}:error"] = np.frombuffer(f"{type(e).__name__}: {e}".encode(), dtype=np.uint8)
         print("ERROR", key, e, flush=True)
+
+
+def _named(names, values):
+    return dict(zip(names, values))
+
+
+def _step_cases(res, e, key, fam, lnk, beta, two_way):
+    """The fits, steps and covariances over the cluster factor (and the second factor) on e's resident design."""
+    def fe1():
+        r = e.fit_glm_fe(fam, lnk)
+        return {"fit": _fit_vec(r.fit), "alpha": r.alpha, "G_eff": [r.G_eff]}
+
+    def fe2():
+        r = e.fit_glm_fe2(fam, lnk)
+        return {"fit": _fit_vec(r.fit), "alpha": r.alpha, "gamma": r.gamma}
+
+    _guard(res, key + ":fe", fe1)
+    if two_way:
+        _guard(res, key + ":fe2", fe2)
+    G = e._G()
+    b1, a1 = res.get(key + ":fe:fit", beta)[: e.p], res.get(key + ":fe:alpha", np.zeros(G))
+    for cl in (True, False):
+        _guard(res, f"{key}:vcov_fe:{int(cl)}", lambda: _named(
+            ("V", "meat"), e.vcov_fe(b1, a1, fam, lnk, cluster=cl, return_meat=True)))
+    if two_way and key + ":fe2:fit" in res:
+        _guard(res, key + ":vcov_fe2", lambda: _named(("V", "meat"), e.vcov_fe2(
+            res[key + ":fe2:fit"][: e.p], res[key + ":fe2:alpha"], res[key + ":fe2:gamma"], fam, lnk, return_meat=True)))
+    for b, tag in ((0.8 * beta, "beta"), (None, "init")):
+        _guard(res, f"{key}:fe_pass:{tag}", lambda: _named(
+            ("A", "b", "S", "t", "W", "scalars"), e.fe_pass(b, None if b is None else a1, fam, lnk, sums=True)))
+        _guard(res, f"{key}:gee_pass:{tag}", lambda: e.gee_pass(b, fam, lnk, sums=True))
+    # (GEE_ITERS: with rho re-estimated at every step a fit of these designs need not reach the default tol)
+    for tag, kw in (("exch", {}), ("rho", dict(rho=0.2)), ("ind", dict(corstr="independence"))):
+        def gee():
+            r = e.fit_glm_gee(fam, lnk, max_iter=GEE_ITERS, **kw)
+            return {"fit": _fit_vec(r.fit), "info": [r.rho, r.phi, r.N, r.G_eff, r.n_max]}
+        _guard(res, f"{key}:gee:{tag}", gee)
+    bg = res.get(key + ":gee:rho:fit", beta)[: e.p]
+    for rb in (True, False):
+        _guard(res, f"{key}:vcov_gee:{int(rb)}", lambda: _named(
+            ("V", "meat"), e.vcov_gee(bg, 0.2, fam, lnk, robust=rb, return_meat=True)))
 
 
 def child(out_path):
@@ -133,43 +180,48 @@ def child(out_path):
                   f"{time.perf_counter() - t0:.3f} s", flush=True)
 
         T = L.cluster_plan(np.zeros(0, dtype=np.int32), 1)[0]
-        for p in (5, 65):
+        for p, layout in ((5, "sorted"), (65, "sorted"), (5, "interleaved"), (5, "shuffled")):
             n = 2 * T + 1000 + 15 * (p % 7)
-            ids1, G = FR.make_ids("sorted", n, T)
+            ids1, G = FR.make_ids(layout, n, T)
             ids2, H = F2.make_ids2("random", ids1, G)
             for fam, lnk in (("binomial", "logit"), ("binomial", "probit"), ("poisson", "log"), ("poisson", "sqrt"),
                              ("gamma", "log"), ("gamma", "inverse"), ("gaussian", "identity"), ("negbin", "log"),
                              ("negbin", "sqrt")):
                 c = F2.make_case2(fam, lnk, n, p, ids1, G, ids2, H, 2)
-                key = f"diag:{fam}:{lnk}:{p}"
+                key = f"diag:{fam}:{lnk}:{p}" + ("" if layout == "sorted" else ":" + layout)
                 if fam == "negbin":
                     e.set_theta(2.0)
                 e.set_data(c["X"], c["y"], m=c["m"], offset=c["off"], prior=c["pw"])
                 e.set_clusters(ids1, G)
                 e.set_fe2(ids2, H)
-
-                def fe1():
-                    r = e.fit_glm_fe(fam, lnk)
-                    return {"fit": _fit_vec(r.fit), "alpha": r.alpha}
-
-                def fe2():
-                    r = e.fit_glm_fe2(fam, lnk)
-                    return {"fit": _fit_vec(r.fit), "alpha": r.alpha, "gamma": r.gamma}
-
-                _guard(res, key + ":fe", fe1)
-                _guard(res, key + ":fe2", fe2)
                 plain = {}
                 _guard(plain, "b", lambda: {"coefs": e.fit_glm(fam, lnk).coefs})
                 beta = plain.get("b:coefs", c["beta"])
                 res[key + ":beta"] = np.ascontiguousarray(beta)
-                for rt in ("deviance", "pearson", "working", "response"):
-                    def infl():
-                        r = e.influence(beta, fam, lnk, resid=rt)
-                        return {"hat": r.hat, "resid": r.resid, "cooks": r.cooks, "sum_hat": [r.sum_hat]}
-                    _guard(res, f"{key}:influence:{rt}", infl)
-                _guard(res, key + ":vcov_robust", lambda: {"V": e.vcov_robust(beta, fam, lnk, type="HC3")})
-                _guard(res, key + ":vcov_cluster", lambda: {"V": e.vcov_cluster(beta, fam, lnk, type="HC1")})
+                _step_cases(res, e, key, fam, lnk, beta, True)
+                if layout == "sorted":
+                    for rt in ("deviance", "pearson", "working", "response"):
+                        def infl():
+                            r = e.influence(beta, fam, lnk, resid=rt)
+                            return {"hat": r.hat, "resid": r.resid, "cooks": r.cooks, "sum_hat": [r.sum_hat]}
+                        _guard(res, f"{key}:influence:{rt}", infl)
+                    _guard(res, key + ":vcov_robust", lambda: {"V": e.vcov_robust(beta, fam, lnk, type="HC3")})
+                    _guard(res, key + ":vcov_cluster", lambda: {"V": e.vcov_cluster(beta, fam, lnk, type="HC1")})
                 print("CASE", key, flush=True)
+
+    # two shards on one device: the sums over shards go through the host, and the group sums turn stale
+    with Engine(devices=[0, 0]) as e:
+        p, n = 5, 2 * T + 1000 + 15 * 5
+        ids1, G = FR.make_ids("sorted", n, T)
+        ids2, H = F2.make_ids2("random", ids1, G)
+        c = F2.make_case2("poisson", "log", n, p, ids1, G, ids2, H, 2)
+        e.set_data(c["X"], c["y"], m=c["m"], offset=c["off"], prior=c["pw"])
+        e.set_clusters(ids1, G)
+        key = "diag:poisson:log:5:group"
+        _guard(res, key, lambda: {"beta": e.fit_glm("poisson", "log").coefs})
+        _step_cases(res, e, key, "poisson", "log", res.get(key + ":beta", c["beta"]), False)
+        _guard(res, key + ":vcov_cluster", lambda: {"V": e.vcov_cluster(res.get(key + ":beta", c["beta"]), "poisson", "log")})
+        print("CASE", key, flush=True)
     np.savez(out_path, **res)
 
 
