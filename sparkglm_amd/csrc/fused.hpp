@@ -733,11 +733,52 @@ __device__ __forceinline__ void stage_block_r(double* lds, int buf, const PassAr
 // every stripe, then u = 2, 3 -- the order K1 adds them in) and beta from a per-lane-group copy
 // (betag: the 32 betas of lane group g contiguous, 16 ds_read_b128 instead of 32 ds_read_b64;
 // groups 34 doubles apart so that the eight groups' broadcasts hit distinct banks).
-template <int P16, int FAM, int LNK>
+//
+// P16 = 16 (SGLM_K1R_BREG=0 / SGLM_K1R_PUB=0 build without either, for A/B timing):
+// the chain landed -> row stage -> ready -> the block's MFMAs -> done is what the block period waits
+// for, and under the Gram waves' MFMA streams a row wave's LDS round trips and fp64 VALU instructions
+// wait for both.  So the lane group's 32 betas stay in registers for the whole launch (breg, loaded
+// once from betag), and w, w*z and eta are stored and `publish` (the bump of ready) runs before the
+// logit fast path's unit deviance -- which then runs while the Gram waves fetch the block's first
+// operands.  The products, their order and every lane's s_dev / s_aux additions are the ones above.
+// (Measured and not kept: the 32 X reads as one round trip, 16 issued ahead and one more per FMA --
+// more ahead spills -- profiles/k1r_rowstage_ab.txt.)
+#ifndef SGLM_K1R_BREG
+#define SGLM_K1R_BREG 1
+#endif
+#ifndef SGLM_K1R_PUB
+#define SGLM_K1R_PUB 1
+#endif
+template <int P16>
+struct RowRegs {
+  static constexpr bool BREG = P16 == 16 && SGLM_K1R_BREG;
+  static constexpr int N = BREG ? GeoR<P16>::CPG * GeoR<P16>::NT : 1;
+  template <int FAM, int LNK>
+  static constexpr bool defer_dev() {
+    return P16 == 16 && SGLM_K1R_PUB && FAM == FAM_BINOMIAL && LNK == LNK_LOGIT;
+  }
+};
+// breg[u * NT + t] = beta[CPG g + u + 32 t] of the lane's group g
+template <int P16>
+__device__ __forceinline__ void row_betas_r(const double* lds, int lane, double (&breg)[RowRegs<P16>::N]) {
+  using R = GeoR<P16>;
+  breg[0] = 0.0;
+  if constexpr (RowRegs<P16>::BREG) {
+    const double* bg = lds + R::OFF_BETAG + (lane / R::RW) * R::BETAG_STRIDE;
+#pragma unroll
+    for (int t = 0; t < R::NT; ++t)
+#pragma unroll
+      for (int u = 0; u < R::CPG; ++u) breg[u * R::NT + t] = bg[t * R::CPG + u];
+  }
+}
+
+template <int P16, int FAM, int LNK, class ST, class PUB>
 __device__ __forceinline__ void row_stage_r(double* lds, int buf, const PassArgs& a, int64_t blk, int rw, int lane,
-                                            double& s_dev, double& s_aux) {
+                                            const double (&breg)[RowRegs<P16>::N], double& s_dev, double& s_aux,
+                                            ST& st, PUB publish) {
   using G = Geo<P16>;
   using R = GeoR<P16>;
+  using RR = RowRegs<P16>;
   constexpr int RW = R::RW, CPG = R::CPG, NT = R::NT;
   static_assert(P16 != 16 || (G::RW == RW && G::CPG == CPG && NT == 8), "K1's P16 = 16 row-stage geometry");
   const double* xs = lds + R::OFF_X + buf * R::XB;
@@ -763,21 +804,28 @@ __device__ __forceinline__ void row_stage_r(double* lds, int buf, const PassArgs
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           xv[uu][t] = base[2 * G::BSTR * t];
-          bv[uu][t] = bg[t * CPG + u];
+          if constexpr (RR::BREG) bv[uu][t] = breg[u * NT + t];
+          else bv[uu][t] = bg[t * CPG + u];
         }
       }
 #pragma unroll
       for (int uu = 0; uu < 2; ++uu)
 #pragma unroll
         for (int t = 0; t < NT; ++t) e4[t & 3] += xv[uu][t] * bv[uu][t];
-      __builtin_amdgcn_sched_group_barrier(0x100, 3 * NT, 2);
+      __builtin_amdgcn_sched_group_barrier(0x100, (RR::BREG ? 2 : 3) * NT, 2);
       __builtin_amdgcn_sched_group_barrier(0x002, 2 * NT, 2);
+      if (h == 0) st.ev(4);
     }
     eta = (e4[0] + e4[1]) + (e4[2] + e4[3]);
     if constexpr (RW <= 8) eta = add_xor8(eta);
     eta = add_xor16(eta);
     eta = add_xor32(eta);
+    st.ev(5);
   }
+  // the logit fast path's rows (P16 = 16): the unit deviance follows the hand-off, from the row's e, u, t
+  constexpr bool DEFER = RR::template defer_dev<FAM, LNK>();
+  bool dev_due = false;
+  LogitEUT eut{};
   if (lane < RW) {
     const int64_t row = blk * RB + r;
     double w = 0.0, wz = 0.0;
@@ -785,8 +833,12 @@ __device__ __forceinline__ void row_stage_r(double* lds, int buf, const PassArgs
       if (a.mode == MODE_IRLS) eta = eta + off;
       if (FAM == FAM_BINOMIAL && init_fast_row(FAM, a.mode, a.m != nullptr) && y >= 0.0 && y <= 1.0)
         pass_row_init(lds + R::OFF_INIT, y, off, pw, w, wz, s_dev, s_aux);
-      else pass_row(FAM, LNK, a.mode, eta, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
-                    false, nullptr, a.link, a.theta);
+      else if (DEFER && logit_fast_row(a.mode, a.m != nullptr, eta, y)) {
+        eut = logit_row_wz(eta, y, off, pw, true, w, wz);  // pass_row's logit_row, its first half
+        dev_due = true;
+      } else
+        pass_row(FAM, LNK, a.mode, eta, y, m, off, pw, a.mu0, a.ybar, a.m != nullptr, w, wz, s_dev, s_aux, true,
+                 false, nullptr, a.link, a.theta, DEFER);
     }
     lds[R::OFF_W + buf * 2 * RB + r] = w;
     lds[R::OFF_W + buf * 2 * RB + RB + r] = wz;
@@ -794,19 +846,34 @@ __device__ __forceinline__ void row_stage_r(double* lds, int buf, const PassArgs
     // vector-memory operations are their LDS-DMA and vmcnt counts exactly the blocks in flight
     lds[R::OFF_ETA + buf * RB + r] = eta;
   }
+  st.ev(6);
+  publish();
+  if constexpr (DEFER) {
+    // neither the stores sink below the log chain nor the chain rises above the hand-off
+    __builtin_amdgcn_sched_barrier(0);
+    if (dev_due) logit_row_dev(eut, eta, y, pw, s_dev, s_aux);
+  }
 }
 
 // Per-phase cycle sums of K1r's waves (s_memtime), a development build only: make variant
 // NAME=stamps DEFS=-DSGLM_K1R_STAMPS=1 (2: also the first k-step of every block), read back by
 // tools/k1r_stamps.py through sglm_k1r_stamps (kernels.hip).  Every wave of the middle workgroup
 // sums the cycles between its laps and stores the sums with ordinary vector stores at the end of
-// the kernel.  Row waves: 0 wait_landed, 1 flag round, 2 row stage, 3 wait for ready (tail blocks),
+// the kernel.  Row waves: 0 wait_landed, 1 flag round (P16 = 16, which has none: the deviance a row
+// stage forms after its hand-off), 2 row stage (to the bump of ready), 3 wait for ready (tail blocks),
 // 4 X'Wz, 5 wait for done, 6 DMA issue; Gram waves: 0 wait for ready, 1 the block's k-steps (2: the
 // first of them, taken out of 1), 3 eta store and done, and where they issue the DMA (P16 = 16) 8 wait
 // for done, 9 DMA issue, 10 landing; slot 15 of every wave: its blocks.  lap_h also counts the lap by
 // its length (Gram waves: wait for ready in slots 4-7; row waves: wait_landed 7-10, flag round 11-14).  Each
 // lap waits for the wave's outstanding LDS operations, so it sits only where the wave has none
 // by construction (level 2 puts one inside the Gram block and is for the k-step profile only).
+// Level 3 is the event timeline instead of the sums: for one block B of the middle workgroup (the
+// middle one of its range) every wave records the s_memtime of each hand-off of B, ev(i) while
+// watch(blk) holds, and stores them in place of the sums (slot i; 0 = not recorded).  Gram waves 0..3:
+// 0 done(B - 2) seen, 1 DMA of B issued, 2 landed bumped; row waves: 3 landed seen, 4 eta's first LDS
+// round trip back, 5 eta reduced, 6 w, w*z, eta stored, 7 ready bumped, 12 the
+// deferred deviance formed; every wave: 8 ready seen, 11 done bumped; Gram waves: 9 first k-step's
+// MFMAs issued, 10 last k-step's.  tools/k1r_stamps.py prints them against the earliest one.
 #ifndef SGLM_K1R_STAMPS
 #define SGLM_K1R_STAMPS 0
 #endif
@@ -817,6 +884,21 @@ static __device__ unsigned long long k1r_stamps[12 * K1R_STAMP_SLOTS];
 struct StampsR {
 #if SGLM_K1R_STAMPS
   unsigned long long t = 0, s[K1R_STAMP_SLOTS] = {};
+  long long tb = -1;  // level 3: the block whose events are recorded
+  bool on = false;
+  __device__ __forceinline__ void pick(long long b0, long long b1) {
+    if (SGLM_K1R_STAMPS == 3 && b1 - b0 >= 6) tb = b0 + (b1 - b0) / 2;
+  }
+  __device__ __forceinline__ void watch(long long blk) { on = SGLM_K1R_STAMPS == 3 && blk == tb; }
+  __device__ __forceinline__ void ev(int i) {
+    if (SGLM_K1R_STAMPS == 3 && on) s[i] = __builtin_amdgcn_s_memtime();
+  }
+#if SGLM_K1R_STAMPS == 3
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ void lap(int) {}
+  __device__ __forceinline__ void lap_h(int, int) {}
+  __device__ __forceinline__ void count() {}
+#else
   __device__ __forceinline__ void start() { t = __builtin_amdgcn_s_memtime(); }
   __device__ __forceinline__ void lap(int i) {
     const unsigned long long now = __builtin_amdgcn_s_memtime();
@@ -833,6 +915,7 @@ struct StampsR {
     for (int k = 0; k < 4; ++k) s[h + k] += b == k;
   }
   __device__ __forceinline__ void count() { s[K1R_STAMP_SLOTS - 1] += 1; }
+#endif
   __device__ __forceinline__ void flush(int wv, int lane) {
     if (blockIdx.x == gridDim.x / 2 && lane < K1R_STAMP_SLOTS) {
       unsigned long long v = 0;
@@ -843,6 +926,9 @@ struct StampsR {
     }
   }
 #else
+  __device__ __forceinline__ void pick(long long, long long) {}
+  __device__ __forceinline__ void watch(long long) {}
+  __device__ __forceinline__ void ev(int) {}
   __device__ __forceinline__ void start() {}
   __device__ __forceinline__ void lap(int) {}
   __device__ __forceinline__ void lap_h(int, int) {}
@@ -893,7 +979,8 @@ __device__ __forceinline__ void gram_steps_r(const double* lds, int buf, int lan
     // arbitration: waves 0-3 finished their Gram ~7K cycles before waves 4-7)
     if constexpr (!T::ROW) __builtin_amdgcn_s_setprio((WV >> 2) & 1 ? 0 : 1);
     kstep(j);
-    if (SGLM_K1R_STAMPS >= 2 && j == 0) st.lap(2);
+    if (SGLM_K1R_STAMPS == 2 && j == 0) st.lap(2);
+    if (SGLM_K1R_STAMPS == 3 && j == 0) st.ev(9);
     if constexpr (!T::ROW) __builtin_amdgcn_s_setprio((WV >> 2) & 1 ? 1 : 0);
     kstep(j + 1);
   }
@@ -997,7 +1084,10 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
   };
   auto next_buf = [](int b) { return b + 1 == NB ? 0 : b + 1; };
   StampsR st;
+  st.pick(b0, b1);
   st.start();
+  double breg[RowRegs<P16>::N];
+  if constexpr (row_wave) row_betas_r<P16>(lds, lane, breg);
   if constexpr (row_wave) {
     // row stages of the first LA blocks (slots 0 .. LA-1), each after its flag round
 #pragma unroll
@@ -1010,8 +1100,7 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
           bump(flag);
           spin(flag, 4u * (c + 1));
         }
-        row_stage_r<P16, FAM, LNK>(lds, c, a, b0 + c, si, lane, s_dev, s_aux);
-        bump(ready + c);
+        row_stage_r<P16, FAM, LNK>(lds, c, a, b0 + c, si, lane, breg, s_dev, s_aux, st, [&] { bump(ready + c); });
       }
     }
     int cur = 0;
@@ -1023,9 +1112,11 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
           int sl = cur + LA;
           unsigned rs = rnd;  // uses of slot sl before block blk + LA
           if (sl >= NB) sl -= NB, ++rs;
+          st.watch(blk + LA);
           if constexpr (GDMA) {
             spin(landed(sl), 4u * (rs + 1));
             st.lap_h(0, 7);
+            st.ev(3);
           } else {
             wait_landed(std::min<int64_t>(b1 - 1, blk + NB - 1) - (blk + LA));
             st.lap_h(0, 7);
@@ -1033,9 +1124,16 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
             spin(flag, (unsigned)(4 * (blk + LA - b0 + 1)));
             st.lap_h(1, 11);
           }
-          row_stage_r<P16, FAM, LNK>(lds, sl, a, blk + LA, si, lane, s_dev, s_aux);
-          bump(ready + sl);
-          st.lap(2);
+          // (the deviance a row stage defers past its hand-off is counted under the flag round's name)
+          row_stage_r<P16, FAM, LNK>(lds, sl, a, blk + LA, si, lane, breg, s_dev, s_aux, st, [&] {
+            bump(ready + sl);
+            st.ev(7);
+            st.lap(2);
+          });
+          if constexpr (RowRegs<P16>::template defer_dev<FAM, LNK>()) {
+            st.lap(1);
+            st.ev(12);
+          }
         }
       };
       // GDMA: X'Wz first -- done(blk) is what the DMA of block blk + 2 waits for
@@ -1045,9 +1143,12 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
       // (GDMA: no flag round among the row waves, every block waits for ready)
       if (GDMA || blk + LA >= b1) spin(ready + cur, (unsigned)(RG * (rnd + 1)));
       st.lap(3);
+      st.watch(blk);
+      st.ev(8);
       if (do_gram) xz_rows_r<P16, si>(lds, cur, lane, xz);
       bump(done + cur);  // this row wave's reads of block blk (X'Wz) are complete
       st.lap(4);
+      st.ev(11);
       if constexpr (GDMA) row_stage_ahead();
       if constexpr (!GDMA)
         if (blk + NB < b1) {
@@ -1073,22 +1174,30 @@ __device__ __forceinline__ void pass_body_r(double* lds, const PassArgs& a, int 
     for (int64_t blk = b0; blk < b1; ++blk) {
       spin(ready + cur, (unsigned)(RG * (rnd + 1)));
       st.lap_h(0, 4);
+      st.watch(blk);
+      st.ev(8);
       if (do_gram) gram_steps_r<P16, WV>(lds, cur, lane, acc, st);
       st.lap(1);
+      st.ev(10);
       if constexpr (WV == 0)  // the row stage's eta of this block (IRLS passes that keep it)
         if (a.eta_out && a.mode == MODE_IRLS && lane < RB && blk * RB + lane < a.n)
           a.eta_out[blk * RB + lane] = lds[R::OFF_ETA + cur * RB + lane];
       bump(done + cur);
       st.lap(3);
+      st.ev(11);
       if constexpr (GDMA && issuer)
         if (blk + NB < b1) {
+          st.watch(blk + NB);
           spin(done + cur, 12u * (rnd + 1));
           st.lap(8);
+          st.ev(0);
           stage(cur, blk + NB);
           st.lap(9);
+          st.ev(1);
           wait_vm<0>();
           bump(landed(cur));
           st.lap(10);
+          st.ev(2);
         }
       st.count();
       cur = next_buf(cur);

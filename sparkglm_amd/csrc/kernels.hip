@@ -631,4 +631,6 @@ extern "C" int sglm_k1r_stamps(unsigned long long* out, int n) {
   if (n != 12 * sglm::K1R_STAMP_SLOTS || hipDeviceSynchronize() != hipSuccess) return -1;
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(sglm::k1r_stamps), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -1;
 }
+// 1, 2: the sums; 3: the event timeline of one block in their place
+extern "C" int sglm_k1r_stamps_level(void) { return SGLM_K1R_STAMPS; }
 #endif

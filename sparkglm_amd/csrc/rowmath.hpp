@@ -360,21 +360,41 @@ __device__ __forceinline__ void pass_row_init(const double* c, double y, double 
 // STATS: Breeze's Binomial(1, mu).logProbabilityOf(k) = k log mu + (1-k) log(1-mu) with log mu = -log1p(e),
 // log(1-mu) = -eta - log1p(e); |eta| < 8 keeps mu off 0 and 1 (no special cases, k in {0, 1}).
 #define SGLM_LOGIT_FAST(eta, y) (fabs(eta) < 8.0 && (y) >= 0.0 && (y) <= 1.0)
+// The row in two halves, so that a caller can hand w and w*z on before the deviance's log is formed
+// (K1r's row stage, fused.hpp row_stage_r): logit_row_wz leaves e, u, t and v for logit_row_dev.
+struct LogitEUT {
+  double e, u, t, v;
+};
+__device__ __forceinline__ bool logit_fast_row(int mode, bool has_m, double eta, double y) {
+  return mode == MODE_IRLS && !has_m && SGLM_LOGIT_FAST(eta, y);  // pass_row's condition
+}
+__device__ __forceinline__ LogitEUT logit_row_wz(double eta, double y, double off, double pw, bool small_exp,
+                                                 double& w, double& wz) {
+  LogitEUT c;
+  c.e = small_exp ? exp_small(-eta) : exp(-eta);
+  c.u = 1.0 + c.e;
+  c.t = rcp_pos(c.u);
+  c.v = c.e * c.t * c.t;
+  w = pw * c.v;
+  wz = pw * (c.v * (eta - off) + (y - c.t));
+  return c;
+}
+// (returns L = log1p(e) = -log(mu))
+__device__ __forceinline__ double logit_row_dev(const LogitEUT& c, double eta, double y, double pw, double& s_dev,
+                                                double& s_aux) {
+  const double L = fma(c.e - (c.u - 1.0), c.t, log_pos(c.u));
+  s_dev += pw * (L + (1.0 - y) * eta);
+  s_aux += pw;
+  return L;
+}
 template <bool STATS>
 __device__ __forceinline__ void logit_row(double eta, double y, double off, double pw, bool small_exp, double& w,
                                           double& wz, double& s_dev, double& s_aux, double& s_pear, double& s_ll) {
-  const double e = small_exp ? exp_small(-eta) : exp(-eta);
-  const double u = 1.0 + e;
-  const double t = rcp_pos(u);
-  const double v = e * t * t;
-  w = pw * v;
-  wz = pw * (v * (eta - off) + (y - t));
-  const double L = fma(e - (u - 1.0), t, log_pos(u));  // log1p(e) = -log(mu)
-  s_dev += pw * (L + (1.0 - y) * eta);
-  s_aux += pw;
+  const LogitEUT c = logit_row_wz(eta, y, off, pw, small_exp, w, wz);
+  const double L = logit_row_dev(c, eta, y, pw, s_dev, s_aux);
   if constexpr (STATS) {
-    const double r = y - t;
-    s_pear += pw * (r * r) * rcp_pos(v);
+    const double r = y - c.t;
+    s_pear += pw * (r * r) * rcp_pos(c.v);
     s_ll += pw * ((int)y == 1 ? -L : -L - eta);
   }
 }
@@ -459,10 +479,12 @@ __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta,
                                          double pw, double mu0, double ybar, bool has_m, double& w, double& wz,
                                          double& s_dev, double& s_aux, bool small_exp = false,
                                          bool init_fast = false, const double* ylogy = nullptr, int rt_link = 0,
-                                         double theta = 0.0) {
+                                         double theta = 0.0, bool logit_fast_elsewhere = false) {
   (void)ybar;
   double nil;  // the statistics sums of the fast paths: not formed here (STATS = false)
-  if (fam == FAM_BINOMIAL && lnk == LNK_LOGIT && mode == MODE_IRLS && !has_m && SGLM_LOGIT_FAST(eta, y)) {
+  // (logit_fast_elsewhere: the caller took the logit fast rows itself, in halves -- K1r's row stage)
+  if (!logit_fast_elsewhere && fam == FAM_BINOMIAL && lnk == LNK_LOGIT && mode == MODE_IRLS && !has_m &&
+      SGLM_LOGIT_FAST(eta, y)) {
     logit_row<false>(eta, y, off, pw, small_exp, w, wz, s_dev, s_aux, nil, nil);
     return;
   }
