@@ -74,7 +74,8 @@ extern "C" {
                               sglm_fit_glm_fe2 (with sglm_fe2_opts / sglm_fe2_info), sglm_fe2_pass,
                               sglm_vcov_fe2, sglm_get_fe2_ms, sglm_fit_glm_gee (with sglm_gee_opts /
                               sglm_gee_info, enum sglm_corstr), sglm_gee_pass, sglm_vcov_gee,
-                              sglm_get_gee_ms; (new values only:) SGLM_SQRT and
+                              sglm_get_gee_ms, sglm_fit_glm_firth (with sglm_firth_opts / sglm_firth_info),
+                              sglm_firth_pass, sglm_get_firth_ms; (new values only:) SGLM_SQRT and
                               the non-canonical (family, link) pairs of enum sglm_link's table,
                               SGLM_NEGBIN and its three pairs */
 
@@ -670,6 +671,51 @@ int sglm_vcov_gee(sglm_engine *h, const sglm_glm_opts *opts, const sglm_gee_opts
 /* Kernel times of the last GEE step, ms [4]: rows, segment sums, combine, the Gram pass over the group sums
  * (HIP events; -1 before any call). */
 int sglm_get_gee_ms(sglm_engine *h, double *ms);
+
+/* ---- Firth's bias-reduced fits (Firth 1993; logistf::logistf, brglm2::brglmFit(type = "AS_mean"), Stata
+ * firthlogit): finite estimates under complete or quasi-complete separation, and the first-order bias of the ML
+ * estimate removed ----
+ * For binomial (logit, probit, cloglog) and poisson (log, identity, sqrt) -- the phi = 1 families -- on a resident
+ * design with p <= 256.  The adjusted score at beta, on the engine's scales (binomial mu = m pi, prior weights,
+ * offset), is
+ *   g*(beta) = sum_i (u_i + h_i r_i / 2) x_i,  u_i = w_i (y_i - mu_i) g'(mu_i),  h_i = w_i x_i' inv(X'WX) x_i,
+ *   r = (d2mu / deta2) / (dmu / deta): logit 1 - 2 pi, probit -eta, cloglog 1 - e^eta, log 1, sqrt 1 / eta, identity 0
+ * -- for the canonical links the gradient of l(beta) + log det(X'WX) / 2 (the Jeffreys penalty).  A row of prior
+ * weight 0 contributes exactly 0.  The fit iterates beta <- beta + inv(X'WX) g*(beta) from beta_start, or else
+ * from sglm_fit_glm's first iterate (the initial pass of opts->init_mode and its solve), and stops with beta when
+ * |inv(X'WX) g*|_1 < epsilon; a step after which |g*|_inf is not finite or larger than before is retried at half
+ * its length, at most max_halvings times (then the last trial stands).  opts->tol and opts->max_iter are not read.
+ * SGLM_EINVAL, before the handle is looked at: another family, epsilon <= 0 or not finite, maxit < 0; then a
+ * procedural shard, p > 256 or SGLM_FORCE_WIDE.  Collective over a communicator, multi-device handles included;
+ * two calls on the same shape and device give bitwise the same results (no floating-point atomics). */
+typedef struct {
+  double epsilon;   /* stop when the step's 1-norm is below it; R's brglmControl default 1e-8 */
+  int maxit;        /* at most this many steps; 100 */
+  int max_halvings; /* per step; 12 */
+} sglm_firth_opts;
+typedef struct {
+  int iterations;      /* steps taken */
+  int converged;       /* 0: maxit steps without meeting epsilon -- a returned status, not an error */
+  int halvings;        /* over all steps */
+  double deviance;     /* D at the returned coefficients */
+  double pen_deviance; /* D* = D - log det(X'WX) */
+  double logdet;       /* log det(X'WX) */
+  double score_inf;    /* |g*|_inf */
+  double sum_hat;      /* sum h_i (= p up to rounding) */
+  double firth_ms;     /* kernel time of the last Firth pass, as sglm_get_firth_ms */
+  double pass_ms;      /* kernel time of the last ordinary pass (the slowest shard) */
+} sglm_firth_info;
+/* Every returned quantity is evaluated at the returned coefficients: std_err = sqrt(diag(inv(X'WX))), deviance,
+ * pearson, loglik (the unpenalised one); null_deviance and dev_trace as sglm_fit_glm (one entry per step);
+ * iter = info->iterations.  firth_opts NULL: the defaults above; beta_start and info may be NULL. */
+int sglm_fit_glm_firth(sglm_engine *h, const sglm_glm_opts *opts, const sglm_firth_opts *firth_opts,
+                       const double *beta_start, sglm_preglm *out, sglm_firth_info *info);
+/* The test-level pass at beta: A [p*p] col-major = X'WX, g [p] = g*, hat [n_local] = h (a multi-device handle:
+ * every shard's rows, in row order), scalars [3] = deviance, log det A, sum h; any output may be NULL. */
+int sglm_firth_pass(sglm_engine *h, const sglm_glm_opts *opts, const double *beta, double *A, double *g, double *hat,
+                    double *scalars);
+/* Kernel time of the last Firth pass, ms (HIP events; the slowest shard; -1 before any call). */
+int sglm_get_firth_ms(sglm_engine *h, double *ms);
 
 int sglm_get_stats(sglm_engine *h, sglm_stats *out);
 /* The kernel an engine would run a pass of an n x p shard with (enum sglm_pass_kernel, -1 on bad

@@ -44,6 +44,7 @@ EXPORTS = [
     "sglm_fit_glm_fe", "sglm_fe_pass", "sglm_vcov_fe", "sglm_get_fe_ms",
     "sglm_set_fe2", "sglm_fe2_plan", "sglm_fit_glm_fe2", "sglm_fe2_pass", "sglm_vcov_fe2", "sglm_get_fe2_ms",
     "sglm_fit_glm_gee", "sglm_gee_pass", "sglm_vcov_gee", "sglm_get_gee_ms",
+    "sglm_fit_glm_firth", "sglm_firth_pass", "sglm_get_firth_ms",
 ]
 PREDICT_LINK, PREDICT_RESPONSE = 0, 1
 RESID_TYPES = {"response": 0, "working": 1, "pearson": 2, "deviance": 3}  # enum sglm_resid_type
@@ -98,6 +99,20 @@ class GeeInfo(C.Structure):
     _fields_ = [("rho", C.c_double), ("phi", C.c_double), ("N", C.c_double), ("G_eff", C.c_int32),
                 ("n_max", C.c_int32), ("rows_ms", C.c_double), ("sum_ms", C.c_double), ("combine_ms", C.c_double),
                 ("gram_ms", C.c_double)]
+
+
+# the (family, link) pairs of a Firth fit: the phi = 1 families
+FIRTH_LINKS = {"binomial": ("logit", "probit", "cloglog"), "poisson": ("log", "identity", "sqrt")}
+
+
+class FirthOpts(C.Structure):
+    _fields_ = [("epsilon", C.c_double), ("maxit", C.c_int), ("max_halvings", C.c_int)]
+
+
+class FirthInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("halvings", C.c_int), ("deviance", C.c_double),
+                ("pen_deviance", C.c_double), ("logdet", C.c_double), ("score_inf", C.c_double),
+                ("sum_hat", C.c_double), ("firth_ms", C.c_double), ("pass_ms", C.c_double)]
 
 
 class PreLM(C.Structure):
@@ -261,6 +276,10 @@ def load():
         "sglm_vcov_gee": ([h, C.POINTER(GlmOpts), C.POINTER(GeeOpts), dp, C.c_double, C.c_int, C.c_int, dp, dp],
                           C.c_int),
         "sglm_get_gee_ms": ([h, dp], C.c_int),
+        "sglm_fit_glm_firth": ([h, C.POINTER(GlmOpts), C.POINTER(FirthOpts), dp, C.POINTER(PreGLM),
+                                C.POINTER(FirthInfo)], C.c_int),
+        "sglm_firth_pass": ([h, C.POINTER(GlmOpts), dp, dp, dp, dp, dp], C.c_int),
+        "sglm_get_firth_ms": ([h, dp], C.c_int),
         "sglm_cluster_plan": ([C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int64),
                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
     }

@@ -232,6 +232,9 @@ struct InflArgs {
   // FAM_NEGBIN: the dispersion parameter.  hc_k took the block's only 4-byte gap and a double needs 8, so
   // theta goes last: every other field keeps its offset.
   double theta;
+  // firth_kernel: per-workgroup partials [grid][p + 1] of the adjusted score and, last, the sum of h; past the
+  // fused widths out [n] receives v for firth_xtv_kernel.  After theta: every other field keeps its offset.
+  double* gpart;
 };
 
 // Cluster sums S[g, :] = sum_{i: id_i = g} u_i x_i (cluster.hip).  A segment is a

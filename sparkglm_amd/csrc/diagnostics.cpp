@@ -11,7 +11,8 @@ using namespace sglm;
 
 void sglm_engine::free_influence() {
   omega_cap = 0;
-  dev_free({&dct, &dinf[0], &dinf[1], &dinf[2], &dhpart, &domega});
+  dev_free({&dct, &dinf[0], &dinf[1], &dinf[2], &dhpart, &domega, &dgpart});
+  gpart_cap = 0;
   if (hct) (void)hipHostFree(hct);
   hct = nullptr;
   inf_cap[0] = inf_cap[1] = inf_cap[2] = 0;
@@ -90,6 +91,43 @@ int sglm_engine::influence_local(const double* beta, const double* cov, int fami
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, evi0, evi1));
   influence_ms = ms;
+  return SGLM_OK;
+}
+
+// Firth's adjusted score of this shard's rows (firth.cpp): g = g* [p] | sum of h, the workgroups' partials added on
+// the device in a fixed order; hat as influence_local's.  Past the fused widths v goes through domega.
+int sglm_engine::firth_local(const double* beta, const double* cov, int family, int link, double* g, double* hat) {
+  HIPCHK(hipSetDevice(device));
+  if (int rc = check_loaded()) return rc;
+  std::fill(g, g + p + 1, 0.0);
+  firth_ms = 0.0;
+  if (n == 0) return SGLM_OK;
+  if (hat)
+    if (int rc = grow(dinf[0], inf_cap[0], n_pad, "hipMalloc(diagnostics vector)")) return rc;
+  const int P = (int)((p + 15) / 16);
+  const int grid = firth_grid(P, ncu, n);
+  if (int rc = grow(dgpart, gpart_cap, (int64_t)(grid + 1) * (p + 1), "hipMalloc(adjusted-score partials)")) return rc;
+  if (!firth_is_fused(P))
+    if (int rc = grow(domega, omega_cap, n_pad, "hipMalloc(score weights)")) return rc;
+  if (!evi0) HIPCHK(hipEventCreate(&evi0));
+  if (!evi1) HIPCHK(hipEventCreate(&evi1));
+  if (int rc = upload_cov(cov, p)) return rc;
+  std::memcpy(hbeta, beta, sizeof(double) * p);
+  HIPCHK(hipMemcpyAsync(dbeta, hbeta, sizeof(double) * p, hipMemcpyHostToDevice, st));
+  InflArgs a = resident_args(*this, family, link);
+  a.need_q = 1;
+  a.hat = hat ? dinf[0] : nullptr;
+  a.out = domega;
+  a.gpart = dgpart;
+  double* sum = dgpart + (int64_t)grid * (p + 1);
+  HIPCHK(launch_firth(P, a, grid, st, evi0, evi1));
+  HIPCHK(launch_firth_sum(dgpart, grid, (int)p, sum, st));
+  HIPCHK(hipMemcpyAsync(g, sum, sizeof(double) * (size_t)(p + 1), hipMemcpyDeviceToHost, st));
+  if (hat) HIPCHK(hipMemcpyAsync(hat, dinf[0], sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, evi0, evi1));
+  firth_ms = ms;
   return SGLM_OK;
 }
 

@@ -83,6 +83,10 @@ int HostSolver::inverse(double* Ainv) {
   impl_->s.inverse(Ainv);
   return SGLM_OK;
 }
+int HostSolver::logdet(double* out) {
+  *out = impl_->s.logdet(gram_.data());
+  return SGLM_OK;
+}
 int HostSolver::path() const {
   return !impl_->s.has_factor() ? -1 : impl_->s.used_lu() ? SGLM_SOLVE_HOST_LU : SGLM_SOLVE_HOST_CHOL;
 }

@@ -23,6 +23,12 @@ class SolverIface {
   virtual int solve(const double* packed, double* x) = 0;
   virtual int inv_diag(double* d) = 0;
   virtual int inverse(double* Ainv) = 0;
+  // log |det| of the last solve's matrix (the host solver only: Firth's penalty, p <= 256)
+  virtual int logdet(double* out) {
+    (void)out;
+    set_error("requirement failed: the log determinant needs the host solver");
+    return SGLM_EINVAL;
+  }
   // enum sglm_solve_path of the last solve (-1 before any)
   virtual int path() const = 0;
 };
@@ -35,6 +41,7 @@ class HostSolver : public SolverIface {
   int solve(const double* packed, double* x) override;
   int inv_diag(double* d) override;
   int inverse(double* Ainv) override;
+  int logdet(double* out) override;
   int path() const override;
 
  private:

@@ -1,6 +1,6 @@
 // engine.hpp -- the HIP engine behind the C ABI: what its host translation units share.
 // Private to engine.cpp, negbin.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp, fe.cpp, fe2.cpp,
-// gee.cpp and ingest.cpp; never included by a .hip file.  The steps over the cluster factor (fixed effects, two-way,
+// gee.cpp, firth.cpp and ingest.cpp; never included by a .hip file.  The steps over the cluster factor (fixed effects, two-way,
 // GEE) share one state per step kind (sglm_engine::GroupSums) and one frame (fe.cpp: group_sums_local,
 // group_sums_finish, group_gram; StepBackend and drive_step_fit below).
 #pragma once
@@ -253,6 +253,11 @@ struct sglm_engine : public sglm::Backend {
   int64_t omega_cap = 0;
   const double* meat_w = nullptr;
   double score_ms = -1.0, meat_ms = -1.0;         // kernel times of the last sglm_vcov_robust call (-1: none yet)
+  // Firth's adjusted score (influence.hip firth_kernel; firth.cpp): per-workgroup partials [grid][p + 1], then
+  // their sum [p + 1]; past the fused widths v goes through domega
+  double* dgpart = nullptr;
+  int64_t gpart_cap = 0;
+  double firth_ms = -1.0;                         // kernel time of the last Firth pass (-1: none yet)
 
   // ---- cluster sums (cluster.hip; vcov_cluster.cpp): sglm_set_clusters / sglm_vcov_cluster ----
   int32_t cl_G = 0;                               // clusters declared for the resident rows (0: none set)
@@ -420,6 +425,9 @@ struct sglm_engine : public sglm::Backend {
                       double* resid, double* cooks, double* sum_hat);
   int score_local(const double* beta, const double* cov, int family, int link, int k);
   int score_sync();
+  // g [p + 1] = the adjusted score g* | sum of h of this shard's rows at beta against cov (the global C); hat [n]
+  // or null
+  int firth_local(const double* beta, const double* cov, int family, int link, double* g, double* hat);
   int predict_new_se(const double* X, int64_t nn, int64_t pp, int64_t ldx, const double* cov, double disp, double* out);
 
   // ---- vcov_cluster.cpp ----

@@ -28,6 +28,14 @@
 //   omega_i = u_i^2 / (1 - h_i)^k,  u_i = w_i (y_i - mu_i) g'(mu_i),  h_i = w_i q_i
 // (k = 0: no MFMA product), which the engine then feeds to a Gram pass as prior weights.
 // uscore_kernel stores u_i itself, the factor of the cluster sums of cluster.hip.
+//
+// firth_kernel is the body's fifth mode: Firth's adjusted score g* = sum_i v_i x_i, v_i = u_i + h_i r_i / 2, in
+// the same read of X.  The lane that holds X[row i][16 c + 4 s + g] in xv[r][c][s] accumulates v_i times it in
+// gacc[c][s] -- the column sums need no data movement either -- across the workgroup's steps; at the end the 16
+// lanes of a lane group, then the four waves (through LDS), are summed in a fixed order into one partial p-vector
+// per workgroup, and firth_sum_kernel adds the workgroups' partials.  Past FIRTH_FUSED_MAX column blocks the
+// accumulators do not fit beside the design's registers: there the mode stores v and firth_xtv_kernel streams X
+// a second time for X'v, a lane per row, into the same partials.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -59,12 +67,49 @@ __device__ __forceinline__ double group_sum(double v) {  // over the four lane g
 // what the kernel does with a row: the diagnostics at beta, sqrt(phi q) alone, the sandwich
 // estimator's score weight omega = u^2 / (1 - h)^k, or the signed score u itself,
 // the factor of the cluster sums (cluster.hip)
-enum InflMode : int { INFL_ROWS = 0, INFL_QFORM = 1, INFL_SCORE = 2, INFL_USCORE = 3 };
+enum InflMode : int { INFL_ROWS = 0, INFL_QFORM = 1, INFL_SCORE = 2, INFL_USCORE = 3, INFL_FIRTH = 4 };
+
+// The Firth mode: one row block per wave at every width (its accumulators take the second block's registers);
+// fused (g* in the same read of X) up to FIRTH_FUSED_MAX column blocks, v stored for firth_xtv_kernel above.
+// (VGPRs of the fused form, no scratch: 225 / 243 / 255 at P16 = 8 / 9 / 10; P16 = 11 spills)
+constexpr int FIRTH_FUSED_MAX = 10;
+constexpr int FIRTH_STEP = 16 * INFL_NW;  // rows per workgroup step of both Firth kernels
+constexpr bool firth_fused(int P16) { return P16 <= FIRTH_FUSED_MAX; }
+constexpr int firth_wg_per_cu(int P16) { return P16 <= 4 ? 4 : 2; }
+
+// The accumulators gacc[c][s] (column 16 c + 4 s + g, the rows of lane i) of a workgroup into its partial: the 16
+// lanes of each lane group, then the four waves through LDS (red [INFL_NW][16 P16]), each in a fixed order.
+// Columns >= p are never stored.
+template <int P16>
+__device__ __forceinline__ void firth_reduce(double (&gacc)[P16][4], double* red, double* part, int p) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = lane & 15, g = lane >> 4;
+  __syncthreads();  // red may be the MFMA operand panel: every wave is done reading it
+#pragma unroll
+  for (int c = 0; c < P16; ++c)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      double t = gacc[c][s];
+      t += __shfl_xor(t, 1);
+      t += __shfl_xor(t, 2);
+      t += __shfl_xor(t, 4);
+      t += __shfl_xor(t, 8);
+      if (i == 0) red[wave * (16 * P16) + 16 * c + 4 * s + g] = t;
+    }
+  __syncthreads();
+  for (int col = tid; col < p; col += INFL_NT) {
+    double t = red[col];
+    for (int k = 1; k < INFL_NW; ++k) t += red[k * (16 * P16) + col];
+    part[col] = t;
+  }
+}
 
 template <int P16, int MODE>
 __device__ __forceinline__ void influence_body(const InflArgs& a) {
   constexpr bool ROWS = MODE != INFL_QFORM;
-  constexpr int RS = infl_rs(P16);
+  constexpr bool FIRTH = MODE == INFL_FIRTH;
+  constexpr bool GACC = FIRTH && firth_fused(P16);  // the adjusted score accumulates in this kernel
+  constexpr int RS = FIRTH ? 1 : infl_rs(P16);
   constexpr int STEP = 16 * RS * INFL_NW;                      // rows per workgroup step
   constexpr int PF = (P16 * INFL_TILE + INFL_NT - 1) / INFL_NT;  // prefetch registers per thread
   __shared__ double panel[P16 * INFL_TILE];
@@ -82,6 +127,13 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
   for (int k = 0; k < PF; ++k) pf[k] = 0.0;
   if (need_q) pf[0] = a.ct[tid];  // block column 0: one tile
   double hsum = 0.0;
+  double gacc[GACC ? P16 : 1][4];
+  if constexpr (GACC) {
+#pragma unroll
+    for (int c = 0; c < P16; ++c)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) gacc[c][s] = 0.0;
+  }
   const int64_t nsteps = (a.n + STEP - 1) / STEP;
   for (int64_t step = blockIdx.x; step < nsteps; step += gridDim.x) {
     double xv[RS][P16][4];
@@ -177,6 +229,30 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
 #pragma unroll
       for (int r = 0; r < RS; ++r) q[r] = group_sum(q[r]);
     }
+    if constexpr (FIRTH) {
+      // v = u + h r / 2 on lane group 0, exactly 0 for a row >= n (whose registers hold row n - 1) and for a row
+      // of prior weight 0; then from lane i of group 0 to the four lanes that hold row i's columns
+      double v = 0.0;
+      if (g == 0 && row[0] < a.n) {
+        const int64_t ri = row[0];
+        const double e = eta[0] + (a.off ? a.off[ri] : 0.0);
+        const double pw = a.prior ? a.prior[ri] : 1.0;
+        const FirthRow w = firth_row(a.family, a.link, e, a.y[ri], a.m ? a.m[ri] : 1.0, pw);
+        const double h = w.w * q[0];
+        if (a.hat) a.hat[ri] = h;
+        hsum += h;
+        v = pw == 0.0 ? 0.0 : w.u + (0.5 * h) * w.r;
+        if constexpr (!GACC) a.out[ri] = v;
+      }
+      if constexpr (GACC) {
+        v = __shfl(v, i);
+#pragma unroll
+        for (int c = 0; c < P16; ++c)
+#pragma unroll
+          for (int s = 0; s < 4; ++s) gacc[c][s] = fma(v, xv[0][c][s], gacc[c][s]);
+      }
+      continue;
+    }
 #pragma unroll
     for (int r = 0; r < RS; ++r) {
       if (g != 0 || row[r] >= a.n) continue;  // 16 lanes store 16 consecutive rows
@@ -217,6 +293,26 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
       hsum += h;
     }
   }
+  if constexpr (FIRTH) {  // the workgroup's partial [p + 1]: the adjusted score (fused widths), then the sum of h
+    double* part = a.gpart + (int64_t)blockIdx.x * (a.p + 1);
+    hsum += __shfl_xor(hsum, 1);
+    hsum += __shfl_xor(hsum, 2);
+    hsum += __shfl_xor(hsum, 4);
+    hsum += __shfl_xor(hsum, 8);
+    if (lane == 0) swave[wave] = hsum;
+    if constexpr (GACC) {
+      static_assert(INFL_NW * 16 <= INFL_TILE, "the wave partials fit the operand panel");
+      firth_reduce<P16>(gacc, panel, part, a.p);
+    } else {
+      __syncthreads();
+    }
+    if (tid == 0) {
+      double s = swave[0];
+      for (int k = 1; k < INFL_NW; ++k) s += swave[k];
+      part[a.p] = s;
+    }
+    return;
+  }
   if (MODE == INFL_ROWS && a.hpart) {  // lanes, then waves, in a fixed order
     hsum += __shfl_xor(hsum, 1);
     hsum += __shfl_xor(hsum, 2);
@@ -247,6 +343,84 @@ __global__ void __launch_bounds__(INFL_NT, 2) score_kernel(InflArgs a) {
 template <int P16>
 __global__ void __launch_bounds__(INFL_NT, 2) uscore_kernel(InflArgs a) {
   influence_body<P16, INFL_USCORE>(a);
+}
+
+template <int P16>
+__global__ void __launch_bounds__(INFL_NT, 2) firth_kernel(InflArgs a) {
+  influence_body<P16, INFL_FIRTH>(a);
+}
+
+// X'v of the stored v (a.out), the widths past FIRTH_FUSED_MAX: a second stream of X over firth_kernel's steps
+// and grid, into the first p entries of the same partials.  No MFMA operand layout binds here, so a lane is a row:
+// a step's 64 rows are the 64 lanes of every wave (512 contiguous bytes per column and load), wave w owns the
+// 4 P16 columns from 4 P16 w on and carries one accumulator per column across the steps; at the end each column
+// is summed over the 64 lanes in a fixed order.
+template <int P16>
+__global__ void __launch_bounds__(INFL_NT, 2) firth_xtv_kernel(InflArgs a) {
+  constexpr int CW = 4 * P16;  // columns per wave
+  static_assert(FIRTH_STEP == 64, "a step is one row per lane");
+  const int lane = threadIdx.x & 63;
+  const int col0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * CW;
+  double gacc[CW];
+#pragma unroll
+  for (int k = 0; k < CW; ++k) gacc[k] = 0.0;
+  const int64_t ld = a.ld;
+  const int64_t nsteps = (a.n + FIRTH_STEP - 1) / FIRTH_STEP;
+  for (int64_t step = blockIdx.x; step < nsteps; step += gridDim.x) {
+    const int64_t row = step * FIRTH_STEP + lane;
+    const int64_t rr = row < a.n ? row : a.n - 1;  // clamped as in influence_body: v, not x, is masked
+    const double v = row < a.n ? a.out[rr] : 0.0;
+    // a column >= p reads column p - 1 (never stored): the pointer stops advancing there
+    const double* xp = a.X + rr + (int64_t)min(col0, a.p - 1) * ld;
+    // four batches of P16 loads, batch b + 1 issued before batch b's products: up to 2 P16 x 512 bytes per wave
+    // in flight (the scheduling barrier keeps the compiler from sinking the loads to their uses)
+    double x[2][P16];
+#pragma unroll
+    for (int b = 0; b <= 4; ++b) {
+      if (b < 4) {
+#pragma unroll
+        for (int j = 0; j < P16; ++j) {
+          x[b & 1][j] = *xp;
+          xp += (col0 + b * P16 + j + 1 < a.p) ? ld : 0;
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (b > 0) {
+#pragma unroll
+        for (int j = 0; j < P16; ++j)
+          gacc[(b - 1) * P16 + j] = fma(v, x[(b - 1) & 1][j], gacc[(b - 1) * P16 + j]);
+      }
+    }
+  }
+  double* part = a.gpart + (int64_t)blockIdx.x * (a.p + 1);
+#pragma unroll
+  for (int k = 0; k < CW; ++k) {
+    double t = gacc[k];
+    t += __shfl_xor(t, 1);
+    t += __shfl_xor(t, 2);
+    t += __shfl_xor(t, 4);
+    t += __shfl_xor(t, 8);
+    t += __shfl_xor(t, 16);
+    t += __shfl_xor(t, 32);
+    if (lane == 0 && col0 + k < a.p) part[col0 + k] = t;
+  }
+}
+
+// out[j] = the sum over the workgroups' partials part[k][j] (stride doubles apart), one workgroup per entry:
+// 256 strided sums, then those in order
+__global__ void __launch_bounds__(256) firth_sum_kernel(const double* __restrict__ part, int nparts, int stride,
+                                                        double* __restrict__ out) {
+  __shared__ double ss[256];
+  const int j = blockIdx.x;
+  double s = 0.0;
+  for (int k = threadIdx.x; k < nparts; k += 256) s += part[(int64_t)k * stride + j];
+  ss[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = ss[0];
+    for (int k = 1; k < 256; ++k) t += ss[k];
+    out[j] = t;
+  }
 }
 
 __global__ void __launch_bounds__(256) influence_sum_kernel(const double* __restrict__ part, int nparts,
@@ -293,6 +467,25 @@ int influence_grid(int P16, int ncu, int64_t n) {
   return std::max(1, std::min(steps_of(P16, n), ncu * wgs));
 }
 
+// workgroups of firth_kernel<P16> one CU holds
+static hipError_t firth_resident_wgs(int P16, int* out) {
+#define K(N) \
+  case N: return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, firth_kernel<N>, INFL_NT, 0);
+  INFL_CASES(K)
+#undef K
+}
+
+// As influence_grid, for the two Firth kernels (which share it: the second fills the first's partials)
+int firth_grid(int P16, int ncu, int64_t n) {
+  int wgs = 1;
+  if (firth_resident_wgs(P16, &wgs) != hipSuccess || wgs < 1) wgs = 1;
+  wgs = std::min(wgs, firth_wg_per_cu(P16));
+  const int64_t steps = std::min<int64_t>((n + FIRTH_STEP - 1) / FIRTH_STEP, (int64_t)1 << 30);
+  return std::max(1, (int)std::min<int64_t>(steps, (int64_t)ncu * wgs));
+}
+
+bool firth_is_fused(int P16) { return firth_fused(P16); }
+
 void influence_tiles(const double* C, int p, double* out) {
   const int P16 = (p + 15) / 16;
   for (int b = 0; b < P16; ++b)
@@ -328,6 +521,34 @@ hipError_t launch_uscore(int P16, const InflArgs& a, int grid, hipStream_t st, h
   case N: hipExtLaunchKernelGGL(uscore_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
   INFL_CASES(K)
 #undef K
+  return hipGetLastError();
+}
+
+hipError_t launch_firth(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  if (firth_fused(P16)) {
+#define K(N) \
+  case N: hipExtLaunchKernelGGL(firth_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
+    INFL_CASES(K)
+#undef K
+    return hipGetLastError();
+  }
+  // two launches between the events: the rows (v stored), then X'v
+#define K(N)                                                                                               \
+  case N:                                                                                                  \
+    hipExtLaunchKernelGGL(firth_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, nullptr, 0, a);           \
+    hipExtLaunchKernelGGL(firth_xtv_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, nullptr, e1, 0, a);       \
+    break;
+  static_assert(FIRTH_FUSED_MAX == 10, "the cases below are the widths past the fused ones");
+  switch (P16) {
+    K(11) K(12) K(13) K(14) K(15) K(16)
+    default: return hipErrorInvalidValue;
+  }
+#undef K
+  return hipGetLastError();
+}
+
+hipError_t launch_firth_sum(const double* part, int nparts, int p, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(firth_sum_kernel, dim3(p + 1), dim3(256), 0, st, part, nparts, p + 1, out);
   return hipGetLastError();
 }
 

@@ -71,6 +71,15 @@ hipError_t launch_influence_sum(const double* part, int nparts, double* out, hip
 // the signed scores u_i = w_i (y_i - mu_i) g'(mu_i) of the rows < n into a.out (need_q = 0: no MFMA product)
 hipError_t launch_uscore(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
                          hipEvent_t e1 = nullptr);
+// Firth's adjusted score: g* = sum_i (u_i + h_i r_i / 2) x_i, the sum of h and (a.hat) h
+// itself of the rows < n at a.beta against a.ct.  Partials a.gpart [grid][p + 1] with grid = firth_grid;
+// firth_is_fused: one kernel and one read of X, else a.out [n] receives v and a second kernel streams X for X'v
+// (both between e0 and e1).  launch_firth_sum: out [p + 1] = the partials added in a fixed order.
+int firth_grid(int P16, int ncu, int64_t n);
+bool firth_is_fused(int P16);
+hipError_t launch_firth(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
+                        hipEvent_t e1 = nullptr);
+hipError_t launch_firth_sum(const double* part, int nparts, int p, double* out, hipStream_t st);
 
 // cluster sums (cluster.hip): the cluster-robust covariance's grouped scores
 // segments of the n rows under `ids` (cluster_segments: maximal runs of one id, cut at every multiple

@@ -795,6 +795,27 @@ __device__ __noinline__ InflRow influence_row(int fam, int lnk, int rtype, doubl
   return r;
 }
 
+// The row of Firth's adjusted score (influence.hip firth_kernel): the working weight w, the
+// score u = w (y - mu) g'(mu) (the INFL_USCORE value) and r = d' / d with d = dmu / deta, d' = d2mu / deta2 -- the
+// binomial's m cancels in r -- so that the row's adjustment is h r / 2, h = w q.  phi = 1 families only (binomial,
+// poisson).  Reference-order functions; out of line like influence_row.
+struct FirthRow {
+  double w, u, r;
+};
+__device__ __noinline__ FirthRow firth_row(int fam, int lnk, double eta, double y, double m, double pw) {
+  const RowCore c = row_core(noncanonical_pair(fam, lnk), CT<false>{}, fam, lnk, MODE_IRLS, eta, m, pw, 0.0, 0.0);
+  FirthRow f;
+  f.w = c.w;
+  f.u = c.w * ((y + (-1.0 * c.mu)) * c.g);
+  if (lnk == LNK_LOGIT) f.r = 1.0 - 2.0 * (c.mu / m);
+  else if (lnk == LNK_PROBIT) f.r = -eta;
+  else if (lnk == LNK_CLOGLOG) f.r = 1.0 - exp(eta);
+  else if (lnk == LNK_LOG) f.r = 1.0;
+  else if (lnk == LNK_SQRT) f.r = 1.0 / eta;
+  else f.r = 0.0;
+  return f;
+}
+
 #undef SGLM_LOGIT_FAST
 #undef SGLM_POISSON_LOG_FAST
 #undef SGLM_GAMMA_INVERSE_FAST

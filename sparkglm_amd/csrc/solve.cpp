@@ -236,6 +236,31 @@ void Solver::inv_diag(double* d) const {
   }
 }
 
+double Solver::logdet(const double* A) const {
+  double s = 0.0;
+  if (kind_ == 1) {
+    for (int64_t j = 0; j < p_; ++j) s += std::log(fac_[j + j * p_]);
+    return 2.0 * s;
+  }
+  std::vector<double> U(A, A + p_ * p_);
+  for (int64_t k = 0; k < p_; ++k) {
+    int64_t ip = k;
+    for (int64_t i = k + 1; i < p_; ++i)
+      if (std::fabs(U[i + k * p_]) > std::fabs(U[ip + k * p_])) ip = i;
+    if (ip != k)
+      for (int64_t j = k; j < p_; ++j) std::swap(U[k + j * p_], U[ip + j * p_]);
+    const double d = U[k + k * p_];
+    s += std::log(std::fabs(d));
+    if (d == 0.0) break;
+    for (int64_t i = k + 1; i < p_; ++i) {
+      const double l = U[i + k * p_] / d;
+      if (l != 0.0)
+        for (int64_t j = k + 1; j < p_; ++j) U[i + j * p_] -= l * U[k + j * p_];
+    }
+  }
+  return s;
+}
+
 void Solver::inverse(double* Ainv) const {
   if (kind_ == 1) {
     chol_inverse(fac_.data(), p_, Ainv);

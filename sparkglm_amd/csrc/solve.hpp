@@ -26,6 +26,9 @@ class Solver {
   int solve(const double* A, const double* b, double* x);  // 0 ok, 1 singular
   void inv_diag(double* d) const;
   void inverse(double* Ainv) const;
+  // log |det A| of the last solve's A: twice the sum of log L_jj of the Cholesky factor; the LU path (whose factor
+  // was overwritten by the inverse) eliminates A again with partial pivoting and sums log |u_kk|
+  double logdet(const double* A) const;
   bool has_factor() const { return kind_ != 0; }
   bool used_lu() const { return kind_ == 2; }
 

@@ -63,6 +63,20 @@ class FitGEE:
 
 
 @dataclass
+class FitFirth:
+    """sglm_fit_glm_firth: the fit of beta (every field at the returned coefficients; fit.iter: the steps taken),
+    whether the step's 1-norm met epsilon, the step halvings, the penalized deviance D - log det(X'WX), log
+    det(X'WX), |g*|_inf and sum h."""
+    fit: FitGLM
+    converged: bool
+    halvings: int
+    pen_deviance: float
+    logdet: float
+    score_inf: float
+    sum_hat: float
+
+
+@dataclass
 class FitFE2:
     """sglm_fit_glm_fe2: the fit of beta, the effects alpha [G] and gamma [H] (NaN: a level without weight;
     gamma is 0 at the lowest factor-2 code of every component), the sweeps (last iteration, total), the levels
@@ -659,6 +673,42 @@ class Engine:
         t = np.zeros(4)
         L.check(self._lib.sglm_get_gee_ms(self._h, L.ptr(t)), "sglm_get_gee_ms")
         return tuple(float(v) for v in t)
+
+    # ---- Firth's bias-reduced fits (binomial, poisson; p <= 256) ----
+    def fit_glm_firth(self, family="binomial", link="logit", epsilon=1e-8, maxit=100, start=None, init="single",
+                      npart=0, max_trace=512, max_halvings=12, verbose=False) -> FitFirth:
+        """Firth's penalized-likelihood fit (sglm_fit_glm_firth; logistf, brglm2's AS_mean): finite under
+        separation.  Iterates beta += inv(X'WX) g*(beta) from `start` (default: fit_glm's first iterate) until
+        the step's 1-norm is below `epsilon`; converged=False after `maxit` steps is a status, not an error."""
+        o = glm_opts(family, link, verbose=verbose, init=init, npart=npart)
+        fo = L.FirthOpts(float(epsilon), int(maxit), int(max_halvings))
+        pre, fit = self._pre(max_trace)
+        info = L.FirthInfo()
+        b = None if start is None else self._beta(start)
+        L.check(self._lib.sglm_fit_glm_firth(self._h, C.byref(o), C.byref(fo), L.ptr(b), C.byref(pre),
+                                             C.byref(info)), "sglm_fit_glm_firth")
+        return FitFirth(fit(), bool(info.converged), info.halvings, info.pen_deviance, info.logdet, info.score_inf,
+                        info.sum_hat)
+
+    def firth_pass(self, beta, family="binomial", link="logit", hat=False):
+        """One Firth pass at beta (sglm_firth_pass): dict(A = X'WX, g = the adjusted score g*, deviance, logdet,
+        sum_hat; with hat=True also hat [n], the leverages)."""
+        o = glm_opts(family, link)
+        b = self._beta(beta)
+        A, g, s = np.zeros((self.p, self.p), order="F"), np.zeros(self.p), np.zeros(3)
+        hv = np.empty(self.n) if hat else None
+        L.check(self._lib.sglm_firth_pass(self._h, C.byref(o), L.ptr(b), A.ctypes.data_as(L.dp), L.ptr(g), L.ptr(hv),
+                                          L.ptr(s)), "sglm_firth_pass")
+        out = dict(A=A, g=g, deviance=float(s[0]), logdet=float(s[1]), sum_hat=float(s[2]))
+        if hat:
+            out["hat"] = hv
+        return out
+
+    def firth_ms(self) -> float:
+        """Kernel time of the last Firth pass (HIP events; -1 before any)."""
+        t = C.c_double()
+        L.check(self._lib.sglm_get_firth_ms(self._h, C.byref(t)), "sglm_get_firth_ms")
+        return t.value
 
     # ---- two-way fixed effects: a second factor beside the one of set_clusters ----
     def set_fe2(self, ids, H=None):

@@ -112,6 +112,12 @@ class GLMModel:
     rho: Optional[float] = None
     scale: Optional[float] = None
     naive_se: Optional[List[float]] = None
+    # GLM.fit_firth only: the penalized deviance D - log det(X'WX), log det(X'WX), the step halvings and whether
+    # the step met epsilon; aic is None (the likelihood is a penalized one)
+    pen_deviance: Optional[float] = None
+    logdet: Optional[float] = None
+    halvings: Optional[int] = None
+    converged: Optional[bool] = None
 
     def predict(self, newData: Frame, type: str = "response", offset: Optional[Frame] = None,
                 m: Optional[Frame] = None, device: int = 0, cov=None, dispersion: Optional[float] = None,
@@ -233,6 +239,17 @@ def _gee_summary(text: str, obj, lib) -> str:
     text, k = re.subn(r"^AIC: .*$", lambda _: lines, text, count=1, flags=re.M)
     if k != 1:
         raise RuntimeError("sglm_glm_summary printed no 'AIC: ' line to replace with the GEE's correlation and scale")
+    return text
+
+
+def _firth_summary(text: str, obj, lib) -> str:
+    """GLM.summary's text for a GLM.fit_firth model: the AIC line gives way to one naming the method and its
+    penalized deviance (the anchor is sglm_glm_summary's own line, as in _nb_summary)."""
+    line = ("Method: Firth's penalized likelihood (mean bias reduction), penalized deviance: " +
+            L.java_double_str(lib.sglm_sig_digits(float(obj.pen_deviance), 6)))
+    text, k = re.subn(r"^AIC: .*$", lambda _: line, text, count=1, flags=re.M)
+    if k != 1:
+        raise RuntimeError("sglm_glm_summary printed no 'AIC: ' line to replace with the Firth fit's method")
     return text
 
 
@@ -506,6 +523,35 @@ class GLM:
         obj.theta, obj.theta_se, obj.twologlik = th, se, tll
         if theta is None:
             obj.aic += 2.0  # theta was estimated: one more parameter (logLik.negbin's df)
+        return obj
+
+    @staticmethod
+    def fit_firth(y: Frame, x: Frame, family: str = "binomial", link: str = "logit", offset: Frame = None,
+                  m: Frame = None, prior: Frame = None, epsilon: float = 1e-8, maxit: int = 100,
+                  device: int = 0) -> GLMModel:
+        """Extension: Firth's bias-reduced (penalized-likelihood) fit -- logistf::logistf, brglm2::brglmFit(type =
+        "AS_mean"), Stata firthlogit -- of binomial (logit, probit, cloglog) and poisson (log, identity, sqrt)
+        models with at most 256 columns: finite coefficients under separation.  The model carries `pen_deviance`,
+        `logdet`, `halvings`, `converged` (False after `maxit` steps) and aic = None; predict, GLM.vcov,
+        GLM.vcov_cluster, GLM.influence and GLM.coeftest work on it unchanged."""
+        fam = family.lower() if isinstance(family, str) else family
+        _require(fam in L.FIRTH_LINKS, "GLM.fit_firth takes family binomial or poisson (no dispersion families)")
+        _require(link in L.FIRTH_LINKS[fam], f"family {family} supports only the {', '.join(L.FIRTH_LINKS[fam])} links")
+        _require(isinstance(epsilon, (int, float)) and np.isfinite(epsilon) and epsilon > 0,
+                 "epsilon is finite and > 0")
+        _require(isinstance(maxit, (int, np.integer)) and maxit >= 0, "maxit is an integer >= 0")
+        _check_inputs(y, x)
+        for extra in (offset, m, prior):
+            if extra is not None:
+                _require(extra.count() == y.count(), "The two DataFrames must have the same number of rows")
+        npart = x.rdd.partitions.size()
+        eng = _engine(device)
+        eng.set_data(x.to_matrix(), y.to_vector(), None if m is None else m.to_vector(),
+                     None if offset is None else offset.to_vector(), None if prior is None else prior.to_vector())
+        r = eng.fit_glm_firth(fam, link, epsilon, maxit, init="single" if npart == 1 else "multiple", npart=npart)
+        obj = GLM.createObj(x, y, _to_pre(r.fit), fam, link)
+        obj.pen_deviance, obj.logdet, obj.halvings, obj.converged, obj.aic = (r.pen_deviance, r.logdet, r.halvings,
+                                                                              r.converged, None)
         return obj
 
     @staticmethod
@@ -787,6 +833,8 @@ class GLM:
         text = buf.value.decode()
         if getattr(obj, "corstr", None) is not None:  # GLM.fit_gee: no likelihood, the correlation and the scale
             text = _gee_summary(text, obj, lib)
+        elif getattr(obj, "pen_deviance", None) is not None:  # GLM.fit_firth
+            text = _firth_summary(text, obj, lib)
         elif getattr(obj, "theta", None) is not None:  # GLM.fit_nb: theta, and the AIC that counts it when estimated
             text = _nb_summary(text, obj, lib)
         return text
