@@ -205,6 +205,10 @@ struct WideGramArgs {
 
 // Row quadratic forms q_i = x_i' C x_i and the per-row diagnostics built on them (influence.hip).
 constexpr int INFL_TILE = 256;  // doubles per 16 x 16 tile of C~ (MFMA operand order, influence_tiles)
+// what the kernel does with a row: the diagnostics at beta, sqrt(phi q) alone, the sandwich
+// estimator's score weight omega = u^2 / (1 - h)^k, the signed score u itself,
+// the factor of the cluster sums (cluster.hip), or Firth's adjusted score
+enum InflMode : int { INFL_ROWS = 0, INFL_QFORM = 1, INFL_SCORE = 2, INFL_USCORE = 3, INFL_FIRTH = 4 };
 struct InflArgs {
   const double* X;      // col-major, leading dimension ld; columns >= p are never read
   int64_t ld;

@@ -34,9 +34,8 @@ int sglm_engine::upload_cov(const double* cov, int64_t pp) {
   return SGLM_OK;
 }
 
-// the row kernels' view of the resident shard at dbeta
-static InflArgs resident_args(const sglm_engine& e, int family, int link) {
-  InflArgs a{};
+// the row kernels' view of the resident shard at dbeta, into a
+static void resident_args(const sglm_engine& e, int family, int link, InflArgs& a) {
   a.X = e.dX;
   a.ld = e.n_pad;
   a.p = (int)e.p;
@@ -50,109 +49,33 @@ static InflArgs resident_args(const sglm_engine& e, int family, int link) {
   a.family = family;
   a.link = link;
   a.theta = e.theta;
-  return a;
 }
 
-// hat / resid / cooks / sum of h of this shard's rows at beta against cov (the global C); any output null
-int sglm_engine::influence_local(const double* beta, const double* cov, int family, int link, int rtype, double disp,
-                                 double* hat, double* resid, double* cooks, double* sum_hat) {
+int sglm_engine::rows_grid(int mode) const { return infl_grid(mode, (int)((p + 15) / 16), ncu, n); }
+
+// The host frame of every launch of the row kernel over the resident shard (engine.hpp)
+int sglm_engine::rows_enqueue(int mode, const double* beta, const double* cov, int family, int link, InflArgs a,
+                              bool to_omega) {
   HIPCHK(hipSetDevice(device));
   if (int rc = check_loaded()) return rc;
-  double* outs[3] = {hat, resid, cooks};
-  for (int k = 0; k < 3; ++k)
-    if (outs[k])
-      if (int rc = grow(dinf[k], inf_cap[k], n_pad, "hipMalloc(diagnostics vector)")) return rc;
-  const int P = (int)((p + 15) / 16);
-  const int g = influence_grid(P, ncu, n);
-  if (int rc = grow(dhpart, hpart_cap, g + 1, "hipMalloc(leverage partials)")) return rc;
   if (!evi0) HIPCHK(hipEventCreate(&evi0));
   if (!evi1) HIPCHK(hipEventCreate(&evi1));
-  const bool need_q = hat || cooks || sum_hat;
-  if (need_q)
-    if (int rc = upload_cov(cov, p)) return rc;
-  std::memcpy(hbeta, beta, sizeof(double) * p);
-  HIPCHK(hipMemcpyAsync(dbeta, hbeta, sizeof(double) * p, hipMemcpyHostToDevice, st));
-  InflArgs a = resident_args(*this, family, link);
-  a.need_q = need_q ? 1 : 0;
-  a.resid_type = rtype;
-  a.dispersion = disp;
-  a.hat = hat ? dinf[0] : nullptr;
-  a.resid = resid ? dinf[1] : nullptr;
-  a.cooks = cooks ? dinf[2] : nullptr;
-  a.hpart = sum_hat ? dhpart : nullptr;
-  HIPCHK(launch_influence(P, a, g, st, evi0, evi1));
-  if (sum_hat) {
-    HIPCHK(launch_influence_sum(dhpart, g, dhpart + g, st));
-    HIPCHK(hipMemcpyAsync(sum_hat, dhpart + g, sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  for (int k = 0; k < 3; ++k)
-    if (outs[k] && n > 0) HIPCHK(hipMemcpyAsync(outs[k], dinf[k], sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, evi0, evi1));
-  influence_ms = ms;
-  return SGLM_OK;
-}
-
-// Firth's adjusted score of this shard's rows (firth.cpp): g = g* [p] | sum of h, the workgroups' partials added on
-// the device in a fixed order; hat as influence_local's.  Past the fused widths v goes through domega.
-int sglm_engine::firth_local(const double* beta, const double* cov, int family, int link, double* g, double* hat) {
-  HIPCHK(hipSetDevice(device));
-  if (int rc = check_loaded()) return rc;
-  std::fill(g, g + p + 1, 0.0);
-  firth_ms = 0.0;
-  if (n == 0) return SGLM_OK;
-  if (hat)
-    if (int rc = grow(dinf[0], inf_cap[0], n_pad, "hipMalloc(diagnostics vector)")) return rc;
-  const int P = (int)((p + 15) / 16);
-  const int grid = firth_grid(P, ncu, n);
-  if (int rc = grow(dgpart, gpart_cap, (int64_t)(grid + 1) * (p + 1), "hipMalloc(adjusted-score partials)")) return rc;
-  if (!firth_is_fused(P))
+  if (to_omega)
     if (int rc = grow(domega, omega_cap, n_pad, "hipMalloc(score weights)")) return rc;
-  if (!evi0) HIPCHK(hipEventCreate(&evi0));
-  if (!evi1) HIPCHK(hipEventCreate(&evi1));
-  if (int rc = upload_cov(cov, p)) return rc;
-  std::memcpy(hbeta, beta, sizeof(double) * p);
-  HIPCHK(hipMemcpyAsync(dbeta, hbeta, sizeof(double) * p, hipMemcpyHostToDevice, st));
-  InflArgs a = resident_args(*this, family, link);
-  a.need_q = 1;
-  a.hat = hat ? dinf[0] : nullptr;
-  a.out = domega;
-  a.gpart = dgpart;
-  double* sum = dgpart + (int64_t)grid * (p + 1);
-  HIPCHK(launch_firth(P, a, grid, st, evi0, evi1));
-  HIPCHK(launch_firth_sum(dgpart, grid, (int)p, sum, st));
-  HIPCHK(hipMemcpyAsync(g, sum, sizeof(double) * (size_t)(p + 1), hipMemcpyDeviceToHost, st));
-  if (hat) HIPCHK(hipMemcpyAsync(hat, dinf[0], sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, evi0, evi1));
-  firth_ms = ms;
-  return SGLM_OK;
-}
-
-// omega_i = u_i^2 / (1 - h_i)^k of this shard's rows at beta against cov (the global C) into domega,
-// zeros on the padding rows: enqueued on the stream, timed by evi0 / evi1 (score_sync)
-int sglm_engine::score_local(const double* beta, const double* cov, int family, int link, int k) {
-  HIPCHK(hipSetDevice(device));
-  if (int rc = check_loaded()) return rc;
-  if (int rc = grow(domega, omega_cap, n_pad, "hipMalloc(score weights)")) return rc;
-  if (!evi0) HIPCHK(hipEventCreate(&evi0));
-  if (!evi1) HIPCHK(hipEventCreate(&evi1));
-  const int P = (int)((p + 15) / 16);
-  if (k > 0)
+  if (cov)
     if (int rc = upload_cov(cov, p)) return rc;
   std::memcpy(hbeta, beta, sizeof(double) * p);
   HIPCHK(hipMemcpyAsync(dbeta, hbeta, sizeof(double) * p, hipMemcpyHostToDevice, st));
-  InflArgs a = resident_args(*this, family, link);
-  a.need_q = k > 0 ? 1 : 0;
-  a.out = domega;
-  a.hc_k = k;
-  // the padding rows of X are zero, but the pass multiplies them by their weight: 0, not what the
-  // allocation held
-  if (n_pad > n) HIPCHK(hipMemsetAsync(domega + n, 0, sizeof(double) * (size_t)(n_pad - n), st));
+  resident_args(*this, family, link, a);
+  a.need_q = cov ? 1 : 0;
+  if (to_omega) {
+    a.out = domega;
+    // the padding rows of X are zero, but the pass multiplies them by their weight: 0, not what the
+    // allocation held
+    if (n_pad > n) HIPCHK(hipMemsetAsync(domega + n, 0, sizeof(double) * (size_t)(n_pad - n), st));
+  }
   if (n > 0) {
-    HIPCHK(launch_score(P, a, influence_grid(P, ncu, n), st, evi0, evi1));
+    HIPCHK(launch_infl(mode, (int)((p + 15) / 16), a, rows_grid(mode), st, evi0, evi1));
   } else {
     HIPCHK(hipEventRecord(evi0, st));
     HIPCHK(hipEventRecord(evi1, st));
@@ -160,14 +83,77 @@ int sglm_engine::score_local(const double* beta, const double* cov, int family, 
   return SGLM_OK;
 }
 
-// the score kernel is done (the meat pass stages its zero beta in the same pinned buffer): its time
-int sglm_engine::score_sync() {
+int sglm_engine::rows_sync(double* ms) {
   HIPCHK(hipSetDevice(device));
   HIPCHK(hipStreamSynchronize(st));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, evi0, evi1));
-  score_ms = ms;
+  float t = 0.f;
+  HIPCHK(hipEventElapsedTime(&t, evi0, evi1));
+  *ms = t;
   return SGLM_OK;
+}
+
+// hat / resid / cooks / sum of h of this shard's rows at beta against cov (the global C); any output null
+int sglm_engine::influence_local(const double* beta, const double* cov, int family, int link, int rtype, double disp,
+                                 double* hat, double* resid, double* cooks, double* sum_hat) {
+  HIPCHK(hipSetDevice(device));
+  double* outs[3] = {hat, resid, cooks};
+  for (int k = 0; k < 3; ++k)
+    if (outs[k])
+      if (int rc = grow(dinf[k], inf_cap[k], n_pad, "hipMalloc(diagnostics vector)")) return rc;
+  const int g = rows_grid(INFL_ROWS);
+  if (int rc = grow(dhpart, hpart_cap, g + 1, "hipMalloc(leverage partials)")) return rc;
+  InflArgs a{};
+  a.resid_type = rtype;
+  a.dispersion = disp;
+  a.hat = hat ? dinf[0] : nullptr;
+  a.resid = resid ? dinf[1] : nullptr;
+  a.cooks = cooks ? dinf[2] : nullptr;
+  a.hpart = sum_hat ? dhpart : nullptr;
+  if (int rc = rows_enqueue(INFL_ROWS, beta, hat || cooks || sum_hat ? cov : nullptr, family, link, a)) return rc;
+  if (sum_hat) *sum_hat = 0.0;
+  if (n > 0) {
+    if (sum_hat) {
+      HIPCHK(launch_infl_sum(dhpart, g, 1, dhpart + g, st));
+      HIPCHK(hipMemcpyAsync(sum_hat, dhpart + g, sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    for (int k = 0; k < 3; ++k)
+      if (outs[k]) HIPCHK(hipMemcpyAsync(outs[k], dinf[k], sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  }
+  return rows_sync(&influence_ms);
+}
+
+// Firth's adjusted score of this shard's rows (firth.cpp): g = g* [p] | sum of h, the workgroups' partials added on
+// the device in a fixed order; hat as influence_local's.  Past the fused widths v goes through domega.
+int sglm_engine::firth_local(const double* beta, const double* cov, int family, int link, double* g, double* hat) {
+  HIPCHK(hipSetDevice(device));
+  std::fill(g, g + p + 1, 0.0);
+  if (hat)
+    if (int rc = grow(dinf[0], inf_cap[0], n_pad, "hipMalloc(diagnostics vector)")) return rc;
+  const int grid = rows_grid(INFL_FIRTH);
+  if (int rc = grow(dgpart, gpart_cap, (int64_t)(grid + 1) * (p + 1), "hipMalloc(adjusted-score partials)")) return rc;
+  if (!firth_is_fused((int)((p + 15) / 16)))
+    if (int rc = grow(domega, omega_cap, n_pad, "hipMalloc(score weights)")) return rc;
+  InflArgs a{};
+  a.hat = hat ? dinf[0] : nullptr;
+  a.out = domega;
+  a.gpart = dgpart;
+  if (int rc = rows_enqueue(INFL_FIRTH, beta, cov, family, link, a)) return rc;
+  if (n > 0) {
+    double* sum = dgpart + (int64_t)grid * (p + 1);
+    HIPCHK(launch_infl_sum(dgpart, grid, (int)p + 1, sum, st));
+    HIPCHK(hipMemcpyAsync(g, sum, sizeof(double) * (size_t)(p + 1), hipMemcpyDeviceToHost, st));
+    if (hat) HIPCHK(hipMemcpyAsync(hat, dinf[0], sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  }
+  return rows_sync(&firth_ms);
+}
+
+// omega_i = u_i^2 / (1 - h_i)^k of this shard's rows at beta against cov (the global C) into domega, zeros on
+// the padding rows: enqueued on the stream (the meat pass stages its zero beta in the same pinned buffer:
+// rows_sync(&score_ms) comes first)
+int sglm_engine::score_local(const double* beta, const double* cov, int family, int link, int k) {
+  InflArgs a{};
+  a.hc_k = k;
+  return rows_enqueue(INFL_SCORE, beta, k > 0 ? cov : nullptr, family, link, a, true);
 }
 
 // out[i] = sqrt(max(0, disp * x_i' cov x_i)) of NEW rows, streamed through predict_new's scratch
@@ -190,7 +176,7 @@ int sglm_engine::predict_new_se(const double* X, int64_t nn, int64_t pp, int64_t
     a.need_q = 1;
     a.dispersion = disp;
     a.out = dvs;
-    HIPCHK(launch_qform(P, a, influence_grid(P, ncu, nr), st));
+    HIPCHK(launch_infl(INFL_QFORM, P, a, infl_grid(INFL_QFORM, P, ncu, nr), st));
     HIPCHK(hipMemcpyAsync(out + r0, dvs, sizeof(double) * nr, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
@@ -201,20 +187,26 @@ int sglm_engine::predict_new_se(const double* X, int64_t nn, int64_t pp, int64_t
 // solve rule (Cholesky, or the LU inverse below LU_SWITCH_RATIO; SGLM_ESINGULAR as the fit).
 int sglm::vcov_impl(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, double* cov) {
   const int64_t p = h->ncols();
-  std::vector<double> packed((size_t)packed_len(p)), x((size_t)p);
-  int rc = h->pass(MODE_IRLS, beta, 0.0, 0.0, opts->family, opts->link, packed.data());
-  if (rc) return rc;
+  std::vector<double> packed((size_t)packed_len(p));
+  if (int rc = h->pass(MODE_IRLS, beta, 0.0, 0.0, opts->family, opts->link, packed.data())) return rc;
+  return bread(h, packed.data(), "breeze.linalg.MatrixSingularException: X'WX is singular", cov);
+}
+
+int sglm::bread(sglm_engine* h, double* packed, const char* singular, double* C, double* logdet) {
+  const int64_t p = h->ncols();
+  std::vector<double> x((size_t)p);
   std::unique_ptr<SolverIface> solver = h->make_solver(p);
   const double t0 = now_ms();
-  const int srv = solver->solve(packed.data(), x.data());
-  if (srv) {
-    if (srv == SGLM_ESINGULAR) set_error("breeze.linalg.MatrixSingularException: X'WX is singular");
+  if (const int srv = solver->solve(packed, x.data())) {
+    if (srv == SGLM_ESINGULAR) set_error(singular);
     return srv;
   }
-  rc = solver->inverse(cov);
+  if (int rc = solver->inverse(C)) return rc;
+  if (logdet)
+    if (int rc = solver->logdet(logdet)) return rc;
   h->solve_ms += now_ms() - t0;
   h->solve_path = solver->path();
-  return rc;
+  return SGLM_OK;
 }
 
 // The row kernel covers resident designs on the fused / narrow paths' range only: anything else is
@@ -268,8 +260,8 @@ static int influence_shards(sglm_engine* h, const double* beta, const double* co
                                             sum_hat ? &part : nullptr))
       return rc;
     total += part;
-    h->influence_ms = d == 0 ? shards[d]->influence_ms : std::max(h->influence_ms, shards[d]->influence_ms);
   }
+  h->influence_ms = slowest_shard(h, [](const sglm_engine* s) { return s->influence_ms; });
   if (sum_hat) *sum_hat = total;
   return SGLM_OK;
 }
@@ -278,10 +270,9 @@ static int influence_shards(sglm_engine* h, const double* beta, const double* co
 static int score_shards(sglm_engine* h, const double* beta, const double* cov, const sglm_glm_opts* opts, int k) {
   for (sglm_engine* s : h->shards())
     if (int rc = s->score_local(beta, cov, opts->family, opts->link, k)) return rc;
-  for (sglm_engine* s : h->shards()) {
-    if (int rc = s->score_sync()) return rc;
-    h->score_ms = s == h->shards()[0] ? s->score_ms : std::max(h->score_ms, s->score_ms);
-  }
+  for (sglm_engine* s : h->shards())
+    if (int rc = s->rows_sync(&s->score_ms)) return rc;
+  h->score_ms = slowest_shard(h, [](const sglm_engine* s) { return s->score_ms; });
   return SGLM_OK;
 }
 
@@ -354,8 +345,7 @@ int sglm_vcov_robust(sglm_engine* h, const sglm_glm_opts* opts, const double* be
     MeatPassScope scope(h);
     if (int rc = h->pass(MODE_IRLS, zero.data(), 0.0, 0.0, FAM_GAUSSIAN, LNK_IDENTITY, packed.data())) return rc;
   }
-  for (const sglm_engine* s : h->shards())  // kernel time: the slowest shard
-    h->meat_ms = s == h->shards()[0] ? s->last_pass_ms : std::max(h->meat_ms, s->last_pass_ms);
+  h->meat_ms = slowest_shard(h, [](const sglm_engine* s) { return s->last_pass_ms; });
   unpack_gram(packed.data(), p, M.data(), x.data());
   double nrows = (double)(h->group() ? h->g_n : h->n);  // HC1: every row of every shard, weight 0 included
   if (hc_type == SGLM_HC1 && !h->group())

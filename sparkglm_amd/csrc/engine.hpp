@@ -421,10 +421,19 @@ struct sglm_engine : public sglm::Backend {
   // ---- diagnostics.cpp ----
   void free_influence();
   int upload_cov(const double* cov, int64_t pp);
+  // One launch of the row kernel (influence.hip) in `mode` (enum InflMode) over the resident shard at beta, on the
+  // stream between evi0 and evi1.  a: the mode's own fields (outputs, hc_k, resid_type, dispersion, gpart); the
+  // shard's are filled here.  cov: the global C (null: need_q = 0, nothing uploaded).  to_omega: a.out is domega
+  // feeding a later pass -- grown here, zeros on its padding rows.  An empty shard launches nothing (both events
+  // are recorded).  rows_grid: the launch's workgroups, by which a caller sizes the partials it asks for;
+  // rows_sync: the stream drained, ms = the kernel time of the launch.
+  int rows_enqueue(int mode, const double* beta, const double* cov, int family, int link, sglm::InflArgs a,
+                   bool to_omega = false);
+  int rows_grid(int mode) const;
+  int rows_sync(double* ms);
   int influence_local(const double* beta, const double* cov, int family, int link, int rtype, double disp, double* hat,
                       double* resid, double* cooks, double* sum_hat);
   int score_local(const double* beta, const double* cov, int family, int link, int k);
-  int score_sync();
   // g [p + 1] = the adjusted score g* | sum of h of this shard's rows at beta against cov (the global C); hat [n]
   // or null
   int firth_local(const double* beta, const double* cov, int family, int link, double* g, double* hat);
@@ -569,8 +578,6 @@ constexpr double FE_ABSORBED_RATIO = 1e-10;  // A_jj below this part of X'WX_jj:
 int fe_step_mode(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, int* mode, double* mu0);
 // a step's packed = lower tri A | b | scalars into the outputs that are wanted
 void fe_unpack_step(const double* packed, int64_t p, double* A, double* b, double* scalars);
-// The bread C = inv(A) of a step's packed A (its time and path into the handle); `singular`: the message
-int fe_bread(sglm_engine* h, double* packed, const char* singular, std::vector<double>& C);
 // the covariance of a call without clustering: the bread itself, a zero meat
 int fe_plain_cov(const std::vector<double>& C, double* cov, double* meat);
 // columns [col0, col0 + ncol) of a col-major level buffer on s's device, the first L rows of each, to the host
@@ -584,6 +591,16 @@ std::pair<int64_t, int64_t> uninformative_levels(const std::vector<double>& ab);
 // ---- diagnostics.cpp: what the covariance estimators share ----
 // inv(X'WX) at beta (collective over a communicator), the bread of both sandwich estimators
 int vcov_impl(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, double* cov);
+// The bread C [p x p] = inv(A) of a pass's or a step's packed A by the fit's solve rule, log det A where asked for
+// (the solve's time and path into the handle); `singular`: the message of a singular A
+int bread(sglm_engine* h, double* packed, const char* singular, double* C, double* logdet = nullptr);
+// a kernel time of a call over the handle's shards (ms(shard)): the slowest shard's
+template <class F>
+double slowest_shard(const sglm_engine* h, F ms) {
+  double v = ms(h->shards()[0]);
+  for (const sglm_engine* s : h->shards()) v = std::max(v, ms(s));
+  return v;
+}
 // SGLM_EINVAL unless every shard is a resident design on the fused / narrow path
 int require_fused_or_narrow(const sglm_engine* h, const char* what);
 // cov = f (C M C + (C M C)') / 2, exactly symmetric (col-major p x p, on the host); false: M or cov is not finite

@@ -18,7 +18,7 @@
 // free_group, group_sums_local (stale clear, row kernel, both combine trees), group_sums_finish (times, the sum
 // over shards and ranks), group_gram (scale launch, the internal engine's Gram pass), keep_group_sums, and
 // drive_step_fit over a StepBackend.  The frame of a step entry point (fe_check, fe_step_mode,
-// fe_unpack_step), the bread (fe_bread), the downloads and scans of level buffers, FeScope (engine.hpp).
+// fe_unpack_step), the downloads and scans of level buffers, FeScope (engine.hpp).
 // The refusals and the finish of a clustered covariance are vcov_cluster.cpp's.
 #include <algorithm>
 #include <cmath>
@@ -221,12 +221,7 @@ int group_times(sglm_engine* h, GroupSumsOf gs, bool rows) {
       sms[2] = ms;
     }
   }
-  double* out = (h->*gs).ms;
-  for (int k = 0; k < 3; ++k)
-    for (sglm_engine* s : shards) {
-      const double v = (s->*gs).ms[k];
-      out[k] = s == shards[0] ? v : std::max(out[k], v);
-    }
+  for (int k = 0; k < 3; ++k) (h->*gs).ms[k] = slowest_shard(h, [&](const sglm_engine* s) { return (s->*gs).ms[k]; });
   return SGLM_OK;
 }
 
@@ -303,22 +298,6 @@ void sglm::fe_unpack_step(const double* packed, int64_t p, double* A, double* b,
   if (A) std::memcpy(A, g.data(), sizeof(double) * g.size());
   if (b) std::memcpy(b, x.data(), sizeof(double) * x.size());
   if (scalars) std::memcpy(scalars, packed + tri_count(p) + p, sizeof(double) * NS);
-}
-
-int sglm::fe_bread(sglm_engine* h, double* packed, const char* singular, std::vector<double>& C) {
-  const int64_t p = h->ncols();
-  std::vector<double> x((size_t)p);
-  std::unique_ptr<SolverIface> solver = h->make_solver(p);
-  const double t0 = now_ms();
-  if (const int srv = solver->solve(packed, x.data())) {
-    if (srv == SGLM_ESINGULAR) set_error(singular);
-    return srv;
-  }
-  C.resize((size_t)(p * p));
-  if (int rc = solver->inverse(C.data())) return rc;
-  h->solve_ms += now_ms() - t0;
-  h->solve_path = solver->path();
-  return SGLM_OK;
 }
 
 int sglm::fe_plain_cov(const std::vector<double>& C, double* cov, double* meat) {
@@ -514,10 +493,10 @@ int sglm_vcov_fe(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, 
   const int64_t p = h->ncols();
   if (int rc = fe_set_alpha_all(h, alpha)) return rc;
   if (int rc = fe_offsets(h)) return rc;
-  std::vector<double> packed((size_t)packed_len(p)), C, M((size_t)(p * p)), x((size_t)p);
+  std::vector<double> packed((size_t)packed_len(p)), C((size_t)(p * p)), M((size_t)(p * p)), x((size_t)p);
   if (int rc = fe_step(h, opts->family, opts->link, MODE_IRLS, beta, 0.0, true, packed.data())) return rc;
   const char* singular = "breeze.linalg.MatrixSingularException: the within-group X'WX is singular";
-  if (int rc = fe_bread(h, packed.data(), singular, C)) return rc;
+  if (int rc = bread(h, packed.data(), singular, C.data())) return rc;
   if (!cluster) return fe_plain_cov(C, cov, meat);
   // the w-weighted sums s | W stay in g2 while the u-weighted ones S | U are formed in g
   if (int rc = h->shards()[0]->keep_group_sums(h->shards()[0]->fe)) return rc;

@@ -735,11 +735,11 @@ int sglm_vcov_fe2(sglm_engine* h, const sglm_glm_opts* opts, const sglm_fe2_opts
   if (int rc = h->set_effects(h->dalpha, alpha, G)) return rc;
   if (int rc = h->set_effects(F->dgamma, gamma, F->H)) return rc;
   if (int rc = zero_Y(h)) return rc;
-  std::vector<double> packed((size_t)packed_len(p)), C, M((size_t)(p * p)), x((size_t)p);
+  std::vector<double> packed((size_t)packed_len(p)), C((size_t)(p * p)), M((size_t)(p * p)), x((size_t)p);
   int k = 0;
   if (int rc = fe2_step(h, fe2, opts->family, opts->link, MODE_IRLS, beta, 0.0, true, 0, packed.data(), &k)) return rc;
   const char* singular = "breeze.linalg.MatrixSingularException: the two-way within X'WX is singular";
-  if (int rc = fe_bread(h, packed.data(), singular, C)) return rc;
+  if (int rc = bread(h, packed.data(), singular, C.data())) return rc;
   if (!cluster) return fe_plain_cov(C, cov, meat);
   int32_t geff = 0, heff = 0;
   if (int rc = count_levels(h, &geff, &heff)) return rc;

@@ -63,17 +63,7 @@ const char* FIRTH_SINGULAR = "breeze.linalg.MatrixSingularException: X'WX is sin
 int firth_eval(sglm_engine* h, const sglm_glm_opts& o, const double* beta, FirthEval& e, double* hat) {
   const int64_t p = h->ncols();
   if (int rc = h->pass(MODE_IRLS, beta, 0.0, 0.0, o.family, o.link, e.packed.data())) return rc;
-  std::unique_ptr<SolverIface> solver = h->make_solver(p);
-  const double t0 = now_ms();
-  const int srv = solver->solve(e.packed.data(), e.delta.data());
-  if (srv) {
-    if (srv == SGLM_ESINGULAR) set_error(FIRTH_SINGULAR);
-    return srv;
-  }
-  if (int rc = solver->inverse(e.C.data())) return rc;
-  if (int rc = solver->logdet(&e.logdet)) return rc;
-  h->solve_ms += now_ms() - t0;
-  h->solve_path = solver->path();
+  if (int rc = bread(h, e.packed.data(), FIRTH_SINGULAR, e.C.data(), &e.logdet)) return rc;
   // shard order: g* and sum h summed as the shards lie, hat concatenated in row order; kernel time: the slowest shard
   const std::vector<sglm_engine*>& shards = h->shards();
   std::vector<double> part((size_t)(p + 1));
@@ -83,8 +73,8 @@ int firth_eval(sglm_engine* h, const sglm_glm_opts& o, const double* beta, Firth
     if (int rc = shards[d]->firth_local(beta, e.C.data(), o.family, o.link, part.data(), hat ? hat + lo : nullptr))
       return rc;
     for (int64_t k = 0; k <= p; ++k) e.g[(size_t)k] += part[(size_t)k];
-    h->firth_ms = d == 0 ? shards[d]->firth_ms : std::max(h->firth_ms, shards[d]->firth_ms);
   }
+  h->firth_ms = slowest_shard(h, [](const sglm_engine* s) { return s->firth_ms; });
   if (!h->group())
     if (int rc = h->allreduce_small(e.g.data(), p + 1)) return rc;
   e.score_inf = 0.0;

@@ -249,7 +249,7 @@ int sglm_vcov_gee(sglm_engine* h, const sglm_glm_opts* opts, const sglm_gee_opts
   FeScope scope(h);
   if (int rc = gee_counts(h, opts, &g)) return rc;
   const int64_t p = h->ncols();
-  std::vector<double> packed((size_t)packed_len(p)), C, M((size_t)(p * p)), x((size_t)p);
+  std::vector<double> packed((size_t)packed_len(p)), C((size_t)(p * p)), M((size_t)(p * p)), x((size_t)p);
   if (int rc = gee_step(h, opts->family, opts->link, MODE_IRLS, beta, 0.0, &g, true, -1, packed.data())) return rc;
   const double phi = phi_of(g.m, p);
   // a row whose working weight is not a number (its mean left the family's range) shows in the residual sums, and
@@ -259,7 +259,7 @@ int sglm_vcov_gee(sglm_engine* h, const sglm_glm_opts* opts, const sglm_gee_opts
               "beta)");
     return SGLM_EINVAL;
   }
-  if (int rc = fe_bread(h, packed.data(), GEE_SINGULAR, C)) return rc;
+  if (int rc = bread(h, packed.data(), GEE_SINGULAR, C.data())) return rc;
   if (!robust) {
     bool finite = std::isfinite(phi);
     for (size_t k = 0; k < C.size(); ++k) {

@@ -33,9 +33,13 @@
 // the same read of X.  The lane that holds X[row i][16 c + 4 s + g] in xv[r][c][s] accumulates v_i times it in
 // gacc[c][s] -- the column sums need no data movement either -- across the workgroup's steps; at the end the 16
 // lanes of a lane group, then the four waves (through LDS), are summed in a fixed order into one partial p-vector
-// per workgroup, and firth_sum_kernel adds the workgroups' partials.  Past FIRTH_FUSED_MAX column blocks the
+// per workgroup, and infl_sum_kernel adds the workgroups' partials.  Past FIRTH_FUSED_MAX column blocks the
 // accumulators do not fit beside the design's registers: there the mode stores v and firth_xtv_kernel streams X
 // a second time for X'v, a lane per row, into the same partials.
+//
+// The host side is written once for every mode (enum InflMode, common.hpp): launch_infl, the grid rule
+// infl_grid -- whose rows per step are the body's own infl_step -- and the fixed-order sum launch_infl_sum of
+// the workgroups' partials (the leverage sum: one column).
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -54,8 +58,11 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 constexpr int INFL_NW = 4;            // waves per workgroup
 constexpr int INFL_NT = 64 * INFL_NW;
 // row blocks of 16 per wave: two while the kernel stays within 256 VGPRs without scratch (P16 <= 7;
-// two workgroups per CU, and no AGPRs: the fp64 MFMA's AGPR form runs at 60 %)
-constexpr int infl_rs(int P16) { return P16 <= 7 ? 2 : 1; }
+// two workgroups per CU, and no AGPRs: the fp64 MFMA's AGPR form runs at 60 %).
+// The Firth mode: one at every width (its accumulators take the second block's registers).
+constexpr int infl_rs(int mode, int P16) { return mode != INFL_FIRTH && P16 <= 7 ? 2 : 1; }
+// rows per workgroup step: the body's and (firth_xtv_kernel: the Firth mode's) the grid rule's
+constexpr int infl_step(int mode, int P16) { return 16 * infl_rs(mode, P16) * INFL_NW; }
 constexpr int infl_wg_per_cu(int P16) { return P16 <= 4 ? 4 : 2; }
 
 __device__ __forceinline__ double group_sum(double v) {  // over the four lane groups l / 16
@@ -64,18 +71,11 @@ __device__ __forceinline__ double group_sum(double v) {  // over the four lane g
   return v;
 }
 
-// what the kernel does with a row: the diagnostics at beta, sqrt(phi q) alone, the sandwich
-// estimator's score weight omega = u^2 / (1 - h)^k, or the signed score u itself,
-// the factor of the cluster sums (cluster.hip)
-enum InflMode : int { INFL_ROWS = 0, INFL_QFORM = 1, INFL_SCORE = 2, INFL_USCORE = 3, INFL_FIRTH = 4 };
-
-// The Firth mode: one row block per wave at every width (its accumulators take the second block's registers);
-// fused (g* in the same read of X) up to FIRTH_FUSED_MAX column blocks, v stored for firth_xtv_kernel above.
+// The Firth mode: fused (g* in the same read of X) up to FIRTH_FUSED_MAX column blocks, v stored for
+// firth_xtv_kernel above.
 // (VGPRs of the fused form, no scratch: 225 / 243 / 255 at P16 = 8 / 9 / 10; P16 = 11 spills)
 constexpr int FIRTH_FUSED_MAX = 10;
-constexpr int FIRTH_STEP = 16 * INFL_NW;  // rows per workgroup step of both Firth kernels
 constexpr bool firth_fused(int P16) { return P16 <= FIRTH_FUSED_MAX; }
-constexpr int firth_wg_per_cu(int P16) { return P16 <= 4 ? 4 : 2; }
 
 // The accumulators gacc[c][s] (column 16 c + 4 s + g, the rows of lane i) of a workgroup into its partial: the 16
 // lanes of each lane group, then the four waves through LDS (red [INFL_NW][16 P16]), each in a fixed order.
@@ -109,8 +109,8 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
   constexpr bool ROWS = MODE != INFL_QFORM;
   constexpr bool FIRTH = MODE == INFL_FIRTH;
   constexpr bool GACC = FIRTH && firth_fused(P16);  // the adjusted score accumulates in this kernel
-  constexpr int RS = FIRTH ? 1 : infl_rs(P16);
-  constexpr int STEP = 16 * RS * INFL_NW;                      // rows per workgroup step
+  constexpr int RS = infl_rs(MODE, P16);
+  constexpr int STEP = infl_step(MODE, P16);                     // rows per workgroup step
   constexpr int PF = (P16 * INFL_TILE + INFL_NT - 1) / INFL_NT;  // prefetch registers per thread
   __shared__ double panel[P16 * INFL_TILE];
   __shared__ double sbeta[16 * P16];
@@ -293,8 +293,10 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
       hsum += h;
     }
   }
-  if constexpr (FIRTH) {  // the workgroup's partial [p + 1]: the adjusted score (fused widths), then the sum of h
-    double* part = a.gpart + (int64_t)blockIdx.x * (a.p + 1);
+  if (FIRTH || (MODE == INFL_ROWS && a.hpart)) {
+    // the workgroup's sum of h: lanes, then waves, in a fixed order.  The Firth mode's partial [p + 1]: the
+    // adjusted score (fused widths), then the sum of h
+    double* part = FIRTH ? a.gpart + (int64_t)blockIdx.x * (a.p + 1) : a.hpart + blockIdx.x;
     hsum += __shfl_xor(hsum, 1);
     hsum += __shfl_xor(hsum, 2);
     hsum += __shfl_xor(hsum, 4);
@@ -309,21 +311,7 @@ __device__ __forceinline__ void influence_body(const InflArgs& a) {
     if (tid == 0) {
       double s = swave[0];
       for (int k = 1; k < INFL_NW; ++k) s += swave[k];
-      part[a.p] = s;
-    }
-    return;
-  }
-  if (MODE == INFL_ROWS && a.hpart) {  // lanes, then waves, in a fixed order
-    hsum += __shfl_xor(hsum, 1);
-    hsum += __shfl_xor(hsum, 2);
-    hsum += __shfl_xor(hsum, 4);
-    hsum += __shfl_xor(hsum, 8);
-    if (lane == 0) swave[wave] = hsum;
-    __syncthreads();
-    if (tid == 0) {
-      double s = swave[0];
-      for (int k = 1; k < INFL_NW; ++k) s += swave[k];
-      a.hpart[blockIdx.x] = s;
+      part[FIRTH ? a.p : 0] = s;
     }
   }
 }
@@ -358,6 +346,7 @@ __global__ void __launch_bounds__(INFL_NT, 2) firth_kernel(InflArgs a) {
 template <int P16>
 __global__ void __launch_bounds__(INFL_NT, 2) firth_xtv_kernel(InflArgs a) {
   constexpr int CW = 4 * P16;  // columns per wave
+  constexpr int FIRTH_STEP = infl_step(INFL_FIRTH, P16);  // firth_kernel's steps
   static_assert(FIRTH_STEP == 64, "a step is one row per lane");
   const int lane = threadIdx.x & 63;
   const int col0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * CW;
@@ -408,8 +397,8 @@ __global__ void __launch_bounds__(INFL_NT, 2) firth_xtv_kernel(InflArgs a) {
 
 // out[j] = the sum over the workgroups' partials part[k][j] (stride doubles apart), one workgroup per entry:
 // 256 strided sums, then those in order
-__global__ void __launch_bounds__(256) firth_sum_kernel(const double* __restrict__ part, int nparts, int stride,
-                                                        double* __restrict__ out) {
+__global__ void __launch_bounds__(256) infl_sum_kernel(const double* __restrict__ part, int nparts, int stride,
+                                                       double* __restrict__ out) {
   __shared__ double ss[256];
   const int j = blockIdx.x;
   double s = 0.0;
@@ -423,64 +412,45 @@ __global__ void __launch_bounds__(256) firth_sum_kernel(const double* __restrict
   }
 }
 
-__global__ void __launch_bounds__(256) influence_sum_kernel(const double* __restrict__ part, int nparts,
-                                                            double* __restrict__ out) {
-  __shared__ double ss[256];
-  double s = 0.0;
-  for (int k = threadIdx.x; k < nparts; k += 256) s += part[k];
-  ss[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = ss[0];
-    for (int k = 1; k < 256; ++k) t += ss[k];
-    out[0] = t;
-  }
+// The kernels of one width, by mode; xtv: the Firth mode's second kernel, null at the fused widths (where it
+// is not built)
+typedef void (*InflKernel)(InflArgs);
+struct WidthKernels {
+  InflKernel mode[5], xtv;
+};
+template <int N>
+WidthKernels width_kernels() {
+  static_assert(INFL_ROWS == 0 && INFL_QFORM == 1 && INFL_SCORE == 2 && INFL_USCORE == 3 && INFL_FIRTH == 4);
+  WidthKernels k{{influence_kernel<N>, qform_kernel<N>, score_kernel<N>, uscore_kernel<N>, firth_kernel<N>}, nullptr};
+  if constexpr (!firth_fused(N)) k.xtv = firth_xtv_kernel<N>;
+  return k;
 }
 
-int steps_of(int P16, int64_t n) {
-  const int64_t step = 16 * infl_rs(P16) * INFL_NW;
-  return (int)std::min<int64_t>((n + step - 1) / step, (int64_t)1 << 30);
+// the only list of the widths; null: no such width or mode
+const WidthKernels* kernels_of(int mode, int P16) {
+#define K(N) width_kernels<N>()
+  static const WidthKernels all[MAX_P16] = {K(1), K(2),  K(3),  K(4),  K(5),  K(6),  K(7),  K(8),
+                                            K(9), K(10), K(11), K(12), K(13), K(14), K(15), K(16)};
+#undef K
+  return mode >= INFL_ROWS && mode <= INFL_FIRTH && P16 >= 1 && P16 <= MAX_P16 ? &all[P16 - 1] : nullptr;
 }
 
 }  // namespace
 
-#define INFL_CASES(K)                                                                                      \
-  switch (P16) {                                                                                           \
-    K(1) K(2) K(3) K(4) K(5) K(6) K(7) K(8) K(9) K(10) K(11) K(12) K(13) K(14) K(15) K(16)                 \
-    default: return hipErrorInvalidValue;                                                                  \
-  }
-
-// workgroups of influence_kernel<P16> one CU holds (registers and LDS: the runtime's own count)
-static hipError_t resident_wgs(int P16, int* out) {
-#define K(N) \
-  case N: return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, influence_kernel<N>, INFL_NT, 0);
-  INFL_CASES(K)
-#undef K
-}
-
-// One workgroup per resident slot (capped at infl_wg_per_cu): the grid -- and with it the order of the
-// sum of h -- depends on the shape and the device only.
-int influence_grid(int P16, int ncu, int64_t n) {
+// One workgroup per resident slot (capped at infl_wg_per_cu): the grid -- and with it the order of the sum of h
+// and of the Firth partials -- depends on the mode, the shape and the device only.  The two Firth kernels share
+// it: the second fills the first's partials.
+int infl_grid(int mode, int P16, int ncu, int64_t n) {
+  // workgroups of the kernel one CU holds (registers and LDS: the runtime's own count): the Firth mode's of
+  // firth_kernel, every other mode's of influence_kernel
+  const WidthKernels* k = kernels_of(mode, P16);
   int wgs = 1;
-  if (resident_wgs(P16, &wgs) != hipSuccess || wgs < 1) wgs = 1;
+  if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k->mode[mode == INFL_FIRTH ? INFL_FIRTH : INFL_ROWS],
+                                                         INFL_NT, 0) != hipSuccess || wgs < 1)
+    wgs = 1;
   wgs = std::min(wgs, infl_wg_per_cu(P16));
-  return std::max(1, std::min(steps_of(P16, n), ncu * wgs));
-}
-
-// workgroups of firth_kernel<P16> one CU holds
-static hipError_t firth_resident_wgs(int P16, int* out) {
-#define K(N) \
-  case N: return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, firth_kernel<N>, INFL_NT, 0);
-  INFL_CASES(K)
-#undef K
-}
-
-// As influence_grid, for the two Firth kernels (which share it: the second fills the first's partials)
-int firth_grid(int P16, int ncu, int64_t n) {
-  int wgs = 1;
-  if (firth_resident_wgs(P16, &wgs) != hipSuccess || wgs < 1) wgs = 1;
-  wgs = std::min(wgs, firth_wg_per_cu(P16));
-  const int64_t steps = std::min<int64_t>((n + FIRTH_STEP - 1) / FIRTH_STEP, (int64_t)1 << 30);
+  const int64_t step = infl_step(mode, P16);
+  const int64_t steps = std::min<int64_t>((n + step - 1) / step, (int64_t)1 << 30);
   return std::max(1, (int)std::min<int64_t>(steps, (int64_t)ncu * wgs));
 }
 
@@ -500,68 +470,21 @@ void influence_tiles(const double* C, int p, double* out) {
     }
 }
 
-hipError_t launch_influence(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-#define K(N) \
-  case N: hipExtLaunchKernelGGL(influence_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
-  INFL_CASES(K)
-#undef K
-  return hipGetLastError();
-}
-
-hipError_t launch_score(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-#define K(N) \
-  case N: hipExtLaunchKernelGGL(score_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
-  INFL_CASES(K)
-#undef K
-  return hipGetLastError();
-}
-
-hipError_t launch_uscore(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-#define K(N) \
-  case N: hipExtLaunchKernelGGL(uscore_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
-  INFL_CASES(K)
-#undef K
-  return hipGetLastError();
-}
-
-hipError_t launch_firth(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-  if (firth_fused(P16)) {
-#define K(N) \
-  case N: hipExtLaunchKernelGGL(firth_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, e1, 0, a); break;
-    INFL_CASES(K)
-#undef K
-    return hipGetLastError();
+hipError_t launch_infl(int mode, int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  const WidthKernels* k = kernels_of(mode, P16);
+  if (!k) return hipErrorInvalidValue;
+  const dim3 g(grid), b(INFL_NT);
+  if (mode == INFL_FIRTH && k->xtv) {  // two launches between the events: the rows (v stored), then X'v
+    hipExtLaunchKernelGGL(k->mode[mode], g, b, 0, st, e0, nullptr, 0, a);
+    hipExtLaunchKernelGGL(k->xtv, g, b, 0, st, nullptr, e1, 0, a);
+  } else {
+    hipExtLaunchKernelGGL(k->mode[mode], g, b, 0, st, e0, e1, 0, a);
   }
-  // two launches between the events: the rows (v stored), then X'v
-#define K(N)                                                                                               \
-  case N:                                                                                                  \
-    hipExtLaunchKernelGGL(firth_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, e0, nullptr, 0, a);           \
-    hipExtLaunchKernelGGL(firth_xtv_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, nullptr, e1, 0, a);       \
-    break;
-  static_assert(FIRTH_FUSED_MAX == 10, "the cases below are the widths past the fused ones");
-  switch (P16) {
-    K(11) K(12) K(13) K(14) K(15) K(16)
-    default: return hipErrorInvalidValue;
-  }
-#undef K
   return hipGetLastError();
 }
 
-hipError_t launch_firth_sum(const double* part, int nparts, int p, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(firth_sum_kernel, dim3(p + 1), dim3(256), 0, st, part, nparts, p + 1, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_qform(int P16, const InflArgs& a, int grid, hipStream_t st) {
-#define K(N) \
-  case N: hipLaunchKernelGGL(qform_kernel<N>, dim3(grid), dim3(INFL_NT), 0, st, a); break;
-  INFL_CASES(K)
-#undef K
-  return hipGetLastError();
-}
-
-hipError_t launch_influence_sum(const double* part, int nparts, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(influence_sum_kernel, dim3(1), dim3(256), 0, st, part, nparts, out);
+hipError_t launch_infl_sum(const double* part, int nparts, int ncol, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(infl_sum_kernel, dim3(ncol), dim3(256), 0, st, part, nparts, ncol, out);
   return hipGetLastError();
 }
 

@@ -57,29 +57,25 @@ hipError_t launch_narrow(int P16, const PassArgs& a, int grid, hipStream_t st, h
                          hipEvent_t e1 = nullptr);
 
 // per-row diagnostics (influence.hip): p <= 256
-int influence_grid(int P16, int ncu, int64_t n);  // workgroups (each owns the steps g, g + grid, ...: a fixed order)
+// workgroups of a mode (enum InflMode) over n rows; each owns the steps g, g + grid, ...: a fixed order
+int infl_grid(int mode, int P16, int ncu, int64_t n);
 // C (col-major p x p, symmetric) -> C~ in the kernels' operand order: the block triangle c <= b of
 // 16 x 16 tiles (tile b (b + 1) / 2 + c), off-diagonal tiles doubled, zero past p; out [T][INFL_TILE]
 void influence_tiles(const double* C, int p, double* out);
-hipError_t launch_influence(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
-                            hipEvent_t e1 = nullptr);
-hipError_t launch_qform(int P16, const InflArgs& a, int grid, hipStream_t st);
-// the sandwich estimator's score weights of the rows < n into a.out (hat / resid / cooks / hpart unused)
-hipError_t launch_score(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
-                        hipEvent_t e1 = nullptr);
-hipError_t launch_influence_sum(const double* part, int nparts, double* out, hipStream_t st);  // fixed order
-// the signed scores u_i = w_i (y_i - mu_i) g'(mu_i) of the rows < n into a.out (need_q = 0: no MFMA product)
-hipError_t launch_uscore(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
-                         hipEvent_t e1 = nullptr);
-// Firth's adjusted score: g* = sum_i (u_i + h_i r_i / 2) x_i, the sum of h and (a.hat) h
-// itself of the rows < n at a.beta against a.ct.  Partials a.gpart [grid][p + 1] with grid = firth_grid;
-// firth_is_fused: one kernel and one read of X, else a.out [n] receives v and a second kernel streams X for X'v
-// (both between e0 and e1).  launch_firth_sum: out [p + 1] = the partials added in a fixed order.
-int firth_grid(int P16, int ncu, int64_t n);
+// One launcher for every mode, with grid = infl_grid of the same mode (e0 / e1 as launch_pass's):
+//   INFL_ROWS    the diagnostics of the rows < n at a.beta (hat / resid / cooks; hpart [grid]: the sums of h)
+//   INFL_QFORM   a.out = sqrt(max(0, dispersion q))
+//   INFL_SCORE   the sandwich estimator's score weights into a.out (hat / resid / cooks / hpart unused)
+//   INFL_USCORE  the signed scores u_i = w_i (y_i - mu_i) g'(mu_i) into a.out (need_q = 0: no MFMA product)
+//   INFL_FIRTH   Firth's adjusted score: g* = sum_i (u_i + h_i r_i / 2) x_i, the sum of h and
+//                (a.hat) h itself at a.beta against a.ct, into the partials a.gpart [grid][p + 1].  firth_is_fused:
+//                one kernel and one read of X, else a.out [n] receives v and a second kernel streams X for X'v
+//                (both between e0 and e1).
+hipError_t launch_infl(int mode, int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
+                       hipEvent_t e1 = nullptr);
 bool firth_is_fused(int P16);
-hipError_t launch_firth(int P16, const InflArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
-                        hipEvent_t e1 = nullptr);
-hipError_t launch_firth_sum(const double* part, int nparts, int p, double* out, hipStream_t st);
+// out [ncol] = the workgroups' partials part [nparts][ncol] added in a fixed order (hpart: one column; gpart: p + 1)
+hipError_t launch_infl_sum(const double* part, int nparts, int ncol, double* out, hipStream_t st);
 
 // cluster sums (cluster.hip): the cluster-robust covariance's grouped scores
 // segments of the n rows under `ids` (cluster_segments: maximal runs of one id, cut at every multiple

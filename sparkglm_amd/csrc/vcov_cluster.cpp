@@ -155,33 +155,9 @@ int sglm_engine::set_clusters_local(const int32_t* ids, int64_t nl, int32_t G) {
 // enqueued on the stream, timed by evi0 / evi1
 int sglm_engine::uscore_local(const double* beta, int family, int link) {
   HIPCHK(hipSetDevice(device));
-  if (int rc = check_loaded()) return rc;
-  if (int rc = grow(domega, omega_cap, n_pad, "hipMalloc(score weights)")) return rc;
-  if (!evi0) HIPCHK(hipEventCreate(&evi0));
-  if (!evi1) HIPCHK(hipEventCreate(&evi1));
   for (hipEvent_t& e : evcl)
     if (!e) HIPCHK(hipEventCreate(&e));
-  const int P = (int)((p + 15) / 16);
-  std::memcpy(hbeta, beta, sizeof(double) * p);
-  HIPCHK(hipMemcpyAsync(dbeta, hbeta, sizeof(double) * p, hipMemcpyHostToDevice, st));
-  InflArgs a{};
-  a.X = dX;
-  a.ld = n_pad;
-  a.p = (int)p;
-  a.n = n;
-  a.beta = dbeta;
-  a.y = dy;
-  a.m = dm;
-  a.off = doff;
-  a.prior = dprior;
-  a.family = family;
-  a.link = link;
-  a.theta = theta;
-  a.need_q = 0;
-  a.out = domega;
-  if (n_pad > n) HIPCHK(hipMemsetAsync(domega + n, 0, sizeof(double) * (size_t)(n_pad - n), st));
-  HIPCHK(launch_uscore(P, a, influence_grid(P, ncu, n), st, evi0, evi1));
-  return SGLM_OK;
+  return rows_enqueue(INFL_USCORE, beta, nullptr, family, link, InflArgs{}, true);
 }
 
 // The internal engine on this device whose design is the G x p matrix of cluster sums
@@ -224,11 +200,8 @@ int sglm_engine::cluster_sums_local() {
 }
 
 int sglm_engine::cluster_sync() {
-  HIPCHK(hipSetDevice(device));
-  HIPCHK(hipStreamSynchronize(st));
+  if (int rc = rows_sync(&cl_ms[0])) return rc;
   float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, evi0, evi1));
-  cl_ms[0] = ms;
   HIPCHK(hipEventElapsedTime(&ms, evcl[0], evcl[1]));
   cl_ms[1] = ms;
   cl_ms[2] = 0.0;
@@ -431,8 +404,7 @@ int sglm_vcov_cluster(sglm_engine* h, const sglm_glm_opts* opts, const double* b
   std::vector<double> packed((size_t)packed_len(p));
   if (int rc = in->pass(MODE_LM_GRAM, nullptr, 0.0, 0.0, FAM_GAUSSIAN, LNK_IDENTITY, packed.data())) return rc;
   unpack_gram(packed.data(), p, M.data(), x.data());
-  for (int k = 0; k < 3; ++k)  // kernel times: the slowest shard
-    for (const sglm_engine* s : shards) h->cl_ms[k] = s == shards[0] ? s->cl_ms[k] : std::max(h->cl_ms[k], s->cl_ms[k]);
+  for (int k = 0; k < 3; ++k) h->cl_ms[k] = slowest_shard(h, [k](const sglm_engine* s) { return s->cl_ms[k]; });
   h->cl_ms[3] = in->last_pass_ms;
   double nrows = (double)(h->group() ? h->g_n : h->n);  // HC1: every row of every shard, weight 0 included
   if (hc_type == SGLM_HC1 && !h->group())

@@ -12,9 +12,15 @@ binomial log and sqrt at theta = 2.
 Diagnostics and the steps over the cluster factor (p = 5 and 65, the two-way designs of tests/fe2_reference.py,
 every family): fit_glm_fe, fit_glm_fe2, fit_glm_gee (exchangeable, rho fixed at 0.2, independence), fe_pass and
 gee_pass at 0.8 beta and in the initial mode (the GEE fits stop after GEE_ITERS iterations at the latest), vcov_fe, vcov_fe2 and vcov_gee (with their meats), influence (every
-residual type), vcov_robust and vcov_cluster at the plain fit's coefficients.  At p = 5 also the interleaved and
+residual type), vcov_robust (HC0, HC2, HC3) and vcov_cluster at the plain fit's coefficients, firth_pass with the
+leverages (binomial, Poisson) and predict_new_se of 1 000 new rows against vcov.  At p = 5 also the interleaved and
 shuffled id layouts of tests/fe_reference.py, and one Poisson case on a group handle of two shards on one device
 (the host sum over shards, the stale mark of the group sums).
+Grids at their device cap (binomial logit, n = 140 003 -- past 131 072 rows, where on 256 CUs the widest-stepping
+class, P16 <= 4, reaches its cap -- at p = 5, 65, 129, 161: one width per class of the row kernel's grid rule, the
+last on the two-kernel Firth route): influence, vcov_robust HC3, firth_pass with the leverages and a 5-iteration
+fit_glm_firth.  N above gives fewer steps than resident workgroups at every width, so only this block sees a
+wrong cap or step.
 A case that raises is recorded by its message, which must then be the same in every build."""
 import os
 import subprocess
@@ -26,6 +32,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 30_011
 GEE_ITERS = 25
+GRID_N = 140_003
+GRID_P = (5, 65, 129, 161)  # P16 = 1, 5, 9, 11
 
 
 def _fit_vec(f):
@@ -160,9 +168,14 @@ def _step_cases(res, e, key, fam, lnk, beta, two_way):
             ("V", "meat"), e.vcov_gee(bg, 0.2, fam, lnk, robust=rb, return_meat=True)))
 
 
+def _firth_pass(e, beta, fam, lnk):
+    r = e.firth_pass(beta, fam, lnk, hat=True)
+    return {"A": r["A"], "g": r["g"], "hat": r["hat"], "scalars": [r["deviance"], r["logdet"], r["sum_hat"]]}
+
+
 def child(out_path):
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
-    from sparkglm_amd import Engine, _lib as L
+    from sparkglm_amd import Engine, synth, _lib as L
     import fe_reference as FR
     import fe2_reference as F2
 
@@ -206,8 +219,37 @@ def child(out_path):
                             return {"hat": r.hat, "resid": r.resid, "cooks": r.cooks, "sum_hat": [r.sum_hat]}
                         _guard(res, f"{key}:influence:{rt}", infl)
                     _guard(res, key + ":vcov_robust", lambda: {"V": e.vcov_robust(beta, fam, lnk, type="HC3")})
+                    for hc in ("HC0", "HC2"):
+                        _guard(res, f"{key}:vcov_robust:{hc}", lambda: {"V": e.vcov_robust(beta, fam, lnk, type=hc)})
                     _guard(res, key + ":vcov_cluster", lambda: {"V": e.vcov_cluster(beta, fam, lnk, type="HC1")})
+                    if fam in ("binomial", "poisson"):
+                        _guard(res, key + ":firth_pass", lambda: _firth_pass(e, beta, fam, lnk))
+                    Xnew = np.random.default_rng(1000 + p).standard_normal((1000, p))
+                    _guard(res, key + ":predict_new_se", lambda: {"se": e.predict_new_se(Xnew, e.vcov(beta, fam, lnk))})
                 print("CASE", key, flush=True)
+
+        # grids at their device cap (GRID_N rows: more steps than resident workgroups at every width), one width
+        # per class of the grid rule
+        for p in GRID_P:
+            X, y, _, _ = synth.generate(0, 0, GRID_N, p, 7)
+            e.set_data(X, y)
+            key = f"grid:binomial:logit:{p}"
+            _guard(res, key, lambda: {"beta": e.fit_glm("binomial", "logit").coefs})
+            beta = res.get(key + ":beta", np.zeros(p))
+
+            def infl():
+                r = e.influence(beta, "binomial", "logit")
+                return {"hat": r.hat, "resid": r.resid, "cooks": r.cooks, "sum_hat": [r.sum_hat]}
+
+            def firth_fit():
+                r = e.fit_glm_firth("binomial", "logit", maxit=5)
+                return {"fit": _fit_vec(r.fit), "info": [r.converged, r.halvings, r.pen_deviance, r.logdet,
+                                                         r.score_inf, r.sum_hat]}
+            _guard(res, key + ":influence", infl)
+            _guard(res, key + ":vcov_robust", lambda: {"V": e.vcov_robust(beta, "binomial", "logit", type="HC3")})
+            _guard(res, key + ":firth_pass", lambda: _firth_pass(e, beta, "binomial", "logit"))
+            _guard(res, key + ":fit_glm_firth", firth_fit)
+            print("CASE", key, flush=True)
 
     # two shards on one device: the sums over shards go through the host, and the group sums turn stale
     with Engine(devices=[0, 0]) as e:

@@ -19,7 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-OBJECTS = ("kernels", "fused_odd", "narrow", "wide", "influence", "theta", "cluster", "fe_hip", "fe2_hip")
+OBJECTS = ("kernels", "fused_odd", "narrow", "wide", "influence", "theta", "cluster", "fe_hip", "fe2_hip",
+           "gee_hip")
 
 
 def _code_objects(run):
