@@ -473,7 +473,10 @@ __device__ __forceinline__ void gamma_inverse_row(double eta, double y, double o
 // small_exp selects exp_small over libm's exp.  Every narrow variant (p <= 64) passes true: round 4
 // measured it -1 % at p <= 32 and +4 % at p = 64 on that round's narrow kernel; round 5's rework of
 // the narrow pass (row stage at raised issue priority, block pairs at p > 32) set it for every width
-// without a separate p = 64 A/B of this choice.  The fused / wide kernels leave it off (neutral).
+// without a separate p = 64 A/B of this choice.  K1r's row stage passes true at every width (fused.hpp
+// row_stage_r) and K1 at 16 column blocks (P16 == 16, p = 241..256): exp_small runs on the 256-column
+// paths.  K1 below 16 column blocks and the wide row kernel leave it off (libm's exp).
+// tests/test_gpu_rowmath.py holds every instantiation's rows to the bars derived from these primitives.
 // ylogy: the narrow kernel's IRLS passes' table of the counts' y log y (ylogy_minus_yeta).
 __device__ __forceinline__ void pass_row(int fam, int lnk, int mode, double eta, double y, double m, double off,
                                          double pw, double mu0, double ybar, bool has_m, double& w, double& wz,
