@@ -9,15 +9,19 @@
 // The bracketed terms are grouped so that each group is formed without cancellation -- at a large theta every
 // one of psi(theta + y) - psi(theta), log theta - log(theta + mu) and 1 - (y + theta)/(mu + theta) is O(1/theta)
 // while the row's score is O(1/theta^2):
-//   D = psi(theta + y) - psi(theta)   small integer counts: the exact sum_{k < y} 1/(theta + k), else by digamma
+//   D = psi(theta + y) - psi(theta)   small integer counts: the exact sum_{k < y} 1/(theta + k); every other row:
+//       digamma_diff_pos (polygamma.hpp: the series subtracted term by term, log1p(y/theta) + ..., all terms >= 0)
 //   score row = D + log(theta/(mu + theta)) + (mu - y)/(mu + theta)      (the log as log1p(-mu/(mu + theta)))
-//   T = psi'(theta) - psi'(theta + y)  small integer counts: sum_{k < y} 1/(theta + k)^2, else by trigamma
+//   T = psi'(theta) - psi'(theta + y)  small integer counts: sum_{k < y} 1/(theta + k)^2, else trigamma_diff_pos
 //   info row  = T - mu/(theta (mu + theta)) + (mu - y)/(mu + theta)^2
+// No group is a difference of two rounded function values; the three groups of a row do cancel against each
+// other (that is the row's conditioning, tests/theta_reference.py's scale S).  The log-likelihood row is the
+// textbook sum of six terms and cancels at a large theta (3e-9 relative at theta = 1e8).
 // One partial of NS slots per workgroup (a contiguous row range, lanes then waves in a fixed order);
 // reduce_stats_kernel sums the partials in a fixed order, Neumaier-compensated.  No atomics: run-to-run bitwise.
 // Rows >= n are never read; a row of prior weight 0 contributes exactly 0 whatever its y and mu.  A row whose y is
 // not a finite value >= 0 makes the sums NaN (SGLM_EINVAL on the host); no loop's trip count depends on the data
-// beyond the bounds THETA_SUM_MAX and POLYGAMMA_MAX_TRIPS.
+// beyond the bounds THETA_SUM_MAX and POLYGAMMA_DIFF_TRIPS.
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
@@ -36,7 +40,6 @@ __global__ void __launch_bounds__(256) theta_terms_kernel(ThetaArgs a) {
   __shared__ double red[4][THETA_NT];
   const double th = a.theta;
   // the launch's constants (every thread forms them: ~100 instructions against its rows' thousands)
-  const double psi0 = digamma_pos(th), tri0 = trigamma_pos(th);
   const double lg0 = LL ? lgamma(th) : 0.0, tlt = LL ? th * log(th) : 0.0;
   double s[THETA_NT];
 #pragma unroll
@@ -54,7 +57,7 @@ __global__ void __launch_bounds__(256) theta_terms_kernel(ThetaArgs a) {
     // A count must be >= 0 and finite: any other y (negative, a missing-value sentinel, NaN, Inf) makes the
     // row's terms NaN -- the sums then are NaN and the host returns SGLM_EINVAL, as the pass kernels' invalid
     // rows do.  Every loop of a row is bounded whatever the data: the finite sums by THETA_SUM_MAX - 1 trips,
-    // the polygamma recurrences by POLYGAMMA_MAX_TRIPS (polygamma.hpp).
+    // the polygamma differences by POLYGAMMA_DIFF_TRIPS, a count that theta alone sets (polygamma.hpp).
     if (!(y >= 0.0) || !(y < INFINITY)) {
       D = T = NAN;
     } else if (y < (double)THETA_SUM_MAX && y == floor(y)) {
@@ -65,8 +68,7 @@ __global__ void __launch_bounds__(256) theta_terms_kernel(ThetaArgs a) {
         T += r * r;
       }
     } else {
-      D = digamma_pos(th + y) - psi0;
-      T = tri0 - trigamma_pos(th + y);
+      polygamma_diff_pos(th, y, &D, &T);
     }
     const double q = mu / mt, e = (mu - y) / mt;
     // log(theta/(mu + theta)): log1p where theta dominates (q rounds, 1 - q would cancel), the plain log otherwise

@@ -162,6 +162,10 @@ def _terms_case(n, lnk="log"):
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 3001, 70001])
 def test_theta_terms_against_scipy(n):
+    """The sums over n rows against the same formula in scipy double, at 1e-9 of `norm` (the operand magnitudes of
+    the ungrouped score).  That reference cancels as the formula does, so this bar cannot be tighter: at
+    theta = 1e4 it is twice the whole score.  What the rows are good to, per row and at a large theta, is held by
+    tests/test_gpu_theta_rows.py against exact values."""
     X, y, off, pw, beta, mu = _terms_case(n)
     with Engine(0) as e:
         e.set_data(X, y, offset=off, prior=pw)

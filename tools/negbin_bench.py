@@ -2,6 +2,7 @@
 
     python tools/negbin_bench.py pass  N P     # negbin/log pass against the Poisson/log pass (and, P > 64, the logit pass)
     python tools/negbin_bench.py theta N       # one theta_terms_kernel launch over N rows, with and without the loglik
+    python tools/negbin_bench.py thetarows N   # the theta kernel on counts on both sides of 17, theta = 2 and 1e3 (SGLM_LIB: an A/B)
     python tools/negbin_bench.py fit   N P     # a whole fit_glm_nb on overdispersed counts generated on the device
 
 Pass and theta times are kernel times from HIP events (sglm_stats / sglm_get_theta_ms); the fit's is wall time."""
@@ -62,6 +63,35 @@ def bench_theta(n):
           flush=True)
 
 
+def bench_theta_rows(n, reps=5):
+    """Kernel time per launch on rows that take both branches (integer counts below 17: the finite sums; the rest:
+    the polygamma differences), at a theta below and above the differences' switch.  Run once per library
+    (SGLM_LIB), alternating, for an A/B."""
+    rng = np.random.default_rng(17)
+    eta = rng.uniform(1.5, 3.5, n)                      # mu 4.5 .. 33
+    y = rng.poisson(np.exp(eta) * rng.gamma(2.0, 0.5, n)).astype(np.float64)
+    out = {"what": "theta_rows", "lib": os.environ.get("SGLM_LIB", "tree"), "n": n, "share_y_ge_17": float(np.mean(y >= 17)),
+           "reps": reps}
+    with Engine(0) as e:
+        e.set_data(eta.reshape(-1, 1), y, prior=rng.uniform(0.5, 1.5, n))
+        beta = np.ones(1)
+        for theta in (2.0, 1e3):
+            e.theta_terms(beta, theta)                  # warm-up
+            ms = []
+            for _ in range(reps):
+                k0, t0 = e.theta_ms()
+                e.theta_terms(beta, theta)              # the log-likelihood instantiation
+                k1, t1 = e.theta_ms()
+                ms.append((t1 - t0) / (k1 - k0))
+            out[f"loglik_launch_ms_theta{theta:g}"] = min(ms)
+            out[f"loglik_launch_ms_theta{theta:g}_range"] = [min(ms), max(ms)]
+        k0, t0 = e.theta_ms()
+        r = e.theta_ml(beta, limit=8)                   # the Newton instantiation, at theta.ml's own thetas
+        k1, t1 = e.theta_ms()
+        out.update(newton_launch_ms=(t1 - t0) / (k1 - k0), newton_launches=k1 - k0, theta_ml=r.theta)
+    print(json.dumps(out), flush=True)
+
+
 def bench_fit(n, p, theta_star=2.0):
     import torch
     dev = torch.device("cuda", 0)
@@ -102,5 +132,7 @@ if __name__ == "__main__":
         bench_pass(int(sys.argv[2]), int(sys.argv[3]))
     elif what == "theta":
         bench_theta(int(sys.argv[2]))
+    elif what == "thetarows":
+        bench_theta_rows(int(sys.argv[2]))
     else:
         bench_fit(int(sys.argv[2]), int(sys.argv[3]))
