@@ -75,7 +75,9 @@ extern "C" {
                               sglm_vcov_fe2, sglm_get_fe2_ms, sglm_fit_glm_gee (with sglm_gee_opts /
                               sglm_gee_info, enum sglm_corstr), sglm_gee_pass, sglm_vcov_gee,
                               sglm_get_gee_ms, sglm_fit_glm_firth (with sglm_firth_opts / sglm_firth_info),
-                              sglm_firth_pass, sglm_get_firth_ms; (new values only:) SGLM_SQRT and
+                              sglm_firth_pass, sglm_get_firth_ms, sglm_fit_multinom (with sglm_multinom_opts /
+                              sglm_multinom_info), sglm_multinom_pass, sglm_get_multinom_ms;
+                              (new values only:) SGLM_SQRT and
                               the non-canonical (family, link) pairs of enum sglm_link's table,
                               SGLM_NEGBIN and its three pairs */
 
@@ -716,6 +718,49 @@ int sglm_firth_pass(sglm_engine *h, const sglm_glm_opts *opts, const double *bet
                     double *scalars);
 /* Kernel time of the last Firth pass, ms (HIP events; the slowest shard; -1 before any call). */
 int sglm_get_firth_ms(sglm_engine *h, double *ms);
+
+/* ---- Multinomial logit fits (softmax regression; nnet::multinom, Stata mlogit, statsmodels MNLogit) ----
+ * A response with K unordered classes, 2 <= K <= 16, on a resident design with p <= 256 and q = (K - 1) p <= 1024.
+ * y holds the class code of each row as a double, an integer in 0 .. K - 1; class 0 is the baseline.  B is
+ * [p x (K - 1)] col-major, column j - 1 the coefficients of class j, so the parameter vector of length q is
+ * class-major: index (j - 1) p + c.  Per row eta_0 = 0, eta_j = x' beta_j, pi = softmax(eta) (formed against
+ * max(0, eta_1, ...); pi_0 is never 1 - sum); the deviance is D = -2 sum pw_i log pi_{y_i}, the log-likelihood
+ * -D / 2, aic = D + 2 q, the null deviance -2 sum_k N_k log(N_k / N) over the weighted class counts N_k (the
+ * intercept-only fit's closed form).  Score g = vec(X'R), R_ij = pw_i (1[y_i = j] - pi_ij); Hessian blocks
+ * H_jj = X' diag(pw pi_j (1 - pi_j)) X, H_jk = -X' diag(pw pi_j pi_k) X.  Prior weights are supported; a row of
+ * weight 0 contributes nothing and its y is not looked at.
+ * The fit is Newton's method from B = 0 (nnet's start) or B_start: delta = solve(H, g) by the engine's solve rule;
+ * B + t delta is tried at t = 1, 1/2, ... and accepted when D_new - D_old <= epsilon (|D_new| + 0.1), the search
+ * abandoned (converged = 0) after max_halvings halvings; after an accepted step the fit stops when
+ * |D_old - D_new| / (|D_new| + 0.1) < epsilon (R's glm.control rule), or at max_iter.
+ * SGLM_EINVAL, before the handle is looked at: n_classes outside 2 .. 16, a null opts / B, epsilon <= 0 or not
+ * finite, max_iter < 0, max_halvings < 0; then q > 1024, a procedural shard, p > 256 or SGLM_FORCE_WIDE, a handle
+ * that carries trials m or an offset; then a y of positive weight that is no class code, a class without weight.
+ * Collective over a communicator, multi-device handles included; two calls on the same shape and device give
+ * bitwise the same results (no floating-point atomics). */
+typedef struct {
+  int n_classes;    /* K */
+  double epsilon;   /* 1e-8 */
+  int max_iter;     /* 100 */
+  int max_halvings; /* per step; 12 */
+} sglm_multinom_opts;
+typedef struct {
+  int iter, halvings, converged; /* accepted steps; halvings over all steps; 0: max_iter or an abandoned search */
+  double deviance, null_deviance, loglik, aic, score_inf; /* at the returned coefficients; score_inf = |g|_inf */
+  double class_weight[16];       /* N_k, zeros past K */
+} sglm_multinom_info;
+/* One evaluation at B: H [q*q] col-major, g [q], scalars3 = {deviance, sum pw, null deviance}, prob [n x K]
+ * col-major (n: this handle's rows; a multi-device handle: every shard's, in row order); any output may be NULL.
+ * H, g and prob all NULL: the deviance-only evaluation (nothing stored per row). */
+int sglm_multinom_pass(sglm_engine *h, int n_classes, const double *B, double *H, double *g, double *scalars3,
+                       double *prob);
+/* B [q] out, std_err [q] = sqrt(diag(cov)), cov [q*q] = inv(H) at B; B_start, std_err, cov and info may be NULL. */
+int sglm_fit_multinom(sglm_engine *h, const sglm_multinom_opts *opts, const double *B_start, double *B,
+                      double *std_err, double *cov, sglm_multinom_info *info);
+/* Kernel times of the last call, ms (HIP events; the slowest shard; -1 before any call): the row kernel of the last
+ * evaluation, its second kernel X'R (0 at the fused shapes), and the weight kernels and Gram passes of the last
+ * Hessian, each summed over the K (K - 1) / 2 block pairs. */
+int sglm_get_multinom_ms(sglm_engine *h, double *rows_ms, double *xtr_ms, double *weight_ms, double *gram_ms);
 
 int sglm_get_stats(sglm_engine *h, sglm_stats *out);
 /* The kernel an engine would run a pass of an n x p shard with (enum sglm_pass_kernel, -1 on bad

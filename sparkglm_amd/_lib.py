@@ -45,6 +45,7 @@ EXPORTS = [
     "sglm_set_fe2", "sglm_fe2_plan", "sglm_fit_glm_fe2", "sglm_fe2_pass", "sglm_vcov_fe2", "sglm_get_fe2_ms",
     "sglm_fit_glm_gee", "sglm_gee_pass", "sglm_vcov_gee", "sglm_get_gee_ms",
     "sglm_fit_glm_firth", "sglm_firth_pass", "sglm_get_firth_ms",
+    "sglm_fit_multinom", "sglm_multinom_pass", "sglm_get_multinom_ms",
 ]
 PREDICT_LINK, PREDICT_RESPONSE = 0, 1
 RESID_TYPES = {"response": 0, "working": 1, "pearson": 2, "deviance": 3}  # enum sglm_resid_type
@@ -113,6 +114,19 @@ class FirthInfo(C.Structure):
     _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("halvings", C.c_int), ("deviance", C.c_double),
                 ("pen_deviance", C.c_double), ("logdet", C.c_double), ("score_inf", C.c_double),
                 ("sum_hat", C.c_double), ("firth_ms", C.c_double), ("pass_ms", C.c_double)]
+
+
+MULTINOM_MAX_K, MULTINOM_MAX_Q = 16, 1024  # classes; (K - 1) p
+
+
+class MultinomOpts(C.Structure):
+    _fields_ = [("n_classes", C.c_int), ("epsilon", C.c_double), ("max_iter", C.c_int), ("max_halvings", C.c_int)]
+
+
+class MultinomInfo(C.Structure):
+    _fields_ = [("iter", C.c_int), ("halvings", C.c_int), ("converged", C.c_int), ("deviance", C.c_double),
+                ("null_deviance", C.c_double), ("loglik", C.c_double), ("aic", C.c_double),
+                ("score_inf", C.c_double), ("class_weight", C.c_double * 16)]
 
 
 class PreLM(C.Structure):
@@ -280,6 +294,9 @@ def load():
                                 C.POINTER(FirthInfo)], C.c_int),
         "sglm_firth_pass": ([h, C.POINTER(GlmOpts), dp, dp, dp, dp, dp], C.c_int),
         "sglm_get_firth_ms": ([h, dp], C.c_int),
+        "sglm_multinom_pass": ([h, C.c_int, dp, dp, dp, dp, dp], C.c_int),
+        "sglm_fit_multinom": ([h, C.POINTER(MultinomOpts), dp, dp, dp, dp, C.POINTER(MultinomInfo)], C.c_int),
+        "sglm_get_multinom_ms": ([h, dp, dp, dp, dp], C.c_int),
         "sglm_cluster_plan": ([C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int64),
                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
     }

@@ -475,4 +475,27 @@ struct ThetaArgs {
   double* partials;     // [grid][NS]: THETA_NT sums, zeros in the other slots (reduce_stats_kernel's layout)
 };
 
+// Multinomial logit (multinom.hip): K classes, class 0 the baseline, B [p x (K - 1)] col-major.
+constexpr int MN_MAX_K = 16;
+constexpr int MN_MAX_Q = 1024;  // (K - 1) p at most: the host solve's order, and B beside the rows' slots in LDS
+// the scalars after the score in a workgroup's partial and in a pass's sums: sum pw log pi_y | sum pw | rows of
+// positive weight whose y is no class code | the weighted class counts [MN_MAX_K]
+enum MnScalar : int { MN_LL = 0, MN_SUMW = 1, MN_BAD = 2, MN_COUNT = 3, MN_NSC = 3 + MN_MAX_K };
+enum MnMode : int { MN_DEV = 0, MN_FULL = 1 };  // the scalars alone | also P, and the score (or R for multinom_xtr_kernel)
+struct MultinomArgs {
+  const double* X;      // col-major, leading dimension ld; columns >= p are never read
+  int64_t ld;
+  int p;
+  int K;
+  int64_t n;            // rows; rows >= n are never read or stored
+  const double* B;      // device [(K - 1) p]
+  const double* y;      // class codes
+  const double* prior;  // may be null
+  double* P;            // MN_FULL: the probabilities [K][ld]
+  double* R;            // MN_FULL past the fused shapes: R_ij = pw_i (1[y_i = j] - pi_ij), [K - 1][ld]
+  double* part;         // [grid][stride]: the score [nscore] (MN_FULL), then the MN_NSC scalars
+  int nscore;           // (K - 1) p, or 0 (MN_DEV)
+  int stride;           // nscore + MN_NSC
+};
+
 }  // namespace sglm

@@ -276,19 +276,6 @@ static int score_shards(sglm_engine* h, const double* beta, const double* cov, c
   return SGLM_OK;
 }
 
-namespace {
-// While it lives, the passes of the handle's shards weight their rows by the score weights.
-struct MeatPassScope {
-  sglm_engine* h;
-  explicit MeatPassScope(sglm_engine* handle) : h(handle) {
-    for (sglm_engine* s : h->shards()) s->meat_w = s->domega;
-  }
-  ~MeatPassScope() {
-    for (sglm_engine* s : h->shards()) s->meat_w = nullptr;
-  }
-};
-}  // namespace
-
 extern "C" {
 
 int sglm_vcov(sglm_engine* h, const sglm_glm_opts* opts, const double* beta, double* cov) {

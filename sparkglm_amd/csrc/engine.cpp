@@ -108,6 +108,7 @@ void sglm_engine::free_data() {
   nov = 0;
   ov_rows = 0;
   free_clusters(false);  // cluster ids belong to the rows they were declared for
+  free_multinom();
 }
 
 void sglm_engine::release() {

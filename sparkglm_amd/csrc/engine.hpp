@@ -1,6 +1,6 @@
 // engine.hpp -- the HIP engine behind the C ABI: what its host translation units share.
 // Private to engine.cpp, negbin.cpp, comm.cpp, wide_path.cpp, diagnostics.cpp, vcov_cluster.cpp, fe.cpp, fe2.cpp,
-// gee.cpp, firth.cpp and ingest.cpp; never included by a .hip file.  The steps over the cluster factor (fixed effects, two-way,
+// gee.cpp, firth.cpp, multinom.cpp and ingest.cpp; never included by a .hip file.  The steps over the cluster factor (fixed effects, two-way,
 // GEE) share one state per step kind (sglm_engine::GroupSums) and one frame (fe.cpp: group_sums_local,
 // group_sums_finish, group_gram; StepBackend and drive_step_fit below).
 #pragma once
@@ -259,6 +259,18 @@ struct sglm_engine : public sglm::Backend {
   int64_t gpart_cap = 0;
   double firth_ms = -1.0;                         // kernel time of the last Firth pass (-1: none yet)
 
+  // ---- multinomial logit (multinom.hip; multinom.cpp): sglm_fit_multinom / sglm_multinom_pass.  Allocated when
+  // first asked for, released with the data: the probabilities P [K][n_pad], past the fused shapes R [K - 1][n_pad],
+  // B [MN_MAX_Q], the workgroups' partials [grid][q + MN_NSC] and then their sum.  The Hessian's row weights go
+  // through domega.
+  double *dmnP = nullptr, *dmnR = nullptr, *dmnB = nullptr, *dmnpart = nullptr;
+  int64_t mnP_cap = 0, mnR_cap = 0, mnpart_cap = 0;
+  hipEvent_t evmn[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // rows start / end, X'R end, weights start / end
+  bool mn_two = false;  // the last full evaluation ran multinom_xtr_kernel
+  // kernel times of the last call: the row kernel, X'R (0: fused), the weight kernels and the Gram passes of the
+  // last Hessian, each summed over its block pairs (-1: none yet)
+  double mn_ms[4] = {-1.0, -1.0, -1.0, -1.0};
+
   // ---- cluster sums (cluster.hip; vcov_cluster.cpp): sglm_set_clusters / sglm_vcov_cluster ----
   int32_t cl_G = 0;                               // clusters declared for the resident rows (0: none set)
   int64_t cl_nseg = 0, cl_ntiles = 0;
@@ -439,6 +451,16 @@ struct sglm_engine : public sglm::Backend {
   int firth_local(const double* beta, const double* cov, int family, int link, double* g, double* hat);
   int predict_new_se(const double* X, int64_t nn, int64_t pp, int64_t ldx, const double* cov, double disp, double* out);
 
+  // ---- multinom.cpp ----
+  void free_multinom();
+  // The rows of this shard at B [(K - 1) p] in `mode` (common.hpp MnMode) and the fixed-order sum of the
+  // workgroups' partials, enqueued on the stream; then out [nscore + MN_NSC] = the score (MN_FULL) | the scalars,
+  // prob (or null) [K] columns ldp apart = P of this shard's rows, the stream drained, the kernel times taken
+  int multinom_enqueue(int K, const double* B, int mode);
+  int multinom_collect(int K, int mode, double* out, double* prob, int64_t ldp);
+  // domega = the row weights of the Hessian's block pair (j, k) from P, enqueued
+  int multinom_weight_local(int K, int j, int k);
+
   // ---- vcov_cluster.cpp ----
   void free_clusters(bool inner_too);
   int set_clusters_local(const int32_t* ids, int64_t nl, int32_t G);
@@ -603,6 +625,17 @@ double slowest_shard(const sglm_engine* h, F ms) {
 }
 // SGLM_EINVAL unless every shard is a resident design on the fused / narrow path
 int require_fused_or_narrow(const sglm_engine* h, const char* what);
+// While it lives, the passes of the handle's shards weight their rows by domega: the sandwich's score weights
+// (sglm_vcov_robust), the multinomial Hessian's block weights (multinom.cpp).
+struct MeatPassScope {
+  sglm_engine* h;
+  explicit MeatPassScope(sglm_engine* handle) : h(handle) {
+    for (sglm_engine* s : h->shards()) s->meat_w = s->domega;
+  }
+  ~MeatPassScope() {
+    for (sglm_engine* s : h->shards()) s->meat_w = nullptr;
+  }
+};
 // cov = f (C M C + (C M C)') / 2, exactly symmetric (col-major p x p, on the host); false: M or cov is not finite
 bool sandwich_product(const std::vector<double>& C, const std::vector<double>& M, int64_t p, double f, double* cov);
 

@@ -484,7 +484,11 @@ hipError_t launch_infl(int mode, int P16, const InflArgs& a, int grid, hipStream
 }
 
 hipError_t launch_infl_sum(const double* part, int nparts, int ncol, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(infl_sum_kernel, dim3(ncol), dim3(256), 0, st, part, nparts, ncol, out);
+  return launch_part_sum(part, nparts, ncol, ncol, out, st);
+}
+
+hipError_t launch_part_sum(const double* part, int nparts, int stride, int ncol, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(infl_sum_kernel, dim3(ncol), dim3(256), 0, st, part, nparts, stride, out);
   return hipGetLastError();
 }
 

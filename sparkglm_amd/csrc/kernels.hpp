@@ -77,6 +77,21 @@ bool firth_is_fused(int P16);
 // out [ncol] = the workgroups' partials part [nparts][ncol] added in a fixed order (hpart: one column; gpart: p + 1)
 hipError_t launch_infl_sum(const double* part, int nparts, int ncol, double* out, hipStream_t st);
 
+// multinomial logit (multinom.hip): p <= 256, 2 <= K <= MN_MAX_K, (K - 1) p <= MN_MAX_Q
+// workgroups of the row kernel (and, per column block, of multinom_xtr_kernel) over n rows: a fixed order
+int multinom_grid(int ncu, int64_t n);
+// the score accumulates in the row kernel's own read of X at this shape (else R is stored and a second kernel reads X)
+bool multinom_is_fused(int P16, int K);
+// The rows at a.B in `mode` (enum MnMode) with grid = multinom_grid: the partials a.part [grid][a.stride].  MN_FULL
+// past the fused shapes launches multinom_xtr_kernel behind the row kernel (e1 to e2; fused: e2 is not recorded).
+hipError_t launch_multinom_rows(int mode, int P16, const MultinomArgs& a, int grid, hipStream_t st,
+                                hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, hipEvent_t e2 = nullptr);
+// out [ld] = pw pi_j sum_{l != j} pi_l (j == k) or pw pi_j pi_k of the rows < n, zeros on the padding rows
+hipError_t launch_multinom_weight(const double* P, const double* prior, int64_t n, int64_t ld, int K, int j, int k,
+                                  double* out, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// launch_infl_sum over partials `stride` doubles apart (ncol <= stride)
+hipError_t launch_part_sum(const double* part, int nparts, int stride, int ncol, double* out, hipStream_t st);
+
 // cluster sums (cluster.hip): the cluster-robust covariance's grouped scores
 // segments of the n rows under `ids` (cluster_segments: maximal runs of one id, cut at every multiple
 // of CLUSTER_TILE_ROWS): seg_start [nseg + 1], seg_cluster [nseg], either may be null; returns nseg,

@@ -77,6 +77,24 @@ class FitFirth:
 
 
 @dataclass
+class FitMultinom:
+    """sglm_fit_multinom: coefs / stderr as [K - 1, p] tables (row j - 1: class j against the baseline, class 0),
+    cov [q, q] = inv(H) over the class-major parameter vector, everything at the returned coefficients."""
+    coefs: np.ndarray
+    stderr: np.ndarray
+    cov: np.ndarray
+    deviance: float
+    null_deviance: float
+    loglik: float
+    aic: float
+    iter: int
+    halvings: int
+    converged: bool
+    score_inf: float
+    class_weight: np.ndarray
+
+
+@dataclass
 class FitFE2:
     """sglm_fit_glm_fe2: the fit of beta, the effects alpha [G] and gamma [H] (NaN: a level without weight;
     gamma is 0 at the lowest factor-2 code of every component), the sweeps (last iteration, total), the levels
@@ -709,6 +727,63 @@ class Engine:
         t = C.c_double()
         L.check(self._lib.sglm_get_firth_ms(self._h, C.byref(t)), "sglm_get_firth_ms")
         return t.value
+
+    # ---- multinomial logit (softmax regression; p <= 256, K <= 16, (K - 1) p <= 1024) ----
+    def _multinom_B(self, B, K):
+        """B as the class-major parameter vector: [p, K - 1] (column j - 1: class j), or already flat."""
+        b = np.asarray(B, dtype=np.float64)
+        if b.ndim == 2:
+            if b.shape != (self.p, K - 1):
+                raise L.IllegalArgumentException(f"requirement failed: B is [p, n_classes - 1] = "
+                                                 f"[{self.p}, {K - 1}] (got {list(b.shape)})")
+            b = b.T
+        b = np.ascontiguousarray(b).reshape(-1)
+        if K >= 2 and b.shape[0] != (K - 1) * self.p:
+            raise L.IllegalArgumentException(f"requirement failed: B has (n_classes - 1) * p = {(K - 1) * self.p} "
+                                             f"entries (got {b.shape[0]})")
+        return b
+
+    def multinom_pass(self, B, n_classes, prob=False, hessian=True, score=False):
+        """One evaluation at B (sglm_multinom_pass): dict(H [q, q], g [q], deviance, sum_w, null_deviance; with
+        prob=True also prob [n, K]).  hessian=False: no Gram passes (g with score=True or prob=True); none of the
+        three: the deviance-only evaluation."""
+        K = int(n_classes)
+        b = self._multinom_B(B, K)
+        q = max(K - 1, 0) * self.p
+        H = np.zeros((q, q), order="F") if hessian else None
+        g = np.zeros(q) if hessian or prob or score else None
+        pr = np.zeros((self.n, K), order="F") if prob else None
+        s = np.zeros(3)
+        L.check(self._lib.sglm_multinom_pass(self._h, K, L.ptr(b), L.ptr(H), L.ptr(g), L.ptr(s), L.ptr(pr)),
+                "sglm_multinom_pass")
+        out = dict(deviance=float(s[0]), sum_w=float(s[1]), null_deviance=float(s[2]))
+        if hessian:
+            out["H"] = H
+        if g is not None:
+            out["g"] = g
+        if prob:
+            out["prob"] = pr
+        return out
+
+    def fit_multinom(self, n_classes, epsilon=1e-8, max_iter=100, start=None, max_halvings=12) -> FitMultinom:
+        """Newton's method with step halving on the deviance (sglm_fit_multinom) from B = 0 or `start`."""
+        K = int(n_classes)
+        o = L.MultinomOpts(K, float(epsilon), int(max_iter), int(max_halvings))
+        q = max(K - 1, 0) * self.p
+        b0 = None if start is None else self._multinom_B(start, K)
+        B, se, cov = np.zeros(q), np.zeros(q), np.zeros((q, q), order="F")
+        info = L.MultinomInfo()
+        L.check(self._lib.sglm_fit_multinom(self._h, C.byref(o), L.ptr(b0), L.ptr(B), L.ptr(se), L.ptr(cov),
+                                            C.byref(info)), "sglm_fit_multinom")
+        return FitMultinom(B.reshape(K - 1, self.p), se.reshape(K - 1, self.p), cov, info.deviance,
+                           info.null_deviance, info.loglik, info.aic, info.iter, info.halvings, bool(info.converged),
+                           info.score_inf, np.array(info.class_weight[:K]))
+
+    def multinom_ms(self):
+        """Kernel times (rows, X'R, weights, Gram passes) of the last multinomial call (HIP events)."""
+        t = [C.c_double() for _ in range(4)]
+        L.check(self._lib.sglm_get_multinom_ms(self._h, *[C.byref(v) for v in t]), "sglm_get_multinom_ms")
+        return tuple(v.value for v in t)
 
     # ---- two-way fixed effects: a second factor beside the one of set_clusters ----
     def set_fe2(self, ids, H=None):
