@@ -545,7 +545,8 @@ __global__ void __launch_bounds__(64 * Geo<P16>::NW, (Geo<P16>::WAVES_PER_SIMD))
 // Tile ownership (P16 = 16): Gram wave 0 = block row 15; Gram wave g = 1..7 = block rows g-1
 // and 15-g; every Gram wave also one tile (7, g) of block row 7 (17 tiles each).  (Measured and
 // not kept: the row waves owning block row 7's tiles after their row stage; a block barrier
-// instead of the LDS counters; no alternating issue priority -- DESIGN.md 4 K1r.)
+// instead of the LDS counters; no alternating issue priority -- DESIGN.md 4 K1r.  Since Gram waves
+// 0..3 issue the LDS-DMA, the priority goes by role instead of by turns: gram_steps_r.)
 // ---------------------------------------------------------------------------------
 
 // A wave's tiles are up to NSEG "segments", each a run of tiles (row, j0 .. j0+cnt-1) of one
@@ -554,14 +555,48 @@ __global__ void __launch_bounds__(64 * Geo<P16>::NW, (Geo<P16>::WAVES_PER_SIMD))
 // (16 tiles) + tile (7, g) of block row 7.  Other P16 (the mid-width generalisation): the tile
 // rows taken in pairs (0, P16-1), (1, P16-2), ... -- P16 + 1 tiles a pair -- and that sequence of
 // tiles cut into 8 equal contiguous runs, one per Gram wave (at most NSEG segments each).
+//
+// SGLM_K1R_ISPLIT (P16 = 16; a build-time knob for A/B timing): tiles of each of
+// Gram waves 0..3, the ones that also issue the LDS-DMA (pass_body_r, GDMA) -- their SIMD partners,
+// waves 4..7, hold the rest of the SIMD's 34.  17: the map above.  16: the issuers keep their 16
+// whole-row tiles and partner w + 4 takes the pair (7, 2w), (7, 2w + 1) of block row 7 (18 tiles,
+// still three segments).  15: as 16, and issuer w also hands the diagonal tile (15-w, 15-w) that
+// ends its HI row to its partner (19 tiles, a fourth segment).  Whichever wave owns a tile sums
+// the same k-steps in the same order, so every map is bitwise the others.
+// Measured and not kept (profiles/k1r_tilesplit_ab.txt): at the 168 VGPRs of three waves per SIMD
+// an 18th accumulator does not fit -- 16 / 18 holds 64-80 B of scratch (one accumulator reloaded
+// inside the k-steps, whatever SGLM_K1R_PRA) and runs 28.8 ms against 21.9, 15 / 19 holds
+// 640-704 B and runs 88 ms; the default 17 / 17 compiles to the code it did without the knob.
+// SGLM_K1R_IPRIO (gram_steps_r) holds no scratch either way.
+#ifndef SGLM_K1R_ISPLIT
+#define SGLM_K1R_ISPLIT 17
+#endif
+#ifndef SGLM_K1R_PRA
+#define SGLM_K1R_PRA 4  // B-side reads in flight ahead of the MFMAs on waves 4..7 when they hold 18 or 19 tiles
+#endif
+#ifndef SGLM_K1R_IPRIO
+#define SGLM_K1R_IPRIO 1  // 1: the issuers hold the higher issue priority; 0: turns (gram_steps_r)
+#endif
+static_assert(SGLM_K1R_ISPLIT >= 15 && SGLM_K1R_ISPLIT <= 17, "SGLM_K1R_ISPLIT: 15, 16 or 17 tiles per issuer wave");
 template <int P16, int WV>
 struct TilesR {
   static constexpr bool ROW = WV >= 8;
+  // P16 = 16 with another share than 17: ISSUER -- the Gram wave also issues the LDS-DMA; PW -- a partner's issuer
+  static constexpr bool SPLIT = P16 == 16 && SGLM_K1R_ISPLIT != 17;
+  static constexpr bool ISSUER = WV < 4;
+  static constexpr int PW = WV - 4;
   using S = TileSeq<P16>;
   static constexpr int tlo() { return S::T * WV / 8; }
   static constexpr int thi() { return S::T * (WV + 1) / 8; }
   static constexpr int row(int s) {
-    if constexpr (P16 == 16) {
+    if constexpr (SPLIT) {
+      if (ROW) return -1;
+      if (s == 0) return WV >= 1 ? WV - 1 : -1;  // LO row
+      if (s == 1) return 15 - WV;                // HI row
+      if (s == 2) return ISSUER ? -1 : 7;        // the partners' pairs of block row 7
+      if (s == 3) return SGLM_K1R_ISPLIT == 15 && !ISSUER ? 15 - PW : -1;  // the issuer's HI diagonal tile
+      return -1;
+    } else if constexpr (P16 == 16) {
       if (ROW) return -1;
       if (s == 0) return WV >= 1 ? WV - 1 : -1;   // LO row
       if (s == 1) return WV == 0 ? 15 : 15 - WV;  // HI row
@@ -574,12 +609,17 @@ struct TilesR {
     }
   }
   static constexpr int j0(int s) {
-    if constexpr (P16 == 16) return s == 2 ? WV : 0;
+    if constexpr (SPLIT) return s == 2 ? 2 * PW : s == 3 ? 15 - PW : 0;
+    else if constexpr (P16 == 16) return s == 2 ? WV : 0;
     else return s == 0 && !ROW && thi() > tlo() ? tlo() - S::seq_start(S::seq_of(tlo())) : 0;
   }
   static constexpr int cnt(int s) {
     if (row(s) < 0) return 0;
-    if constexpr (P16 == 16) {
+    if constexpr (SPLIT) {
+      if (s == 2) return 2;
+      if (s == 3) return 1;
+      return row(s) + 1 - (s == 1 && SGLM_K1R_ISPLIT == 15 && ISSUER ? 1 : 0);
+    } else if constexpr (P16 == 16) {
       return s == 2 ? 1 : row(s) + 1;
     } else {
       const int i = S::seq_of(tlo()) + s;
@@ -600,6 +640,17 @@ struct TilesR {
     return sg;
   }
   static_assert(P16 == 16 || ROW || row(NSEG) < 0 || true, "segments");
+  // operand reads a k-step issues before its first MFMA (gram_steps_r): w and the A side, then 6
+  // B-side reads -- SGLM_K1R_PRA of them on a partner that holds more than 17 tiles, whose
+  // accumulators leave fewer of the 168 registers for operands in flight
+  static constexpr int AHEAD = SPLIT && !ISSUER && !ROW ? (cnt(3) > 0 ? 5 : 4) + SGLM_K1R_PRA : 4 + 6;
+  // marks[t] += 1 for every tile t = row (row + 1) / 2 + column this wave owns
+  static constexpr void mark(int* marks) {
+    for (int k = 0; k < NT; ++k) {
+      const int sg = seg_of(k), bi = row(sg), bj = j0(sg) + k - off(sg);
+      if (bi >= 0 && bi < P16 && bj >= 0 && bj <= bi) ++marks[bi * (bi + 1) / 2 + bj];
+    }
+  }
 };
 
 // K1r's LDS: a ring of NBUF row-block buffers -- as deep as 160 KB allows (4 up to P16 = 8, 3 up to
@@ -655,6 +706,24 @@ struct GeoR {
            G::T;
   }
   static_assert(tiles_ok(), "the Gram waves' segments cover the tile triangle");
+  // P16 = 16 (SGLM_K1R_ISPLIT): every tile of the triangle has exactly one owner, and the two Gram
+  // waves of a SIMD (w and w + 4) hold 34 tiles between them whatever the issuers' share
+  static constexpr bool tiles_once() {
+    int marks[G::T] = {};
+    TilesR<P16, 0>::mark(marks), TilesR<P16, 1>::mark(marks), TilesR<P16, 2>::mark(marks), TilesR<P16, 3>::mark(marks);
+    TilesR<P16, 4>::mark(marks), TilesR<P16, 5>::mark(marks), TilesR<P16, 6>::mark(marks), TilesR<P16, 7>::mark(marks);
+    for (int t = 0; t < G::T; ++t)
+      if (marks[t] != 1) return false;
+    return true;
+  }
+  static constexpr bool simd_pairs_ok() {
+    return TilesR<P16, 0>::NT + TilesR<P16, 4>::NT == 34 && TilesR<P16, 1>::NT + TilesR<P16, 5>::NT == 34 &&
+           TilesR<P16, 2>::NT + TilesR<P16, 6>::NT == 34 && TilesR<P16, 3>::NT + TilesR<P16, 7>::NT == 34 &&
+           TilesR<P16, 0>::NT == SGLM_K1R_ISPLIT && TilesR<P16, 1>::NT == SGLM_K1R_ISPLIT &&
+           TilesR<P16, 2>::NT == SGLM_K1R_ISPLIT && TilesR<P16, 3>::NT == SGLM_K1R_ISPLIT;
+  }
+  static_assert(P16 != 16 || tiles_once(), "every tile of the triangle is owned by exactly one Gram wave");
+  static_assert(P16 != 16 || simd_pairs_ok(), "waves w and w + 4 hold 34 tiles: every SIMD the same MFMA load");
 };
 
 // X'Wz of block `buf` on the row waves (the Gram waves keep only their MFMA operands): row wave
@@ -965,7 +1034,7 @@ __device__ __forceinline__ void gram_steps_r(const double* lds, int buf, int lan
     // Keep 6 B-operand reads in flight ahead of the MFMAs (under the 168-VGPR budget of three
     // waves per SIMD the default schedule waits for every read in turn): the A-side reads and the
     // first reads, then one MFMA per further read.
-    __builtin_amdgcn_sched_group_barrier(0x100, 4 + 6, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, T::AHEAD, 0);
 #pragma unroll
     for (int k = 0; k < T::NT; ++k) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -976,12 +1045,18 @@ __device__ __forceinline__ void gram_steps_r(const double* lds, int buf, int lan
   for (int j = 0; j < RB / 4; j += 2) {
     // the two Gram waves of a SIMD take turns at the higher issue priority, one k-step each, so
     // neither runs ahead and leaves the other alone at the end of the block (oldest-first
-    // arbitration: waves 0-3 finished their Gram ~7K cycles before waves 4-7)
+    // arbitration: waves 0-3 finished their Gram ~7K cycles before waves 4-7).
+    // P16 = 16 (SGLM_K1R_IPRIO=1, the default; 0 builds the turns for A/B timing): no turns --
+    // the wave that issues the DMA keeps the higher priority through all its k-steps, its partner
+    // the lower.  Its k-steps are followed by the serial done wait -> DMA issue -> landing that
+    // every block's row stage waits for, while its partner has 5-8K cycles of slack at `ready`
+    // (profiles/k1r_tilesplit_ab.txt).
+    constexpr bool TURNS = !(P16 == 16 && SGLM_K1R_IPRIO);
     if constexpr (!T::ROW) __builtin_amdgcn_s_setprio((WV >> 2) & 1 ? 0 : 1);
     kstep(j);
     if (SGLM_K1R_STAMPS == 2 && j == 0) st.lap(2);
     if (SGLM_K1R_STAMPS == 3 && j == 0) st.ev(9);
-    if constexpr (!T::ROW) __builtin_amdgcn_s_setprio((WV >> 2) & 1 ? 1 : 0);
+    if constexpr (!T::ROW && TURNS) __builtin_amdgcn_s_setprio((WV >> 2) & 1 ? 1 : 0);
     kstep(j + 1);
   }
 }
