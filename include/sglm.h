@@ -76,7 +76,8 @@ extern "C" {
                               sglm_gee_info, enum sglm_corstr), sglm_gee_pass, sglm_vcov_gee,
                               sglm_get_gee_ms, sglm_fit_glm_firth (with sglm_firth_opts / sglm_firth_info),
                               sglm_firth_pass, sglm_get_firth_ms, sglm_fit_multinom (with sglm_multinom_opts /
-                              sglm_multinom_info), sglm_multinom_pass, sglm_get_multinom_ms;
+                              sglm_multinom_info), sglm_multinom_pass, sglm_get_multinom_ms,
+                              sglm_vcov_multinom_robust, sglm_set_multinom_route;
                               (new values only:) SGLM_SQRT and
                               the non-canonical (family, link) pairs of enum sglm_link's table,
                               SGLM_NEGBIN and its three pairs */
@@ -757,10 +758,23 @@ int sglm_multinom_pass(sglm_engine *h, int n_classes, const double *B, double *H
 /* B [q] out, std_err [q] = sqrt(diag(cov)), cov [q*q] = inv(H) at B; B_start, std_err, cov and info may be NULL. */
 int sglm_fit_multinom(sglm_engine *h, const sglm_multinom_opts *opts, const double *B_start, double *B,
                       double *std_err, double *cov, sglm_multinom_info *info);
+/* The robust (sandwich) covariance of a multinomial model at B (Stata mlogit, vce(robust); statsmodels MNLogit
+ * cov_type="HC0"; sandwich::sandwich on nnet::multinom):
+ * cov [q*q] col-major = C M C (x n / (n - q) for SGLM_HC1), C = inv(H) at B, M = sum_i (r_i r_i') (x) x_i x_i',
+ * r_i = pw_i (e_{y_i} - pi_i); n: every row of every shard and rank, weight 0 included.
+ * meat [q*q] may be NULL.  SGLM_HC2 / SGLM_HC3 (per-row leverage blocks): SGLM_EINVAL.  Collective.
+ * The handle is what sglm_fit_multinom takes (no trials, no offset; (K - 1) p <= 1024); y and the class weights are
+ * validated as in a fit; a non-finite M or cov is SGLM_EINVAL.  The resident data and a later fit are unchanged. */
+int sglm_vcov_multinom_robust(sglm_engine *h, int n_classes, const double *B, int hc_type, double *cov, double *meat);
 /* Kernel times of the last call, ms (HIP events; the slowest shard; -1 before any call): the row kernel of the last
  * evaluation, its second kernel X'R (0 at the fused shapes), and the weight kernels and Gram passes of the last
- * Hessian, each summed over the K (K - 1) / 2 block pairs. */
+ * Hessian (or meat), each summed over the K (K - 1) / 2 block pairs.  At p <= 64 the block Gram kernel forms every
+ * block from one read of X per slice where it is the faster route: weight_ms is 0 and gram_ms is that kernel's time. */
 int sglm_get_multinom_ms(sglm_engine *h, double *rows_ms, double *xtr_ms, double *weight_ms, double *gram_ms);
+/* For the measuring tools and the tests: how the Hessian and the meat are formed at p <= 64.  0 (the default): the
+ * measured rule chooses per (p, K); 1: one Gram pass per block pair (the route every p > 64 takes);
+ * 2: the block Gram kernel.  Another value: SGLM_EINVAL. */
+int sglm_set_multinom_route(sglm_engine *h, int route);
 
 int sglm_get_stats(sglm_engine *h, sglm_stats *out);
 /* The kernel an engine would run a pass of an n x p shard with (enum sglm_pass_kernel, -1 on bad

@@ -46,6 +46,7 @@ EXPORTS = [
     "sglm_fit_glm_gee", "sglm_gee_pass", "sglm_vcov_gee", "sglm_get_gee_ms",
     "sglm_fit_glm_firth", "sglm_firth_pass", "sglm_get_firth_ms",
     "sglm_fit_multinom", "sglm_multinom_pass", "sglm_get_multinom_ms",
+    "sglm_vcov_multinom_robust", "sglm_set_multinom_route",
 ]
 PREDICT_LINK, PREDICT_RESPONSE = 0, 1
 RESID_TYPES = {"response": 0, "working": 1, "pearson": 2, "deviance": 3}  # enum sglm_resid_type
@@ -297,6 +298,8 @@ def load():
         "sglm_multinom_pass": ([h, C.c_int, dp, dp, dp, dp, dp], C.c_int),
         "sglm_fit_multinom": ([h, C.POINTER(MultinomOpts), dp, dp, dp, dp, C.POINTER(MultinomInfo)], C.c_int),
         "sglm_get_multinom_ms": ([h, dp, dp, dp, dp], C.c_int),
+        "sglm_vcov_multinom_robust": ([h, C.c_int, dp, C.c_int, dp, dp], C.c_int),
+        "sglm_set_multinom_route": ([h, C.c_int], C.c_int),
         "sglm_cluster_plan": ([C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int64),
                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
     }

@@ -498,4 +498,23 @@ struct MultinomArgs {
   int stride;           // nscore + MN_NSC
 };
 
+// Block Gram (blockgram.hip): every block G_jk = sum_i omega_jk(i) x_i x_i', 1 <= j <= k <= K - 1,
+// of the multinomial Hessian (BG_HESS) or of the robust covariance's meat (BG_MEAT) from one read of X per slice.
+// The block pairs are numbered m = 0 .. K (K - 1) / 2 - 1 in the order (1, 1), (1, 2), .., (1, K - 1), (2, 2), ..
+enum BgMode : int { BG_HESS = 0, BG_MEAT = 1 };
+constexpr int BG_TILE = 256;  // a 16 x 16 tile, row-major: element (i, j) of tile (bi, bj) is G[16 bi + i][16 bj + j]
+struct BlockGramArgs {
+  const double* X;      // col-major, leading dimension ld (a multiple of RB), whole column octets stored
+  int64_t ld;
+  int p;
+  int K;
+  int64_t n;            // rows >= n contribute exactly 0
+  const double* P;      // the probabilities [K][ld] of the last MN_FULL evaluation (rows >= n: never looked at)
+  const double* y;      // class codes (BG_MEAT; not looked at on a row of weight 0)
+  const double* prior;  // may be null
+  int m0, cnt;          // this launch's slice: the block pairs m0 .. m0 + cnt - 1
+  double* part;         // [grid][stride]: tile t = bi (bi + 1) / 2 + bj of pair m at ((m - m0) T + t) BG_TILE
+  int64_t stride;
+};
+
 }  // namespace sglm

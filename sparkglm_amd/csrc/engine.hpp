@@ -270,6 +270,13 @@ struct sglm_engine : public sglm::Backend {
   // kernel times of the last call: the row kernel, X'R (0: fused), the weight kernels and the Gram passes of the
   // last Hessian, each summed over its block pairs (-1: none yet)
   double mn_ms[4] = {-1.0, -1.0, -1.0, -1.0};
+  // block Gram (blockgram.hip; p <= 64): the workgroups' partials [grid][blockgram_stride], reused by every slice,
+  // then the summed tiles [M][T][BG_TILE]; allocated at first use, released with the data
+  double* dbgpart = nullptr;
+  int64_t bgpart_cap = 0;
+  hipEvent_t evbg[2] = {nullptr, nullptr};
+  double bg_ms = -1.0;       // kernel time of the last block Gram (its slices and their sums)
+  int mn_route = 0;  // sglm_set_multinom_route: 0 the measured rule (blockgram_preferred), 1 per block, 2 block kernel
 
   // ---- cluster sums (cluster.hip; vcov_cluster.cpp): sglm_set_clusters / sglm_vcov_cluster ----
   int32_t cl_G = 0;                               // clusters declared for the resident rows (0: none set)
@@ -459,7 +466,11 @@ struct sglm_engine : public sglm::Backend {
   int multinom_enqueue(int K, const double* B, int mode);
   int multinom_collect(int K, int mode, double* out, double* prob, int64_t ldp);
   // domega = the row weights of the Hessian's block pair (j, k) from P, enqueued
-  int multinom_weight_local(int K, int j, int k);
+  int multinom_weight_local(int K, int j, int k, bool meat = false);
+  // The block Gram of this shard in `mode` (enum BgMode) at the P of the last full evaluation, enqueued on the
+  // stream; then tiles [M][T][BG_TILE] on the host (synchronises; bg_ms: the kernel time)
+  int blockgram_enqueue(int K, int mode);
+  int blockgram_collect(int K, double* tiles);
 
   // ---- vcov_cluster.cpp ----
   void free_clusters(bool inner_too);

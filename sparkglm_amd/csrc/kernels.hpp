@@ -86,11 +86,23 @@ bool multinom_is_fused(int P16, int K);
 // past the fused shapes launches multinom_xtr_kernel behind the row kernel (e1 to e2; fused: e2 is not recorded).
 hipError_t launch_multinom_rows(int mode, int P16, const MultinomArgs& a, int grid, hipStream_t st,
                                 hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, hipEvent_t e2 = nullptr);
-// out [ld] = pw pi_j sum_{l != j} pi_l (j == k) or pw pi_j pi_k of the rows < n, zeros on the padding rows
-hipError_t launch_multinom_weight(const double* P, const double* prior, int64_t n, int64_t ld, int K, int j, int k,
-                                  double* out, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// out [ld] = pw pi_j sum_{l != j} pi_l (j == k) or pw pi_j pi_k of the rows < n, zeros on the padding rows; y != null:
+// the meat's signed weights r_j r_k instead
+hipError_t launch_multinom_weight(const double* P, const double* prior, const double* y, int64_t n, int64_t ld, int K,
+                                  int j, int k, double* out, hipStream_t st, hipEvent_t e0 = nullptr,
+                                  hipEvent_t e1 = nullptr);
 // launch_infl_sum over partials `stride` doubles apart (ncol <= stride)
 hipError_t launch_part_sum(const double* part, int nparts, int stride, int ncol, double* out, hipStream_t st);
+
+// block Gram (blockgram.hip): every block pair of a multinomial Hessian or meat at p <= 64, one read of X per slice
+bool blockgram_preferred(int P16, int K);   // the measured rule: this kernel over a Gram pass per block pair
+int blockgram_pairs_per_slice(int P16);    // block pairs one launch holds in registers (0: no kernel for this width)
+int blockgram_slices(int P16, int K);      // launches -- reads of X -- for the K (K - 1) / 2 pairs
+int64_t blockgram_stride(int P16, int K);  // doubles per workgroup partial (the largest slice's tiles)
+int blockgram_grid(int ncu, int64_t n);    // one workgroup per CU at most: a function of the shape and the device
+// out [M][T][BG_TILE] (pair-major, lower-triangular tiles) in `mode` (enum BgMode) from a.X, a.P, a.y, a.prior with
+// grid = blockgram_grid and a.part of grid * blockgram_stride doubles; a.m0, a.cnt and a.stride are set here
+hipError_t launch_blockgram(int mode, int P16, BlockGramArgs a, int grid, double* out, hipStream_t st);
 
 // cluster sums (cluster.hip): the cluster-robust covariance's grouped scores
 // segments of the n rows under `ids` (cluster_segments: maximal runs of one id, cut at every multiple

@@ -8,8 +8,11 @@
 // the small all-reduce.  The Hessian H = sum_i (diag(pi_i) - pi_i pi_i') (x) x_i x_i' is K (K - 1) / 2 symmetric
 // p x p blocks X' diag(omega) X: for each pair the weight kernel writes omega into the shard's score weights and the
 // tuned Gram pass runs under the meat-pass scope, as the sandwich covariance's meat does; the off-diagonal blocks'
-// weights are pw pi_j pi_k >= 0 and the block is negated here.  The fit is Newton's method with step halving on
+// weights are pw pi_j pi_k >= 0 and the block is negated here.  At p <= 64 the block kernel (blockgram.hip, K16)
+// forms every block from one read of X per slice instead.  The fit is Newton's method with step halving on
 // the deviance (deviance-only evaluations) and R's glm.control stop rule.
+// sglm_vcov_multinom_robust: the sandwich C M C with the meat M = sum_i (r_i r_i') (x) x_i x_i', the same blocks
+// under the weights r_j r_k.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -19,11 +22,11 @@
 using namespace sglm;
 
 void sglm_engine::free_multinom() {
-  dev_free({&dmnP, &dmnR, &dmnB, &dmnpart});
-  mnP_cap = mnR_cap = mnpart_cap = 0;
-  for (hipEvent_t& e : evmn) {
-    if (e) (void)hipEventDestroy(e);
-    e = nullptr;
+  dev_free({&dmnP, &dmnR, &dmnB, &dmnpart, &dbgpart});
+  mnP_cap = mnR_cap = mnpart_cap = bgpart_cap = 0;
+  for (hipEvent_t* ev : {evmn, evmn + 1, evmn + 2, evmn + 3, evmn + 4, evbg, evbg + 1}) {
+    if (*ev) (void)hipEventDestroy(*ev);
+    *ev = nullptr;
   }
 }
 
@@ -95,15 +98,59 @@ int sglm_engine::multinom_collect(int K, int mode, double* out, double* prob, in
   return SGLM_OK;
 }
 
-int sglm_engine::multinom_weight_local(int K, int j, int k) {
+int sglm_engine::multinom_weight_local(int K, int j, int k, bool meat) {
   HIPCHK(hipSetDevice(device));
   if (int rc = grow(domega, omega_cap, n_pad, "hipMalloc(score weights)")) return rc;
   if (n_pad > 0) {
-    HIPCHK(launch_multinom_weight(dmnP, dprior, n, n_pad, K, j, k, domega, st, evmn[3], evmn[4]));
+    HIPCHK(launch_multinom_weight(dmnP, dprior, meat ? dy : nullptr, n, n_pad, K, j, k, domega, st, evmn[3], evmn[4]));
   } else {
     HIPCHK(hipEventRecord(evmn[3], st));
     HIPCHK(hipEventRecord(evmn[4], st));
   }
+  return SGLM_OK;
+}
+
+int sglm_engine::blockgram_enqueue(int K, int mode) {
+  HIPCHK(hipSetDevice(device));
+  if (int rc = check_loaded()) return rc;
+  for (hipEvent_t& e : evbg)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  const int P16 = (int)((p + 15) / 16), T = P16 * (P16 + 1) / 2, M = K * (K - 1) / 2;
+  const int64_t len = (int64_t)M * T * BG_TILE;
+  const int grid = blockgram_grid(ncu, n);
+  // the partials, then the summed tiles in the buffer's last len doubles (blockgram_collect, the all-reduce)
+  if (int rc = grow(dbgpart, bgpart_cap, (int64_t)grid * blockgram_stride(P16, K) + len, "hipMalloc(block Gram partials)"))
+    return rc;
+  double* out = dbgpart + (bgpart_cap - len);
+  HIPCHK(hipEventRecord(evbg[0], st));
+  if (n > 0) {
+    BlockGramArgs a{};
+    a.X = dX;
+    a.ld = n_pad;
+    a.p = (int)p;
+    a.K = K;
+    a.n = n;
+    a.P = dmnP;
+    a.y = dy;
+    a.prior = dprior;
+    a.part = dbgpart;
+    HIPCHK(launch_blockgram(mode, P16, a, grid, out, st));
+  } else {
+    HIPCHK(hipMemsetAsync(out, 0, sizeof(double) * (size_t)len, st));
+  }
+  HIPCHK(hipEventRecord(evbg[1], st));
+  return SGLM_OK;
+}
+
+int sglm_engine::blockgram_collect(int K, double* tiles) {
+  HIPCHK(hipSetDevice(device));
+  const int P16 = (int)((p + 15) / 16), T = P16 * (P16 + 1) / 2, M = K * (K - 1) / 2;
+  const int64_t len = (int64_t)M * T * BG_TILE;
+  HIPCHK(hipMemcpyAsync(tiles, dbgpart + (bgpart_cap - len), sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  float t = 0.f;
+  HIPCHK(hipEventElapsedTime(&t, evbg[0], evbg[1]));
+  bg_ms = t;
   return SGLM_OK;
 }
 
@@ -171,15 +218,74 @@ int mn_eval(sglm_engine* h, int K, const double* B, int mode, std::vector<double
 
 double mn_deviance(const std::vector<double>& out) { return -2.0 * out[out.size() - MN_NSC + MN_LL]; }
 
-// H [q x q] col-major at the P of the last full evaluation: a Gram pass per block pair (collective)
-int mn_hessian(sglm_engine* h, int K, double* H) {
+// One block pair's p x p matrix G (symmetric; its lower triangle is read) into the class-major q x q matrix: the
+// blocks (j, k) and (k, j), mirrored to exact symmetry
+void mn_place_block(const double* G, int64_t p, int64_t q, int j, int k, double sign, double* H) {
+  for (int64_t a = 0; a < p; ++a)
+    for (int64_t b = 0; b <= a; ++b) {
+      const double v = sign * G[(size_t)(a + b * p)];
+      const int64_t ja = (j - 1) * p + a, jb = (j - 1) * p + b, ka = (k - 1) * p + a, kb = (k - 1) * p + b;
+      H[ja + kb * q] = H[jb + ka * q] = H[kb + ja * q] = H[ka + jb * q] = v;
+    }
+}
+
+// The block kernel's route (p <= 64): every shard's tiles from one read of X per slice, summed over shards in
+// order and over ranks, then unpacked
+int mn_blocks_one_read(sglm_engine* h, int K, int mode, double* H) {
   const int64_t p = h->ncols(), q = (int64_t)(K - 1) * p;
+  const int P16 = (int)((p + 15) / 16), T = P16 * (P16 + 1) / 2, M = K * (K - 1) / 2;
+  const int64_t len = (int64_t)M * T * BG_TILE;
+  const std::vector<sglm_engine*>& shards = h->shards();
+  for (sglm_engine* s : shards)
+    if (int rc = s->blockgram_enqueue(K, mode)) return rc;
+  std::vector<double> tiles((size_t)len, 0.0), part((size_t)len);
+  for (sglm_engine* s : shards) {
+    if (int rc = s->blockgram_collect(K, part.data())) return rc;
+    for (int64_t i = 0; i < len; ++i) tiles[(size_t)i] += part[(size_t)i];
+  }
+  h->mn_ms[2] = 0.0;
+  h->mn_ms[3] = slowest_shard(h, [](const sglm_engine* s) { return s->bg_ms; });
+  if (!h->group() && h->comm.kind != 0) {
+    if (h->comm_on_device()) {  // through the summed tiles' own device buffer
+      HIPCHK(hipSetDevice(h->device));
+      double* dev = h->dbgpart + (h->bgpart_cap - len);
+      HIPCHK(hipMemcpyAsync(dev, tiles.data(), sizeof(double) * (size_t)len, hipMemcpyHostToDevice, h->st));
+      if (int rc = h->allreduce_device(dev, len)) return rc;
+      HIPCHK(hipMemcpyAsync(tiles.data(), dev, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, h->st));
+      HIPCHK(hipStreamSynchronize(h->st));
+    } else if (int rc = h->allreduce_host(tiles.data(), len)) {
+      return rc;
+    }
+  }
+  std::vector<double> G((size_t)(p * p));
+  int m = 0;
+  for (int j = 1; j < K; ++j)
+    for (int k = j; k < K; ++k, ++m) {
+      const double* tm = tiles.data() + (int64_t)m * T * BG_TILE;
+      for (int64_t a = 0; a < p; ++a)
+        for (int64_t b = 0; b <= a; ++b) {
+          const int64_t bi = a >> 4, bj = b >> 4;
+          G[(size_t)(a + b * p)] = tm[(bi * (bi + 1) / 2 + bj) * BG_TILE + (a & 15) * 16 + (b & 15)];
+        }
+      mn_place_block(G.data(), p, q, j, k, 1.0, H);  // (the kernel carries the Hessian's signs)
+    }
+  return SGLM_OK;
+}
+
+// The q x q class-major matrix of the block pairs at the P of the last full evaluation (collective): the Hessian
+// H (BG_HESS) or the robust covariance's meat sum_i (r_i r_i') (x) x_i x_i' (BG_MEAT).  p <= 64: the block kernel;
+// and blockgram_preferred (the measured rule; sglm_set_multinom_route overrides it), else a weight kernel and a Gram
+// pass per block pair.
+int mn_blocks(sglm_engine* h, int K, int mode, double* H) {
+  const int64_t p = h->ncols(), q = (int64_t)(K - 1) * p;
+  const bool block = h->mn_route == 2 || (h->mn_route == 0 && blockgram_preferred((int)((p + 15) / 16), K));
+  if (p <= 64 && block) return mn_blocks_one_read(h, K, mode, H);
   std::vector<double> packed((size_t)packed_len(p)), zero((size_t)p, 0.0), M((size_t)(p * p)), x((size_t)p);
   double wms = 0.0, gms = 0.0;
   for (int j = 1; j < K; ++j)
     for (int k = j; k < K; ++k) {
       for (sglm_engine* s : h->shards())
-        if (int rc = s->multinom_weight_local(K, j, k)) return rc;
+        if (int rc = s->multinom_weight_local(K, j, k, mode == BG_MEAT)) return rc;
       {
         MeatPassScope scope(h);
         if (int rc = h->pass(MODE_IRLS, zero.data(), 0.0, 0.0, FAM_GAUSSIAN, LNK_IDENTITY, packed.data())) return rc;
@@ -195,18 +301,16 @@ int mn_hessian(sglm_engine* h, int K, double* H) {
       wms += w;
       gms += slowest_shard(h, [](const sglm_engine* s) { return s->last_pass_ms; });
       unpack_gram(packed.data(), p, M.data(), x.data());
-      const double sign = j == k ? 1.0 : -1.0;
-      for (int64_t b = 0; b < p; ++b)
-        for (int64_t a = 0; a < p; ++a) {
-          const double v = sign * M[(size_t)(a + b * p)];
-          H[((j - 1) * p + a) + ((k - 1) * p + b) * q] = v;
-          H[((k - 1) * p + b) + ((j - 1) * p + a) * q] = v;
-        }
+      // the Hessian's off-diagonal weights are pw pi_j pi_k >= 0: negated here; the meat's are signed already
+      mn_place_block(M.data(), p, q, j, k, mode == BG_HESS && j != k ? -1.0 : 1.0, H);
     }
   h->mn_ms[2] = wms;
   h->mn_ms[3] = gms;
   return SGLM_OK;
 }
+
+int mn_hessian(sglm_engine* h, int K, double* H) { return mn_blocks(h, K, BG_HESS, H); }
+int mn_meat(sglm_engine* h, int K, double* M) { return mn_blocks(h, K, BG_MEAT, M); }
 
 const char* MN_SINGULAR = "breeze.linalg.MatrixSingularException: the multinomial Hessian is singular";
 
@@ -344,6 +448,47 @@ int sglm_fit_multinom(sglm_engine* h, const sglm_multinom_opts* opts, const doub
     info->score_inf = si;
     for (int k = 0; k < MN_MAX_K; ++k) info->class_weight[k] = k < K ? sc[MN_COUNT + k] : 0.0;
   }
+  return SGLM_OK;
+}
+
+int sglm_vcov_multinom_robust(sglm_engine* h, int n_classes, const double* B, int hc_type, double* cov, double* meat) {
+  if (int rc = mn_check_k(n_classes)) return rc;
+  if (!B || !cov) {
+    set_error("requirement failed: B, cov");
+    return SGLM_EINVAL;
+  }
+  if (hc_type != SGLM_HC0 && hc_type != SGLM_HC1) {
+    set_error("requirement failed: hc_type SGLM_HC0 or SGLM_HC1 for a multinomial model (HC2 / HC3 need per-row "
+              "leverage blocks)");
+    return SGLM_EINVAL;
+  }
+  if (int rc = mn_check_handle(h, n_classes)) return rc;
+  const int K = n_classes;
+  const int64_t q = (int64_t)(K - 1) * h->ncols();
+  std::vector<double> out, H((size_t)(q * q)), C((size_t)(q * q)), M((size_t)(q * q)), delta((size_t)q);
+  if (int rc = mn_eval(h, K, B, MN_FULL, out, nullptr)) return rc;
+  if (int rc = mn_hessian(h, K, H.data())) return rc;
+  if (int rc = mn_solve(h, q, H.data(), out.data(), delta.data(), C.data())) return rc;
+  if (int rc = mn_meat(h, K, M.data())) return rc;
+  double nrows = (double)(h->group() ? h->g_n : h->n);  // HC1: every row of every shard, weight 0 included
+  if (hc_type == SGLM_HC1 && !h->group())
+    if (int rc = h->allreduce_small(&nrows, 1)) return rc;
+  const double f = hc_type == SGLM_HC1 ? nrows / (nrows - (double)q) : 1.0;
+  if (!sandwich_product(C, M, q, f, cov)) {
+    set_error("requirement failed: the multinomial sandwich covariance is not finite at B");
+    return SGLM_EINVAL;
+  }
+  if (meat) std::memcpy(meat, M.data(), sizeof(double) * M.size());
+  return SGLM_OK;
+}
+
+int sglm_set_multinom_route(sglm_engine* h, int route) {
+  if (int rc = check_handle(h)) return rc;
+  if (route < 0 || route > 2) {
+    set_error("requirement failed: route 0 (the measured rule), 1 (a Gram pass per block pair) or 2 (the block Gram kernel)");
+    return SGLM_EINVAL;
+  }
+  h->mn_route = route;
   return SGLM_OK;
 }
 

@@ -32,7 +32,9 @@
 // (launch_part_sum) workgroups in a fixed order.  No floating-point atomics: two calls are bitwise equal.
 //
 // multinom_weight_kernel writes the Gram pass's row weights of one block pair of the Hessian from P:
-// pw pi_j sum_{l != j} pi_l (no 1 - pi_j: nothing cancels as pi_j -> 1) or pw pi_j pi_k (the host negates).
+// pw pi_j sum_{l != j} pi_l (no 1 - pi_j: nothing cancels as pi_j -> 1) or pw pi_j pi_k (the host negates); with
+// y (the robust covariance's meat past the block Gram's widths) the signed r_j r_k, r_j = pw (1[y = j] - pi_j) and
+// r_y = pw sum_{l != y} pi_l.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -309,7 +311,8 @@ __global__ void __launch_bounds__(MN_NT, MN_WG_PER_CU) multinom_xtr_kernel(Multi
 }
 
 __global__ void __launch_bounds__(256) multinom_weight_kernel(const double* __restrict__ P,
-                                                              const double* __restrict__ prior, int64_t n, int64_t ld,
+                                                              const double* __restrict__ prior,
+                                                              const double* __restrict__ y, int64_t n, int64_t ld,
                                                               int K, int j, int k, double* __restrict__ out) {
   const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (r >= ld) return;
@@ -317,6 +320,20 @@ __global__ void __launch_bounds__(256) multinom_weight_kernel(const double* __re
   if (r < n) {
     const double pw = prior ? prior[r] : 1.0;
     double f;
+    if (y) {  // the meat's weights; a row of weight 0: y is not looked at
+      if (pw > 0.0) {
+        const double yv = y[r];
+        const int yc = yv >= 0.0 && yv < (double)K ? (int)yv : 0;
+        double sy = 0.0;
+        for (int l = 0; l < K; ++l)
+          if (l != yc) sy += P[(int64_t)l * ld + r];
+        const double rj = pw * (j == yc ? sy : -P[(int64_t)j * ld + r]);
+        const double rk = pw * (k == yc ? sy : -P[(int64_t)k * ld + r]);
+        w = rj * rk;
+      }
+      out[r] = w;
+      return;
+    }
     if (j == k) {
       f = 0.0;  // 1 - pi_j as the sum of the other classes' probabilities, baseline included
       for (int l = 0; l < K; ++l)
@@ -384,11 +401,11 @@ hipError_t launch_multinom_rows(int mode, int P16, const MultinomArgs& a, int gr
   return hipGetLastError();
 }
 
-hipError_t launch_multinom_weight(const double* P, const double* prior, int64_t n, int64_t ld, int K, int j, int k,
-                                  double* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+hipError_t launch_multinom_weight(const double* P, const double* prior, const double* y, int64_t n, int64_t ld, int K,
+                                  int j, int k, double* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   if (ld <= 0) return hipSuccess;
   hipExtLaunchKernelGGL(multinom_weight_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, st, e0, e1, 0, P,
-                        prior, n, ld, K, j, k, out);
+                        prior, y, n, ld, K, j, k, out);
   return hipGetLastError();
 }
 

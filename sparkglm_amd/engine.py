@@ -779,8 +779,33 @@ class Engine:
                            info.null_deviance, info.loglik, info.aic, info.iter, info.halvings, bool(info.converged),
                            info.score_inf, np.array(info.class_weight[:K]))
 
+    def vcov_multinom_robust(self, n_classes, B, type="HC0"):
+        """(cov, meat) of sglm_vcov_multinom_robust at B: the sandwich C M C over the class-major parameter vector
+        ([q, q]; "HC1": times n / (n - q)), C = inv(H), and its meat M = sum_i (r_i r_i') (x) x_i x_i'.  "HC2" and
+        "HC3" are refused by the library."""
+        if type not in L.HC_TYPES:
+            raise L.IllegalArgumentException(f"requirement failed: type must be one of {sorted(L.HC_TYPES)}, "
+                                             f"got {type!r}")
+        K = int(n_classes)
+        b = self._multinom_B(B, K)
+        q = max(K - 1, 0) * self.p
+        cov, meat = np.zeros((q, q), order="F"), np.zeros((q, q), order="F")
+        L.check(self._lib.sglm_vcov_multinom_robust(self._h, K, L.ptr(b), L.HC_TYPES[type], L.ptr(cov), L.ptr(meat)),
+                "sglm_vcov_multinom_robust")
+        return cov, meat
+
+    def set_multinom_route(self, route="auto"):
+        """For the measuring tools and the tests: how the multinomial Hessian and meat are formed at p <= 64 --
+        "auto" (the default: the measured rule per (p, K)), "per_block" (one Gram pass per block pair) or "block"
+        (the block Gram kernel)."""
+        routes = {"auto": 0, "per_block": 1, "block": 2}
+        if route not in routes:
+            raise L.IllegalArgumentException(f"requirement failed: route must be one of {sorted(routes)}, got {route!r}")
+        L.check(self._lib.sglm_set_multinom_route(self._h, routes[route]), "sglm_set_multinom_route")
+
     def multinom_ms(self):
-        """Kernel times (rows, X'R, weights, Gram passes) of the last multinomial call (HIP events)."""
+        """Kernel times (rows, X'R, weights, Gram passes) of the last multinomial call (HIP events); on the block Gram
+        kernel's route the weights' slot is 0 and the Gram slot is that kernel's time."""
         t = [C.c_double() for _ in range(4)]
         L.check(self._lib.sglm_get_multinom_ms(self._h, *[C.byref(v) for v in t]), "sglm_get_multinom_ms")
         return tuple(v.value for v in t)

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib as L
 from .frame import Frame
-from .glm import _engine, _require
+from .glm import _coef_table, _engine, _require
 
 
 def code_levels(labels):
@@ -103,6 +103,48 @@ class Multinom:
         return MultinomModel(levels, list(x.columns), y.columns[0], f.coefs, f.stderr, z, pv, f.cov, f.deviance,
                              f.null_deviance, f.loglik, f.aic, f.iter, f.halvings, f.converged,
                              float(np.sum(f.class_weight)))
+
+    @staticmethod
+    def _load(obj: MultinomModel, y: Frame, x: Frame, prior: Optional[Frame], type: str, device: int):
+        """The estimation data resident on the engine, y coded by the model's levels: (engine, K)."""
+        if type not in ("HC0", "HC1"):
+            raise L.IllegalArgumentException(f'requirement failed: type must be one of ["HC0", "HC1"] for a multinomial '
+                                             f"model, got {type!r}")
+        _require(len(y.columns) == 1, "y has one column of class labels")
+        _require(y.count() == x.count(), "The two DataFrames must have the same number of rows")
+        _require(list(x.columns) == list(obj.xnames), "x has the model's predictors, in its order")
+        labels = np.asarray(y[y.columns[0]])
+        codes = np.searchsorted(obj.levels, labels)
+        _require(bool(np.all(np.asarray(obj.levels)[np.minimum(codes, len(obj.levels) - 1)] == labels)),
+                 "every label of y is one of the model's levels")
+        pw = None
+        if prior is not None:
+            _require(prior.count() == y.count(), "The two DataFrames must have the same number of rows")
+            pw = prior.to_vector()
+        eng = _engine(device)
+        eng.set_data(x.to_matrix(), codes.astype(np.float64).reshape(-1), prior=pw)
+        return eng, len(obj.levels)
+
+    @staticmethod
+    def vcov(obj: MultinomModel, y: Frame, x: Frame, prior: Optional[Frame] = None, type: str = "HC0",
+             device: int = 0) -> np.ndarray:
+        """Extension: the robust (sandwich) covariance of the fitted coefficients on the estimation data, [q, q]
+        over the class-major parameter vector (Stata's mlogit, vce(robust); statsmodels' cov_type="HC0";
+        sandwich::sandwich on nnet::multinom).  `type` "HC0" or "HC1" (times n / (n - q))."""
+        eng, K = Multinom._load(obj, y, x, prior, type, device)
+        return eng.vcov_multinom_robust(K, np.asarray(obj.coefs).reshape(-1), type=type)[0]
+
+    @staticmethod
+    def coeftest(obj: MultinomModel, y: Frame, x: Frame, prior: Optional[Frame] = None, type: str = "HC0",
+                 device: int = 0) -> Frame:
+        """Extension: lmtest::coeftest on the robust covariance -- a row per level and predictor: level, name,
+        estimate, robust standard error, z and its two-sided normal p-value."""
+        V = Multinom.vcov(obj, y, x, prior, type, device)
+        t = _coef_table([nm for _ in obj.levels[1:] for nm in obj.xnames], np.asarray(obj.coefs).reshape(-1), V,
+                        L.load().sglm_pval_normal)
+        cols = {"level": np.repeat(np.asarray(obj.levels[1:]), len(obj.xnames))}
+        cols.update({c: t[c] for c in t.columns})
+        return Frame(cols)
 
     @staticmethod
     def summary_string(obj: MultinomModel) -> str:

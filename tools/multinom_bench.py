@@ -9,7 +9,11 @@ to the engine by set_data_device: 100M x 32, 20M x 64, 20M x 128, 20M x 256 by d
 rounds, then REPS rounds of (one full evaluation with its Hessian, one deviance-only evaluation, one influence call
 -- gaussian / identity: y holds class codes), the medians (HIP events).  An iteration of the fit is one Hessian, one
 deviance-only trial and one full evaluation: iteration_ms is the sum of their kernel times, gram_share the Gram
-passes' part of it.  One JSON line per shape and K, appended to OUT (default profiles/multinom_bench.jsonl).
+passes' part of it.  At p <= 64 the Hessian is timed on the block Gram kernel (blockgram.hip: weight_ms is 0
+and gram_ms its time) whatever the engine's own rule would choose; the per-block route -- a weight kernel and a Gram pass per block pair, kept reachable by
+Engine.set_multinom_route -- is timed in the same rounds on the same shard: per_block_weight_ms, per_block_gram_ms,
+and block_over_per_block = gram_ms / (their sum), with the minimum and maximum of both.  One JSON line per shape and
+K, appended to OUT (default profiles/multinom_bench.jsonl).
 
     python tools/multinom_bench.py
 """
@@ -60,10 +64,19 @@ def run(eng, n, p, K, warm, reps, rate):
     load(eng, n, p, K)
     B = np.full((K - 1) * p, 0.01)
     beta = np.full(p, 0.01)
-    full, xtr, wgt, gram, dev, infl = [], [], [], [], [], []
+    full, xtr, wgt, gram, dev, infl, pbw, pbg = [], [], [], [], [], [], [], []
     for k in range(warm + reps):
+        if p <= 64:
+            eng.set_multinom_route("block")
         eng.multinom_pass(B, K)
         f = eng.multinom_ms()
+        if p <= 64:  # the per-block route of the same process and shard
+            eng.set_multinom_route("per_block")
+            eng.multinom_pass(B, K)
+            pb = eng.multinom_ms()
+            eng.set_multinom_route("auto")
+            if k >= warm:
+                pbw.append(pb[2]); pbg.append(pb[3])
         eng.multinom_pass(B, K, hessian=False)
         d = eng.multinom_ms()[0]
         eng.influence(beta, "gaussian", "identity")
@@ -76,7 +89,17 @@ def run(eng, n, p, K, warm, reps, rate):
     stream_ms = n * 8.0 * p / rate * 1e3
     rows_ms = med(full) + med(xtr)
     it = rows_ms + med(dev) + med(wgt) + med(gram)
+    extra = {}
+    if pbw:
+        per_block = [a + b for a, b in zip(pbw, pbg)]
+        extra = {"per_block_weight_ms": med(pbw), "per_block_gram_ms": med(pbg),
+                 "block_over_per_block": med(gram) / med(per_block), "reads_of_x": -(-(K * (K - 1) // 2) //
+                                                                                    {1: 64, 2: 60, 3: 28, 4: 16}[P16]),
+                 "gram_ms_min": float(min(gram)), "gram_ms_max": float(max(gram)),
+                 "per_block_ms_min": float(min(per_block)), "per_block_ms_max": float(max(per_block)),
+                 "gram_over_stream": med(gram) / stream_ms}
     return {
+        **extra,
         "n": n, "p": p, "K": K, "P16": P16, "reps": reps, "route": "fused" if fused else "rows + xtr",
         "rows_ms": med(full), "xtr_ms": med(xtr), "rows_dev_ms": med(dev), "weight_ms": med(wgt), "gram_ms": med(gram),
         "influence_ms": med(infl), "rows_over_influence": rows_ms / med(infl),
