@@ -77,7 +77,9 @@ extern "C" {
                               sglm_get_gee_ms, sglm_fit_glm_firth (with sglm_firth_opts / sglm_firth_info),
                               sglm_firth_pass, sglm_get_firth_ms, sglm_fit_multinom (with sglm_multinom_opts /
                               sglm_multinom_info), sglm_multinom_pass, sglm_get_multinom_ms,
-                              sglm_vcov_multinom_robust, sglm_set_multinom_route;
+                              sglm_vcov_multinom_robust, sglm_set_multinom_route, sglm_set_data_f32,
+                              sglm_store_f32, sglm_get_storage (SGLM_KERNEL_NARROW_F32, flag 4 of
+                              sglm_pass_kernel_for);
                               (new values only:) SGLM_SQRT and
                               the non-canonical (family, link) pairs of enum sglm_link's table,
                               SGLM_NEGBIN and its three pairs */
@@ -146,8 +148,9 @@ enum sglm_pass_kernel {
   SGLM_KERNEL_FUSED_SPLIT = 2, /* irls_pass_r_kernel<P16, fam, link> (K1r, split roles) */
   SGLM_KERNEL_NARROW = 3,      /* irls_narrow_kernel<P16, fam, link, irls, stats>: p <= 64 */
   SGLM_KERNEL_WIDE = 4,        /* wide_rows_kernel + wide_gram_kernel: p > 256 (resident X) */
-  SGLM_KERNEL_WIDE_PROC = 5    /* the same over procedural X (generated chunks or in-kernel) */
+  SGLM_KERNEL_WIDE_PROC = 5,   /* the same over procedural X (generated chunks or in-kernel) */
   /* 6 (SGLM_KERNEL_NARROW_SPLIT, ABI <= 7): retired with its kernel, never returned */
+  SGLM_KERNEL_NARROW_F32 = 7   /* irls_narrow_f32_kernel<P16, fam, link>: p <= 64 over an fp32-stored design */
 };
 
 /* Prediction scale (R's predict(type = "link" | "response")). */
@@ -275,7 +278,24 @@ void sglm_destroy(sglm_engine *h);
 /* Host arrays.  m (binomial trials), offset and prior (weights) may be NULL. */
 int sglm_set_data(sglm_engine *h, const double *X, int64_t n, int64_t p, int64_t ldx,
                   const double *y, const double *m, const double *offset, const double *prior);
-/* Same, from device memory already on this engine's device. */
+/* Host float array, column-major (ldx >= n), p <= 64; half the host->HBM bytes of sglm_set_data.
+ * y / m / offset / prior stay double.  The design is stored as fp32 (every pass widens it exactly, so a fit
+ * is the fp64 fit of the design rounded to float).  Single-device handles; see sglm_store_f32 for what an
+ * fp32-stored design supports. */
+int sglm_set_data_f32(sglm_engine *h, const float *X, int64_t n, int64_t p, int64_t ldx,
+                      const double *y, const double *m, const double *offset, const double *prior);
+/* Convert the resident fp64 design (sglm_set_data, sglm_set_rows once complete, sglm_synth) to fp32 storage,
+ * rounding to nearest even, and free the fp64 image (peak: 1.5 x the fp64 image).  p > 64, a procedural shard,
+ * SGLM_FORCE_WIDE or a group handle: SGLM_EINVAL, data unchanged.  Drops clusters / fe2 as every data
+ * replacement does.  On an fp32-stored design sglm_fit_glm / _start / _nb, sglm_nb_theta_terms, sglm_theta_ml,
+ * sglm_irls_pass / _step / _iterations, sglm_vcov, sglm_predict*, sglm_get_data (X widened) and sglm_get_stats
+ * work, with or without a communicator; sglm_fit_lm, sglm_set_rows, the per-row diagnostics, the sandwich and
+ * clustered covariances and the fixed-effects, GEE, Firth and multinomial fits return SGLM_EINVAL before any
+ * launch. */
+int sglm_store_f32(sglm_engine *h);
+/* 0 fp64, 1 fp32. */
+int sglm_get_storage(sglm_engine *h, int *storage);
+/* Same as sglm_set_data, from device memory already on this engine's device. */
 int sglm_set_data_device(sglm_engine *h, const double *dX, int64_t n, int64_t p, int64_t ldx,
                          const double *dy, const double *dm, const double *doffset,
                          const double *dprior);
@@ -780,7 +800,8 @@ int sglm_get_stats(sglm_engine *h, sglm_stats *out);
 /* The kernel an engine would run a pass of an n x p shard with (enum sglm_pass_kernel, -1 on bad
  * arguments) and its name into name[namelen] -- the engine's own dispatch rule, for callers and CPU
  * tests.  fused_split: SGLM_FUSED_SPLIT's meaning (1 default threshold, 0 never K1r, N from P16 = N);
- * flags: 1 procedural shard, 2 forced wide path (SGLM_FORCE_WIDE).  No device is touched. */
+ * flags: 1 procedural shard, 2 forced wide path (SGLM_FORCE_WIDE), 4 fp32 storage (p <= 64 on the narrow
+ * path: SGLM_KERNEL_NARROW_F32; otherwise an error).  No device is touched. */
 int sglm_pass_kernel_for(int64_t n, int64_t p, int fused_split, int flags, int family, int link, char *name,
                          int64_t namelen);
 int sglm_reset_stats(sglm_engine *h);

@@ -28,7 +28,7 @@ S_DEV, S_PEARSON, S_LL, S_BAD, S_AUX0, S_AUX1, S_AUX2, S_SUMW = range(8)
 # Symbols include/sglm.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "sglm_abi_version", "sglm_last_error", "sglm_device_count", "sglm_create", "sglm_destroy",
-    "sglm_set_data", "sglm_set_data_device", "sglm_synth", "sglm_synth_procedural", "sglm_get_data", "sglm_set_comm",
+    "sglm_set_data", "sglm_set_data_f32", "sglm_store_f32", "sglm_get_storage", "sglm_set_data_device", "sglm_synth", "sglm_synth_procedural", "sglm_get_data", "sglm_set_comm",
     "sglm_rccl_unique_id", "sglm_set_comm_rccl", "sglm_fit_glm", "sglm_fit_lm", "sglm_irls_pass", "sglm_irls_step",
     "sglm_irls_iterations", "sglm_predict", "sglm_get_stats", "sglm_reset_stats",
     "sglm_fit_glm_external", "sglm_fit_lm_external", "sglm_glm_create_obj", "sglm_glm_summary",
@@ -151,7 +151,7 @@ class Stats(C.Structure):
 
 COMM_PATHS = {0: "none", 1: "caller-host", 2: "caller-device", 3: "rccl", 4: "group-rccl", 5: "group-host"}
 SOLVE_PATHS = {-1: "none", 0: "host-cholesky", 1: "host-lu", 2: "device-cholesky", 3: "device-lu"}
-PASS_KERNELS = {0: "none", 1: "fused", 2: "fused-split", 3: "narrow", 4: "wide", 5: "wide-procedural"}
+PASS_KERNELS = {0: "none", 1: "fused", 2: "fused-split", 3: "narrow", 4: "wide", 5: "wide-procedural", 7: "narrow-f32"}
 
 
 class GlmDerived(C.Structure):
@@ -210,6 +210,9 @@ def load():
         "sglm_create_multi": ([C.POINTER(C.c_int), C.c_int, E], C.c_int),
         "sglm_destroy": ([h], None),
         "sglm_set_data": ([h, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp], C.c_int),
+        "sglm_set_data_f32": ([h, C.POINTER(C.c_float), C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp], C.c_int),
+        "sglm_store_f32": ([h], C.c_int),
+        "sglm_get_storage": ([h, C.POINTER(C.c_int)], C.c_int),
         "sglm_set_data_device": ([h, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p], C.c_int),
         "sglm_synth": ([h, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_uint64], C.c_int),
@@ -314,10 +317,10 @@ def load():
 
 
 def pass_kernel_for(n: int, p: int, family: str = "binomial", link: str = "logit", fused_split: int = 1,
-                    procedural: bool = False, force_wide: bool = False):
+                    procedural: bool = False, force_wide: bool = False, f32: bool = False):
     """(kind, name) of the kernel an engine runs an n x p pass with (sglm_pass_kernel_for; no GPU)."""
     buf = C.create_string_buffer(64)
-    flags = (1 if procedural else 0) | (2 if force_wide else 0)
+    flags = (1 if procedural else 0) | (2 if force_wide else 0) | (4 if f32 else 0)
     k = load().sglm_pass_kernel_for(int(n), int(p), int(fused_split), flags, FAMILIES[family], LINKS[link], buf, 64)
     if k < 0:
         raise IllegalArgumentException(last_error())

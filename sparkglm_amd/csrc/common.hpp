@@ -126,7 +126,8 @@ struct PassArgs {
   int no_gram;          // deviance-only pass (glm_drive's speculative last pass): row stage, no Gram
   int fused_split;      // split-role kernel K1r (irls_pass_r_kernel) from P16 >= threshold: 1 default, 0 never, N: P16 >= N
   int lm_extras;        // narrow LM Gram pass of the one-round-trip LM.fit: X'1 after the scalars, y'y in S_PEARSON
-  double theta;         // FAM_NEGBIN: the dispersion parameter (sglm_set_theta); last, so every other field keeps its offset
+  double theta;         // FAM_NEGBIN: the dispersion parameter (sglm_set_theta); after the older fields, which keep their offsets
+  const float* X32;     // fp32-stored design (narrow_f32.hip): then X is null and ld counts floats; null otherwise
 };
 
 // ---- wide-design path (p > 16*MAX_P16): row kernel + panel-pair Gram kernel ----

@@ -214,7 +214,7 @@ int sglm::bread(sglm_engine* h, double* packed, const char* singular, double* C,
 int sglm::require_fused_or_narrow(const sglm_engine* h, const char* what) {
   bool refuse = false;
   for (const sglm_engine* s : h->shards()) refuse = refuse || s->procx.on || s->wide;
-  if (!refuse) return SGLM_OK;
+  if (!refuse) return refuse_f32(h, "this entry point (diagnostics, robust covariances, step and multinomial fits)");
   set_error(std::string("requirement failed: ") + what + " a resident design with p <= " +
             std::to_string(16 * MAX_P16) + " columns on the fused / narrow path (procedural shards, wider "
             "designs and SGLM_FORCE_WIDE are not supported)");

@@ -30,7 +30,7 @@ using namespace sglm;
 // ensure_workspace / launch_pass / launch_narrow / the wide path, in one place (the engine labels
 // its passes with it; sglm_pass_kernel_for exposes it for a CPU test of the mapping).
 static int pass_kernel_choice(int64_t n_pad, int P16, bool narrow, bool wide, bool proc, int fused_split, int family,
-                              int link, char* name, size_t len) {
+                              int link, char* name, size_t len, bool f32 = false) {
   static const char* fam[] = {"binomial", "gaussian", "poisson", "gamma", "negbin"};
   static const char* lnk[] = {"logit", "probit", "cloglog", "identity", "log", "inverse", "sqrt"};
   const char* f = (family >= 0 && family < 5) ? fam[family] : "?";
@@ -42,6 +42,9 @@ static int pass_kernel_choice(int64_t n_pad, int P16, bool narrow, bool wide, bo
   if (wide) {
     k = proc ? SGLM_KERNEL_WIDE_PROC : SGLM_KERNEL_WIDE;
     std::snprintf(name, len, "wide_gram_kernel<%s>", proc ? "procedural" : "resident");
+  } else if (narrow && f32) {
+    k = SGLM_KERNEL_NARROW_F32;
+    std::snprintf(name, len, "irls_narrow_f32_kernel<%d,%s,%s>", P16, f, l);
   } else if (narrow) {
     k = SGLM_KERNEL_NARROW;
     std::snprintf(name, len, "irls_narrow_kernel<%d,%s,%s>", P16, f, l);
@@ -95,6 +98,9 @@ void sglm_engine::dev_free(std::initializer_list<double**> ptrs) {
 
 void sglm_engine::free_data() {
   dev_free({&dX, &dy, &dm, &doff, &dprior, &deta, &dw, &dwz});
+  if (dX32) (void)hipFree(dX32);
+  dX32 = nullptr;
+  ld32 = 0;
   n = p = n_pad = nblocks = 0;
   lm_last_pass_ms = -1.0;  // a new shard: the next device LM fit is timed
   rows_loaded = 0;
@@ -188,7 +194,7 @@ int sglm_engine::ensure_workspace() {
     P16 = narrow_variant((int)p);
     stride = narrow_stride(P16);
     const int64_t want_grid = (int64_t)ncu * narrow_wg_per_cu();
-    const int64_t per_wg = narrow_rows_per_wg(P16);
+    const int64_t per_wg = dX32 ? narrow_f32_rows_per_wg(P16) : narrow_rows_per_wg(P16);
     const int64_t need = (nblocks * RB + per_wg - 1) / per_wg;
     grid = (int)std::max<int64_t>(1, std::min(need, want_grid));
   } else {
@@ -205,7 +211,43 @@ int sglm_engine::ensure_workspace() {
   return ensure_small(64);
 }
 
-int sglm_engine::alloc_data(int64_t n_, int64_t p_, bool has_m, bool has_off, bool has_prior, bool proc) {
+int sglm_engine::alloc_f32() {
+  ld32 = (n_pad + 63) / 64 * 64;  // whole 64-row blocks of the p <= 32 variants
+  const size_t bytes = sizeof(float) * (size_t)ld32 * (size_t)((p + 7) / 8 * 8);
+  const hipError_t e = hipMalloc(&dX32, bytes);
+  if (e != hipSuccess) {
+    dX32 = nullptr;
+    ld32 = 0;
+    (void)hipGetLastError();
+    set_error(hip_msg(e, "hipMalloc(X, fp32 storage)"));
+    return SGLM_ENOMEM;
+  }
+  HIPCHK(hipMemsetAsync(dX32, 0, bytes, st));
+  return SGLM_OK;
+}
+
+// The fp64 image rounded to nearest even into a new fp32 image, then freed (peak: 1.5 x the fp64 image).
+int sglm_engine::store_f32() {
+  HIPCHK(hipSetDevice(device));
+  if (int rc = alloc_f32()) return rc;
+  hipError_t e = launch_round_f32(dX, n_pad, dX32, ld32, n, (int)p, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {  // data unchanged: the handle keeps its fp64 image and reports f64
+    (void)hipFree(dX32);
+    dX32 = nullptr;
+    ld32 = 0;
+    set_error(hip_msg(e, "sglm_store_f32 (rounding the design)"));
+    return SGLM_EHIP;
+  }
+  dev_free({&dX});
+  consts_family = -1;
+  free_clusters(false);  // as every data replacement
+  free_multinom();
+  free_influence();
+  return ensure_workspace();
+}
+
+int sglm_engine::alloc_data(int64_t n_, int64_t p_, bool has_m, bool has_off, bool has_prior, bool proc, bool f32) {
   HIPCHK(hipSetDevice(device));
   free_data();
   if (n_ < 0 || p_ <= 0) {
@@ -224,7 +266,12 @@ int sglm_engine::alloc_data(int64_t n_, int64_t p_, bool has_m, bool has_off, bo
   const size_t vb = sizeof(double) * (size_t)n_pad;
   const size_t ncols = (size_t)((p + 7) / 8 * 8);  // whole column octets for the LDS-DMA staging
   hipError_t e = hipSuccess;
-  if (!proc) {
+  if (f32) {
+    if (int rc = alloc_f32()) {
+      free_data();
+      return rc;
+    }
+  } else if (!proc) {
     e = hipMalloc(&dX, vb * ncols);
     if (e != hipSuccess) {
       set_error(hip_msg(e, "hipMalloc(X)"));
@@ -246,6 +293,16 @@ int sglm_engine::alloc_data(int64_t n_, int64_t p_, bool has_m, bool has_off, bo
     HIPCHK(hipMemsetAsync(*pr.first, 0, vb, st));
   }
   return ensure_workspace();
+}
+
+int sglm::refuse_f32(const sglm_engine* h, const char* what) {
+  for (const sglm_engine* s : h->shards())
+    if (s->dX32) {
+      set_error(std::string("requirement failed: ") + what + " is not available on a design stored as fp32 (storage "
+                "f32: sglm_set_data_f32 / sglm_store_f32); it needs the fp64 image of sglm_set_data");
+      return SGLM_EINVAL;
+    }
+  return SGLM_OK;
 }
 
 // ---- Backend ----
@@ -371,7 +428,8 @@ int sglm_engine::enqueue_pass(int mode, const double* beta, double mu0, double y
   }
   PassArgs a{};
   a.X = dX;
-  a.ld = n_pad;
+  a.X32 = dX32;
+  a.ld = dX32 ? ld32 : n_pad;
   a.p = (int)p;
   a.nq = (int)((p + 3) / 4);
   a.y = dy;
@@ -421,7 +479,8 @@ int sglm_engine::enqueue_pass(int mode, const double* beta, double mu0, double y
   // a tenth of an LM.fit on configs[0]
   hipEvent_t e0 = timed ? ev0 : nullptr, e1 = timed ? ev1 : nullptr, e2 = timed ? ev2 : nullptr;
   if (nblocks > 0) {
-    if (narrow) HIPCHK(launch_narrow(P16, a, grid, st, e0, e1));
+    if (narrow && dX32) HIPCHK(launch_narrow_f32(P16, a, grid, st, e0, e1));
+    else if (narrow) HIPCHK(launch_narrow(P16, a, grid, st, e0, e1));
     else HIPCHK(launch_pass(P16, a, grid, st, e0, e1));
   } else {
     HIPCHK(hipEventRecord(ev0, st));
@@ -438,7 +497,7 @@ int sglm_engine::enqueue_pass(int mode, const double* beta, double mu0, double y
 // row limit -- so a roofline line is labelled by what ran, not by a re-derived threshold.
 void sglm_engine::note_kernel(int family, int link) {
   last_kernel = pass_kernel_choice(n_pad, P16, narrow, wide, procx.on != 0, fused_split, family, link,
-                                   last_kernel_name, sizeof last_kernel_name);
+                                   last_kernel_name, sizeof last_kernel_name, dX32 != nullptr);
 }
 
 // ---- multi-device handle: every shard's pass enqueued, then one reduction ----
@@ -843,6 +902,7 @@ int sglm_fit_lm(sglm_engine* h, sglm_prelm* out) {
     return SGLM_EINVAL;
   }
   if (int rc = check_ready(h)) return rc;
+  if (int rc = refuse_f32(h, "sglm_fit_lm")) return rc;
   return lm_drive(*h, out);
 }
 
@@ -896,9 +956,14 @@ int sglm_pass_kernel_for(int64_t n, int64_t p, int fused_split, int flags, int f
   }
   const int64_t n_pad = (n + RB - 1) / RB * RB;  // alloc_data's leading dimension
   const bool proc = (flags & 1) != 0, wide = proc || (flags & 2) || p > 16 * MAX_P16, narrow = !wide && p <= 64;
+  const bool f32 = (flags & 4) != 0;
+  if (f32 && !narrow) {
+    set_error("requirement failed: fp32 storage holds resident designs of p <= 64 columns on the narrow path");
+    return -1;
+  }
   const int P16 = wide ? 0 : narrow ? narrow_variant((int)p) : pass_variant((int)p, fused_split, n_pad);
   char buf[64];
-  const int k = pass_kernel_choice(n_pad, P16, narrow, wide, proc, fused_split, family, link, buf, sizeof buf);
+  const int k = pass_kernel_choice(n_pad, P16, narrow, wide, proc, fused_split, family, link, buf, sizeof buf, f32);
   if (name && namelen > 0) std::snprintf(name, (size_t)namelen, "%s", buf);
   return k;
 }

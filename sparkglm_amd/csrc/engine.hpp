@@ -144,6 +144,10 @@ struct sglm_engine : public sglm::Backend {
   // ---- resident shard ----
   int64_t n = 0, p = 0, n_pad = 0, nblocks = 0;
   double *dX = nullptr, *dy = nullptr, *dm = nullptr, *doff = nullptr, *dprior = nullptr, *deta = nullptr;
+  // fp32 storage (sglm_set_data_f32 / sglm_store_f32; narrow_f32.hip): the design as floats, column-major with
+  // leading dimension ld32 (n_pad rounded up to 64), whole column octets, zero past n and p; dX is then null
+  float* dX32 = nullptr;
+  int64_t ld32 = 0;
   // procedural shard (sglm_synth_procedural): X regenerated in the wide kernels, not stored
   sglm::ProcX procx{};
 
@@ -376,7 +380,10 @@ struct sglm_engine : public sglm::Backend {
   ~sglm_engine() override;
   void free_data();
   void release();
-  int alloc_data(int64_t n_, int64_t p_, bool has_m, bool has_off, bool has_prior, bool proc = false);
+  // f32: the design's fp32 image instead of the fp64 one (p <= 64, never wide)
+  int alloc_data(int64_t n_, int64_t p_, bool has_m, bool has_off, bool has_prior, bool proc = false, bool f32 = false);
+  int alloc_f32();  // dX32 for the shard's n_pad and p, zeroed
+  int store_f32();  // the resident fp64 image rounded into dX32, dX freed
   int ensure_workspace();
   int ensure_red_len(int64_t len);  // dred / hred / dbeta / hbeta hold at least len doubles
   int ensure_small(int64_t count);
@@ -429,7 +436,8 @@ struct sglm_engine : public sglm::Backend {
 
   // ---- ingest.cpp: host rows in, scores of new rows out ----
   int ensure_staging();
-  int h2d_block(double* dst, int64_t dld, const double* src, int64_t sld, int64_t rows, int64_t cols);
+  template <class T>
+  int h2d_block(T* dst, int64_t dld, const T* src, int64_t sld, int64_t rows, int64_t cols);
   int set_rows(int64_t row0, int64_t nr, const double* X, int64_t ldx, const double* yv, const double* mv,
                const double* ov, const double* pv);
   int check_loaded() const;
@@ -649,6 +657,9 @@ struct MeatPassScope {
 };
 // cov = f (C M C + (C M C)') / 2, exactly symmetric (col-major p x p, on the host); false: M or cov is not finite
 bool sandwich_product(const std::vector<double>& C, const std::vector<double>& M, int64_t p, double f, double* cov);
+
+// SGLM_EINVAL, before any launch, on a handle whose design is stored as fp32: `what` names the entry point
+int refuse_f32(const sglm_engine* h, const char* what);
 
 // The handle holds a complete design: every reserved row written (or generated).
 inline int check_ready(sglm_engine* h) {

@@ -11,17 +11,18 @@ using namespace sglm;
 
 // Copy a column-major host block (rows x cols, leading dimension sld) into a packed buffer,
 // on several threads for large blocks (the pageable -> pinned leg of the ingest path).
-static void pack_cols(double* dst, const double* src, int64_t sld, int64_t rows, int64_t cols) {
+template <class T>
+static void pack_cols(T* dst, const T* src, int64_t sld, int64_t rows, int64_t cols) {
   const int64_t total = rows * cols;
   const int hw = (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
-  const int nt = total >= ((int64_t)2 << 20) ? hw : 1;  // >= 16 MiB: split the copy
+  const int nt = total * (int64_t)sizeof(T) >= ((int64_t)16 << 20) ? hw : 1;  // >= 16 MiB: split the copy
   auto part = [&](int t) {
     if (cols >= nt) {
-      for (int64_t c = t; c < cols; c += nt) std::memcpy(dst + c * rows, src + c * sld, sizeof(double) * rows);
+      for (int64_t c = t; c < cols; c += nt) std::memcpy(dst + c * rows, src + c * sld, sizeof(T) * rows);
     } else {
       const int64_t r0 = rows * t / nt, r1 = rows * (t + 1) / nt;
       for (int64_t c = 0; c < cols; ++c)
-        std::memcpy(dst + c * rows + r0, src + c * sld + r0, sizeof(double) * (size_t)(r1 - r0));
+        std::memcpy(dst + c * rows + r0, src + c * sld + r0, sizeof(T) * (size_t)(r1 - r0));
     }
   };
   if (nt == 1) {
@@ -47,23 +48,26 @@ int sglm_engine::ensure_staging() {
 
 // Column-major host block (rows x cols, leading dimension sld) -> device (leading dimension
 // dld) through the two pinned buffers: the CPU packs one while the DMA engine drains the
-// other.  Pageable memory is never handed to the DMA engine directly.
-int sglm_engine::h2d_block(double* dst, int64_t dld, const double* src, int64_t sld, int64_t rows, int64_t cols) {
+// other.  Pageable memory is never handed to the DMA engine directly.  T: double, or float (an fp32 design:
+// the staging buffers then hold twice the elements, half the bytes go over the link).
+template <class T>
+int sglm_engine::h2d_block(T* dst, int64_t dld, const T* src, int64_t sld, int64_t rows, int64_t cols) {
   if (rows <= 0 || cols <= 0) return SGLM_OK;
   int rc = ensure_staging();
   if (rc) return rc;
-  const int64_t rchunk = std::min<int64_t>(rows, STAGE_DOUBLES);
+  constexpr int64_t STAGE = STAGE_DOUBLES * (int64_t)(sizeof(double) / sizeof(T));
+  const int64_t rchunk = std::min<int64_t>(rows, STAGE);
   for (int64_t r0 = 0; r0 < rows; r0 += rchunk) {
     const int64_t rr = std::min(rchunk, rows - r0);
-    const int64_t cchunk = std::max<int64_t>(1, STAGE_DOUBLES / rr);
+    const int64_t cchunk = std::max<int64_t>(1, STAGE / rr);
     for (int64_t c0 = 0; c0 < cols; c0 += cchunk) {
       const int64_t cc = std::min(cchunk, cols - c0);
       const int k = stage_k;
       stage_k ^= 1;
       HIPCHK(hipEventSynchronize(evstage[k]));  // the copy that last read this buffer is done
-      pack_cols(hstage[k], src + r0 + c0 * sld, sld, rr, cc);
-      HIPCHK(hipMemcpy2DAsync(dst + r0 + c0 * dld, sizeof(double) * (size_t)dld, hstage[k], sizeof(double) * rr,
-                              sizeof(double) * rr, (size_t)cc, hipMemcpyHostToDevice, st));
+      pack_cols((T*)hstage[k], src + r0 + c0 * sld, sld, rr, cc);
+      HIPCHK(hipMemcpy2DAsync(dst + r0 + c0 * dld, sizeof(T) * (size_t)dld, hstage[k], sizeof(T) * rr,
+                              sizeof(T) * rr, (size_t)cc, hipMemcpyHostToDevice, st));
       HIPCHK(hipEventRecord(evstage[k], st));
     }
   }
@@ -78,6 +82,7 @@ int sglm_engine::set_rows(int64_t row0, int64_t nr, const double* X, int64_t ldx
     set_error("requirement failed: sglm_reserve the shard before sglm_set_rows");
     return SGLM_EINVAL;
   }
+  if (int rc = refuse_f32(this, "sglm_set_rows")) return rc;
   if (row0 < 0 || nr < 0 || row0 + nr > n || (nr > 0 && (!X || !yv || ldx < nr))) {
     set_error("requirement failed: 0 <= row0, row0 + nrows <= reserved rows, X and y non-null, ldx >= nrows");
     return SGLM_EINVAL;
@@ -273,7 +278,17 @@ static int get_data_impl(sglm_engine* h, double* X, int64_t ldx, double* y, doub
   }
   HIPCHK(hipSetDevice(h->device));
   const size_t vb = sizeof(double) * (size_t)h->n;
-  if (X)
+  if (X && h->dX32) {  // widened (exact) through a bounded scratch (at most 128 MiB), a row chunk at a time
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(h->n, ((int64_t)1 << 24) / h->p));
+    if (int rc = sglm_engine::grow(h->dxs, h->xs_cap, chunk * h->p, "hipMalloc(widening scratch)")) return rc;
+    for (int64_t r0 = 0; r0 < h->n; r0 += chunk) {
+      const int64_t nr = std::min(chunk, h->n - r0);
+      HIPCHK(launch_widen_f32(h->dX32 + r0, h->ld32, h->dxs, nr, nr, (int)h->p, h->st));
+      HIPCHK(hipMemcpy2DAsync(X + r0, sizeof(double) * (size_t)ldx, h->dxs, sizeof(double) * (size_t)nr,
+                              sizeof(double) * (size_t)nr, (size_t)h->p, hipMemcpyDeviceToHost, h->st));
+      HIPCHK(hipStreamSynchronize(h->st));  // the scratch is reused by the next chunk
+    }
+  } else if (X)
     HIPCHK(hipMemcpy2DAsync(X, sizeof(double) * (size_t)ldx, h->dX, sizeof(double) * h->n_pad, vb, (size_t)h->p,
                             hipMemcpyDeviceToHost, h->st));
   if (y) HIPCHK(hipMemcpyAsync(y, h->dy, vb, hipMemcpyDeviceToHost, h->st));
@@ -297,8 +312,11 @@ static int predict_resident(sglm_engine* h, const double* beta, int add_offset, 
   HIPCHK(hipSetDevice(h->device));
   std::memcpy(h->hbeta, beta, sizeof(double) * h->p);
   HIPCHK(hipMemcpyAsync(h->dbeta, h->hbeta, sizeof(double) * h->p, hipMemcpyHostToDevice, h->st));
-  HIPCHK(launch_predict(h->dX, h->n_pad, (int)h->p, h->n, h->dbeta, add_offset ? h->doff : nullptr, h->deta, h->st,
-                        h->procx));
+  if (h->dX32)
+    HIPCHK(launch_predict(h->dX32, h->ld32, (int)h->p, h->n, h->dbeta, add_offset ? h->doff : nullptr, h->deta, h->st));
+  else
+    HIPCHK(launch_predict(h->dX, h->n_pad, (int)h->p, h->n, h->dbeta, add_offset ? h->doff : nullptr, h->deta, h->st,
+                          h->procx));
   if (type == SGLM_PREDICT_RESPONSE) HIPCHK(launch_unlink(h->deta, h->dm, h->n, family, link, h->st));
   HIPCHK(hipMemcpyAsync(out, h->deta, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->st));
   HIPCHK(hipStreamSynchronize(h->st));
@@ -328,6 +346,64 @@ int sglm_set_data(sglm_engine* h, const double* X, int64_t n, int64_t p, int64_t
   int rc = reserve_impl(h, n, p, m != nullptr, offset != nullptr, prior != nullptr);
   if (rc) return rc;
   return set_rows_impl(h, 0, n, X, ldx, y, m, offset, prior);
+}
+
+// What fp32 storage holds: a resident design of p <= 64 columns on a single-device handle's narrow path.
+static int check_f32_shape(sglm_engine* h, int64_t p, const char* what) {
+  if (h->group() || p > 64 || h->force_wide) {
+    set_error(std::string("requirement failed: ") + what + ": fp32 storage (f32) holds p <= 64 columns on a "
+              "single-device handle (no multi-device handle, no SGLM_FORCE_WIDE)");
+    return SGLM_EINVAL;
+  }
+  return SGLM_OK;
+}
+
+int sglm_set_data_f32(sglm_engine* h, const float* X, int64_t n, int64_t p, int64_t ldx, const double* y,
+                      const double* m, const double* offset, const double* prior) {
+  if (int rc = check_handle(h)) return rc;
+  if (!X || !y || ldx < n || n <= 0 || p <= 0) {
+    set_error("requirement failed: X, y non-null, n >= 1, p >= 1, ldx >= n");
+    return SGLM_EINVAL;
+  }
+  if (int rc = check_f32_shape(h, p, "sglm_set_data_f32")) return rc;
+  h->consts_family = -1;
+  int rc = h->alloc_data(n, p, m != nullptr, offset != nullptr, prior != nullptr, false, true);
+  if (rc) return rc;
+  const double t0 = now_ms();
+  rc = h->h2d_block(h->dX32, h->ld32, X, ldx, n, p);
+  for (auto pr : {std::make_pair(h->dy, y), std::make_pair(h->dm, m), std::make_pair(h->doff, offset),
+                  std::make_pair(h->dprior, prior)})
+    if (!rc && pr.second) rc = h->h2d_block(pr.first, h->n_pad, pr.second, n, n, 1);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->st));
+  h->load_ms += now_ms() - t0;
+  const int nvec = 1 + (m != nullptr) + (offset != nullptr) + (prior != nullptr);
+  h->load_bytes += (int64_t)sizeof(float) * n * p + (int64_t)sizeof(double) * n * nvec;
+  h->rows_loaded = n;
+  h->written.assign(1, std::make_pair((int64_t)0, n));
+  return SGLM_OK;
+}
+
+int sglm_store_f32(sglm_engine* h) {
+  if (int rc = check_handle(h)) return rc;
+  if (int rc = check_f32_shape(h, h->p, "sglm_store_f32")) return rc;
+  if (h->procx.on) {
+    set_error("requirement failed: sglm_store_f32: a procedural shard stores no X to convert (storage stays f64)");
+    return SGLM_EINVAL;
+  }
+  if (int rc = h->check_loaded()) return rc;
+  if (h->dX32) return SGLM_OK;
+  return h->store_f32();
+}
+
+int sglm_get_storage(sglm_engine* h, int* storage) {
+  if (int rc = check_handle(h)) return rc;
+  if (!storage) {
+    set_error("requirement failed: storage");
+    return SGLM_EINVAL;
+  }
+  *storage = h->dX32 ? 1 : 0;
+  return SGLM_OK;
 }
 
 int sglm_set_data_device(sglm_engine* h, const double* dX, int64_t n, int64_t p, int64_t ldx, const double* dy,

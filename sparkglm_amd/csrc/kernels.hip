@@ -115,7 +115,8 @@ __global__ void __launch_bounds__(256) reduce_partials_kernel(const double* __re
 // ---------------------------------------------------------------------------------
 // eta = X beta (+ offset): LM.predict (LM.scala:39-61) / etaCreate.
 // ---------------------------------------------------------------------------------
-__global__ void predict_kernel(const double* __restrict__ X, int64_t ld, int p, int64_t n,
+template <class TX>
+__global__ void predict_kernel(const TX* __restrict__ X, int64_t ld, int p, int64_t n,
                                const double* __restrict__ beta, const double* __restrict__ off,
                                double* __restrict__ out, ProcX g) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -123,7 +124,7 @@ __global__ void predict_kernel(const double* __restrict__ X, int64_t ld, int p, 
     if (g.on)
       for (int j = 0; j < p; ++j) s += proc_x(g, i, j) * beta[j];
     else
-      for (int j = 0; j < p; ++j) s += X[(int64_t)j * ld + i] * beta[j];
+      for (int j = 0; j < p; ++j) s += (double)X[(int64_t)j * ld + i] * beta[j];
     out[i] = off ? s + off[i] : s;
   }
 }
@@ -581,7 +582,15 @@ hipError_t launch_predict(const double* X, int64_t ld, int p, int64_t n, const d
   int64_t blocks = (n + 255) / 256;
   if (blocks > 65536) blocks = 65536;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(predict_kernel, dim3((unsigned)blocks), dim3(256), 0, st, X, ld, p, n, beta, off, out, g);
+  hipLaunchKernelGGL(predict_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st, X, ld, p, n, beta, off, out, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_predict(const float* X, int64_t ld, int p, int64_t n, const double* beta, const double* off,
+                          double* out, hipStream_t st) {
+  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(65536, (n + 255) / 256));
+  hipLaunchKernelGGL(predict_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, X, ld, p, n, beta, off, out,
+                     ProcX{});
   return hipGetLastError();
 }
 

@@ -42,6 +42,9 @@ hipError_t launch_reduce(const double* part, int64_t stride, int nparts, int p, 
                          hipEvent_t e1 = nullptr, int extra = 0);
 hipError_t launch_predict(const double* X, int64_t ld, int p, int64_t n, const double* beta, const double* off,
                           double* out, hipStream_t st, const ProcX& g);
+// the same over an fp32-stored design (each x widened before its fp64 product)
+hipError_t launch_predict(const float* X, int64_t ld, int p, int64_t n, const double* beta, const double* off,
+                          double* out, hipStream_t st);
 hipError_t launch_unlink(double* v, const double* m, int64_t n, int family, int link, hipStream_t st);
 hipError_t launch_ysum(const double* y, int64_t n, double* part, int nparts, hipStream_t st);
 uint64_t splitmix64_host(uint64_t x);
@@ -55,6 +58,18 @@ int narrow_wg_per_cu();
 int narrow_rows_per_wg(int P16); // rows one workgroup streams per block step (waves x rows per block)
 hipError_t launch_narrow(int P16, const PassArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
                          hipEvent_t e1 = nullptr);
+
+// narrow path over an fp32-stored design (narrow_f32.hip): a.X32 / a.ld (floats, a multiple of 64); the partials
+// are narrow_stride's.  No LM modes.
+int narrow_f32_rows_per_wg(int P16);
+hipError_t launch_narrow_f32(int P16, const PassArgs& a, int grid, hipStream_t st, hipEvent_t e0 = nullptr,
+                             hipEvent_t e1 = nullptr);
+// dst [rows x cols] = src, column-major with their own leading dimensions: double -> float rounds to nearest
+// even, float -> double is exact
+hipError_t launch_round_f32(const double* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int cols,
+                            hipStream_t st);
+hipError_t launch_widen_f32(const float* src, int64_t lds, double* dst, int64_t ldd, int64_t rows, int cols,
+                            hipStream_t st);
 
 // per-row diagnostics (influence.hip): p <= 256
 // workgroups of a mode (enum InflMode) over n rows; each owns the steps g, g + grid, ...: a fixed order

@@ -213,16 +213,35 @@ class Engine:
         self.close()
 
     # ---- data ----
-    def set_data(self, X, y, m=None, offset=None, prior=None):
-        X = np.asfortranarray(X, dtype=np.float64)
+    def set_data(self, X, y, m=None, offset=None, prior=None, storage: str = "f64"):
+        """storage="f32" (p <= 64): the design is stored as float32 -- X as given if it is float32, rounded on
+        the host otherwise -- and half the bytes go to the device; y / m / offset / prior stay float64."""
+        if storage not in ("f64", "f32"):
+            raise L.IllegalArgumentException(f"requirement failed: storage must be 'f64' or 'f32', got {storage!r}")
+        X = np.asfortranarray(X, dtype=np.float32 if storage == "f32" else np.float64)
         if X.ndim != 2:
             raise L.IllegalArgumentException("requirement failed: X must be a matrix")
         n, p = X.shape
         y, m, offset, prior = _vec(y, n), _vec(m, n), _vec(offset, n), _vec(prior, n)
-        L.check(self._lib.sglm_set_data(self._h, L.ptr(X), n, p, n, L.ptr(y), L.ptr(m), L.ptr(offset),
-                                        L.ptr(prior)), "sglm_set_data")
+        if storage == "f32":
+            L.check(self._lib.sglm_set_data_f32(self._h, X.ctypes.data_as(C.POINTER(C.c_float)), n, p, n, L.ptr(y),
+                                                L.ptr(m), L.ptr(offset), L.ptr(prior)), "sglm_set_data_f32")
+        else:
+            L.check(self._lib.sglm_set_data(self._h, L.ptr(X), n, p, n, L.ptr(y), L.ptr(m), L.ptr(offset),
+                                            L.ptr(prior)), "sglm_set_data")
         self.n, self.p = n, p
         return self
+
+    def store_f32(self):
+        """Round the resident float64 design to float32 storage and free the float64 image (sglm_store_f32)."""
+        L.check(self._lib.sglm_store_f32(self._h), "sglm_store_f32")
+        return self
+
+    @property
+    def storage(self) -> str:
+        s = C.c_int(0)
+        L.check(self._lib.sglm_get_storage(self._h, C.byref(s)), "sglm_get_storage")
+        return "f32" if s.value == 1 else "f64"
 
     def reserve(self, n: int, p: int, m=False, offset=False, prior=False):
         """Allocate the resident shard; rows then arrive by set_rows (partition-wise ingest)."""
@@ -276,14 +295,16 @@ class Engine:
         self.n, self.p = n, p
         return self
 
-    def synth(self, kind: int, row0: int, n: int, p: int, seed: int, procedural: bool = False):
+    def synth(self, kind: int, row0: int, n: int, p: int, seed: int, procedural: bool = False, storage: str = "f64"):
         """Rows [row0, row0+n) of the seeded synthetic design generated in HBM.  procedural=True
         stores y (+ offset / prior) only and regenerates X inside the kernels (wide path)."""
+        if storage not in ("f64", "f32"):
+            raise L.IllegalArgumentException(f"requirement failed: storage must be 'f64' or 'f32', got {storage!r}")
         fn = self._lib.sglm_synth_procedural if procedural else self._lib.sglm_synth
         L.check(fn(self._h, int(kind), int(row0), int(n), int(p), C.c_uint64(seed & (2**64 - 1))),
                 "sglm_synth_procedural" if procedural else "sglm_synth")
         self.n, self.p = n, p
-        return self
+        return self.store_f32() if storage == "f32" else self
 
     def get_data(self):
         X = np.empty((self.n, self.p), order="F")

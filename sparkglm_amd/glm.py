@@ -274,7 +274,7 @@ def _to_pre(f) -> PreGLM:
 
 def _fit_components(y: Frame, x: Frame, family: str, link: str, tol: float, verbose: bool,
                     offset: Optional[Frame] = None, m: Optional[Frame] = None, prior: Optional[Frame] = None,
-                    device: int = 0) -> PreGLM:
+                    device: int = 0, storage: str = "f64") -> PreGLM:
     npart = x.rdd.partitions.size()
     fam, lnk = _engine_family_link(family, link)
     for extra in (offset, m, prior):
@@ -284,7 +284,10 @@ def _fit_components(y: Frame, x: Frame, family: str, link: str, tol: float, verb
             _require(extra.count() == y.count(), "The two DataFrames must have the same number of rows")
     eng = _engine(device)
     eng.set_data(x.to_matrix(), y.to_vector(), None if m is None else m.to_vector(),
-                 None if offset is None else offset.to_vector(), None if prior is None else prior.to_vector())
+                 None if offset is None else offset.to_vector(), None if prior is None else prior.to_vector(),
+                 **({} if storage == "f64" else {"storage": storage}))
+    # (the keyword is passed only when asked for: tests/test_links.py drives this function with a stand-in engine
+    # whose set_data has the five positional arguments alone)
     f = eng.fit_glm(fam, lnk, tol=tol, verbose=verbose, init="single" if npart == 1 else "multiple", npart=npart)
     return _to_pre(f)
 
@@ -441,8 +444,10 @@ class GLM:
                         pre.nrow, pre.npart)
 
     @staticmethod
-    def fit(y: Frame, x: Frame, *args, device: int = 0) -> GLMModel:
-        """The sixteen Scala overloads (GLM.scala:597-995), dispatched on argument types."""
+    def fit(y: Frame, x: Frame, *args, device: int = 0, storage: str = "f64") -> GLMModel:
+        """The sixteen Scala overloads (GLM.scala:597-995), dispatched on argument types.  storage="f32"
+        (p <= 64) keeps the design on the device as float32 (Engine.set_data); the model is the fit of the
+        design rounded to float32."""
         args = list(args)
         offset = None
         if args and isinstance(args[0], Frame):
@@ -476,7 +481,7 @@ class GLM:
             if npart > 1 and not four_arg:
                 # "Will change to fitDouble": fitSingle -> dfToDenseMatrix requires one partition
                 _single_partition(x)
-        pre = _fit_components(y, x, family, link, tol, verbose, offset=offset, m=m, device=device)
+        pre = _fit_components(y, x, family, link, tol, verbose, offset=offset, m=m, device=device, storage=storage)
         return GLM.createObj(x, y, pre, family, link)
 
     @staticmethod
