@@ -26,31 +26,18 @@
 // r ^ f(c) (swz below), applied on the DMA source address.  MFMA fragment reads (lane
 // (rq, cl) reads row 4s+rq of column 16b+cl) and row-stage reads (lane (g, rl) reads row rl
 // of column (64/NRB)u+g) are both bank-conflict free for ds_read_b64.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+//
+// Shared with narrow_f32.hip, in narrow_core.hpp: the issue priorities, the lane helpers, gram_kstep
+// (with its T4 form), the weighted k-step around it and the Poisson table prologue.  The row step and
+// the epilogue are still written out here and there: as shared functions they changed some kernels'
+// register figures (profiles/narrow_core_isa.txt).
 #include <type_traits>
 
-#include "common.hpp"
-#include "kernels.hpp"
-#include "rowmath.hpp"
-#include "waitcnt.hpp"
+#include "narrow_core.hpp"
 
 namespace sglm {
 
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-// Issue priority by phase: a wave runs its row stage (eta, the family arithmetic: a dependent fp64
-// chain) at high priority and its Grams at low, so the partner wave's MFMA stream fills the row
-// stage's latencies instead of delaying its instructions (round 5: p = 32 -2 %, p = 48 -1 %, p = 64
-// +-0 against priorities alternating between the two waves every 4 blocks; 12 waves a CU on 8-row
-// blocks at p > 32: +18-20 %, DESIGN.md 4 K1').  Measured and not kept: the diagonal tiles on three
-// v_mfma_f64_4x4x4f64 (rotated B operands from LDS or by DPP: slower at p = 32 and 64); a
-// batched Gram phase (all operands, then all VALU, then all MFMAs per block: p = 64 +25 %).
-constexpr int PRIO_ROWS = 2, PRIO_GRAM = 0;
 
 // Rows per block NRB: 32 for p <= 32 (the family arithmetic then runs on 32 lanes), 16 above
 // (LDS: 8 waves x 2 buffers).  Row swizzle f(c): 2((c >> 1) & 7) at NRB = 16 (the column
@@ -117,17 +104,6 @@ static_assert(VmCount<4>::younger(1, 1) == 4 * 16 / 8 + 2 && VmCount<1>::younger
 template <int NRB>
 __device__ __forceinline__ constexpr int swz(int c) { return NRB == 16 ? 2 * ((c >> 1) & 7) : 2 * (c & 15); }
 
-__device__ __forceinline__ double xor16_sum(double v) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__double2loint(v), __double2loint(v), false, false);
-  const auto b = __builtin_amdgcn_permlane16_swap(__double2hiint(v), __double2hiint(v), false, false);
-  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-__device__ __forceinline__ double xor32_sum(double v) {
-  const auto a = __builtin_amdgcn_permlane32_swap(__double2loint(v), __double2loint(v), false, false);
-  const auto b = __builtin_amdgcn_permlane32_swap(__double2hiint(v), __double2hiint(v), false, false);
-  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-
 // DMA of block blk into buffer buf of this wave's image: NOCT wave-instructions of CPI
 // columns x NRB rows (1 KiB each) + one for the block's slices of y, m, offset, prior
 // (4 x NRB doubles on 2 NRB lanes).  Column groups past the stored columns re-load the last
@@ -147,39 +123,6 @@ __device__ __forceinline__ void nstage(double* wl, int buf, const PassArgs& a, i
   }
   if (G::NRB == 32 || lane < 2 * G::NRB)
     __builtin_amdgcn_global_load_lds((const void*)(vsrc + blk * G::NRB), (lds_void*)(dst + G::XB), 16, 0, AUX);
-}
-
-// Lane l of a 16-lane row takes the value of lane l & ~12 (the first 4-lane group's lane of the same
-// position): ds_swizzle in bit mode, and_mask 0b10011 on the lane id within 32.
-__device__ __forceinline__ double bcast_quad0(double v) {
-  const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), 0x13);
-  const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), 0x13);
-  return __hiloint2double(hi, lo);
-}
-
-// One k-step (4 rows) of the lower-triangular Gram on v_mfma_f64_16x16x4_f64.
-// T4 (P16 = 2, p <= 20: the second column block holds at most 4 real columns, 16..19): the two
-// tiles of that block's row run on v_mfma_f64_4x4x4f64, which takes its operands in the 16x16x4
-// lane layout with 4x4 block j on columns 4j..4j+3 (tools/mfma_layout.hip) and writes block j's
-// D(m, n) to lane 16 m + 4 j + n -- exactly where the 16x16x4 tile keeps rows 0..3 of its D in
-// acc[t][0].  Tile (1, 1): block 0 is columns 16..19 x 16..19; tile (1, 0): the A operand's first
-// 4-lane group (columns 16..19) broadcast to all four groups gives columns 16..19 x 4j..4j+3 in
-// block j.  16 MFMA cycles each instead of 64 (the LM Gram of configs[0], p = 20: 96 per k-step
-// instead of 192); rows 4..15 of those tiles (columns 20..31: padding) are never formed.
-template <int P16, bool T4 = false>
-__device__ __forceinline__ void gram_kstep(d4 (&acc)[NGeo<P16>::T], const double (&av)[P16], const double (&xv)[P16]) {
-  if constexpr (T4) {
-    static_assert(P16 == 2, "T4: two column blocks");
-    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[0], xv[0], acc[0], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(bcast_quad0(av[1]), xv[0], acc[1][0], 0, 0, 0);
-    acc[2][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(av[1], xv[1], acc[2][0], 0, 0, 0);
-  } else {
-    int t = 0;
-#pragma unroll
-    for (int bi = 0; bi < P16; ++bi)
-#pragma unroll
-      for (int bj = 0; bj <= bi; ++bj, ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[bi], xv[bj], acc[t], 0, 0, 0);
-  }
 }
 
 // IRLS: compile-time a.mode == MODE_IRLS (the iterations); the init and LM Gram passes run the
@@ -215,18 +158,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
   double* ptab = lds + G::LDS;     // PTAB: [2][POIS_TAB]; YTAB: [POIS_TAB]
   double* pconst = ptab + 2 * POIS_TAB;  // init_const (PTAB)
   const double* ylogy = YTAB ? ptab : nullptr;
-  if constexpr (YTAB) {
-    for (int k = threadIdx.x; k < POIS_TAB; k += 64 * G::NW) poisson_ylogy_table(ptab, k);
-    __syncthreads();
-  }
-  if constexpr (PTAB) {
-    for (int k = threadIdx.x; k < POIS_TAB; k += 64 * G::NW) poisson_init_table(ptab, a.mu0, k);
-    if (threadIdx.x == 0) {
-      const InitConst ic = init_const(FAM, link_of<LNK>(a.link), a.mode, a.mu0, link_by_link(FAM, LNK));
-      for (int k = 0; k < 6; ++k) pconst[k] = ic.v[k];
-    }
-    __syncthreads();
-  }
+  fill_poisson_tables<FAM, LNK, PTAB, YTAB, 64 * G::NW>(ptab, a);
 
   const int64_t nb = a.nblocks * (RB / NRB);  // NRB-row blocks (n_pad = nblocks * RB)
   const int64_t gw = (int64_t)blockIdx.x * G::NW + wv, nwt = (int64_t)gridDim.x * G::NW;
@@ -438,15 +370,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
           for (int k = 0; k < KS; ++k) {
             const int r = 4 * k + rq + (h == 0 ? NRB : 0);
             const double wr = wl[G::OFF_W + r], wzr = wl[G::OFF_W + 2 * NRB + r];
-            double av[P16], xk[P16];
-#pragma unroll
-            for (int b = 0; b < P16; ++b) {
-              xk[b] = h == 0 ? xp[k][b] : xc[k][b];
-              av[b] = xk[b] * wr;
-              xz[b] += xk[b] * wzr;
-              if constexpr (LMX) x1[b] += xk[b];
-            }
-            gram_kstep<P16, T4>(acc, av, xk);
+            weighted_kstep<T4, LMX>(acc, xz, x1, [&](int b) { return h == 0 ? xp[k][b] : xc[k][b]; }, wr, wzr);
           }
         }
       }
@@ -487,15 +411,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
         for (int k = 0; k < KS; ++k) {
           const int r = 4 * k + rq;
           const double wr = wl[G::OFF_W + r], wzr = wl[G::OFF_W + 2 * NRB + r];
-          double av[P16], xk[P16];
-#pragma unroll
-          for (int b = 0; b < P16; ++b) {
-            xk[b] = xs[goff[k] + G::BSTR * b];
-            av[b] = xk[b] * wr;
-            xz[b] += xk[b] * wzr;
-            if constexpr (LMX) x1[b] += xk[b];
-          }
-          gram_kstep<P16, T4>(acc, av, xk);
+          weighted_kstep<T4, LMX>(acc, xz, x1, [&](int b) { return xs[goff[k] + G::BSTR * b]; }, wr, wzr);
         }
       }
     };
@@ -549,15 +465,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
       for (int s = 0; s < NRB / 4; ++s) {
         const int r = 4 * s + rq;
         const double wr = wl[G::OFF_W + r], wzr = wl[G::OFF_W + NRB + r];
-        double xv[P16], av[P16];
-#pragma unroll
-        for (int b = 0; b < P16; ++b) {
-          xv[b] = xs[goff[s] + G::BSTR * b];
-          av[b] = xv[b] * wr;
-          xz[b] += xv[b] * wzr;
-          if constexpr (LMX) x1[b] += xv[b];
-        }
-        gram_kstep<P16, T4>(acc, av, xv);
+        weighted_kstep<T4, LMX>(acc, xz, x1, [&](int b) { return xs[goff[s] + G::BSTR * b]; }, wr, wzr);
       }
     }
     // every LDS read of this buffer has returned before the DMA may overwrite it
@@ -630,15 +538,7 @@ __global__ void __launch_bounds__(64 * NGeo<P16>::NW, 1) irls_narrow_kernel(Pass
       for (int s2 = 0; s2 < NRB / 4; ++s2) {
         const int r = 4 * s2 + rq + woff;
         const double wr = wl[G::OFF_W + r], wzr = wl[G::OFF_W + 2 * NRB + r];
-        double xv[P16], av[P16];
-#pragma unroll
-        for (int b = 0; b < P16; ++b) {
-          xv[b] = xs[goff[s2] + G::BSTR * b];
-          av[b] = xv[b] * wr;
-          xz[b] += xv[b] * wzr;
-          if constexpr (LMX) x1[b] += xv[b];
-        }
-        gram_kstep<P16, T4>(acc, av, xv);
+        weighted_kstep<T4, LMX>(acc, xz, x1, [&](int b) { return xs[goff[s2] + G::BSTR * b]; }, wr, wzr);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every read of the buffer returned
     };

@@ -55,28 +55,22 @@
 //    2    64   4    3      8 + 2          20 / 22             120 KiB (+ tables)
 //    3    32   8    2      6 + 1           7 /  8             112 KiB (+ tables)
 //    4    32   8    2      8 + 1           9 / 10             144 KiB (+ tables)
-#include <hip/hip_runtime.h>
-
+//
+// Shared with narrow.hip, in narrow_core.hpp: the issue priorities by phase, the lane helpers, gram_kstep
+// (its T4 form included: the same lane layout, the same accumulators), the weighted k-step around it and
+// the Poisson table prologue.  The row step and the epilogue are still this file's own: as shared
+// functions they changed some kernels' register figures (profiles/narrow_core_isa.txt).
 #include <algorithm>
-#include <cstdint>
 #include <type_traits>
 
-#include "common.hpp"
-#include "kernels.hpp"
-#include "rowmath.hpp"
-#include "waitcnt.hpp"
+#include "narrow_core.hpp"
 
 namespace sglm {
 
 namespace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-// issue priority by phase, as narrow.hip: the row stage (a dependent fp64 chain) high, the Gram low
-constexpr int PRIO_ROWS = 2, PRIO_GRAM = 0;
 
 template <int P16>
 struct FGeo {
@@ -111,41 +105,6 @@ static_assert(FGeo<1>::younger(2, 2) == 14 && FGeo<2>::younger(2, 0) == 20 && FG
 template <int NRB>
 __device__ __forceinline__ constexpr int fsw(int c) { return NRB == 64 ? (c & 15) : ((c & 7) ^ ((c >> 3) & 1)); }
 
-__device__ __forceinline__ double xor16_sum(double v) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__double2loint(v), __double2loint(v), false, false);
-  const auto b = __builtin_amdgcn_permlane16_swap(__double2hiint(v), __double2hiint(v), false, false);
-  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-__device__ __forceinline__ double xor32_sum(double v) {
-  const auto a = __builtin_amdgcn_permlane32_swap(__double2loint(v), __double2loint(v), false, false);
-  const auto b = __builtin_amdgcn_permlane32_swap(__double2hiint(v), __double2hiint(v), false, false);
-  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-// lane l of a 16-lane row takes the value of lane l & ~12 (narrow.hip bcast_quad0)
-__device__ __forceinline__ double bcast_quad0(double v) {
-  const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), 0x13);
-  const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), 0x13);
-  return __hiloint2double(hi, lo);
-}
-
-// One k-step (4 rows) of the lower-triangular Gram; T4 (P16 = 2, p <= 20): the second column block's
-// two tiles on v_mfma_f64_4x4x4f64 (narrow.hip gram_kstep: the same lane layout, the same accumulators).
-template <int P16, bool T4>
-__device__ __forceinline__ void gram_kstep(d4 (&acc)[FGeo<P16>::T], const double (&av)[P16], const double (&xv)[P16]) {
-  if constexpr (T4) {
-    static_assert(P16 == 2, "T4: two column blocks");
-    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[0], xv[0], acc[0], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(bcast_quad0(av[1]), xv[0], acc[1][0], 0, 0, 0);
-    acc[2][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(av[1], xv[1], acc[2][0], 0, 0, 0);
-  } else {
-    int t = 0;
-#pragma unroll
-    for (int bi = 0; bi < P16; ++bi)
-#pragma unroll
-      for (int bj = 0; bj <= bi; ++bj, ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[bi], xv[bj], acc[t], 0, 0, 0);
-  }
-}
-
 // IRLS / STATS / T4 as irls_narrow_kernel's; PassArgs::X32 is the design, PassArgs::ld its leading
 // dimension in floats (a multiple of 64: the last 64-row block of a shard whose n_pad is an odd multiple
 // of RB reads zero rows of X; its row vectors are re-read from the 32 rows before, never past n_pad).
@@ -162,18 +121,7 @@ __global__ void __launch_bounds__(64 * FGeo<P16>::NW, 1) irls_narrow_f32_kernel(
   double* ptab = lds + G::LDS;           // PTAB: [2][POIS_TAB]; YTAB: [POIS_TAB]
   double* pconst = ptab + 2 * POIS_TAB;  // init_const (PTAB)
   const double* ylogy = YTAB ? ptab : nullptr;
-  if constexpr (YTAB) {
-    for (int k = threadIdx.x; k < POIS_TAB; k += 64 * G::NW) poisson_ylogy_table(ptab, k);
-    __syncthreads();
-  }
-  if constexpr (PTAB) {
-    for (int k = threadIdx.x; k < POIS_TAB; k += 64 * G::NW) poisson_init_table(ptab, a.mu0, k);
-    if (threadIdx.x == 0) {
-      const InitConst ic = init_const(FAM, link_of<LNK>(a.link), a.mode, a.mu0, link_by_link(FAM, LNK));
-      for (int k = 0; k < 6; ++k) pconst[k] = ic.v[k];
-    }
-    __syncthreads();
-  }
+  fill_poisson_tables<FAM, LNK, PTAB, YTAB, 64 * G::NW>(ptab, a);
 
   const int64_t n_pad = a.nblocks * RB;
   const int64_t nb = (n_pad + NRB - 1) / NRB;  // NRB-row blocks
@@ -333,14 +281,8 @@ __global__ void __launch_bounds__(64 * FGeo<P16>::NW, 1) irls_narrow_f32_kernel(
         const double wr[4] = {w01[0], w01[1], w23[0], w23[1]}, wzr[4] = {z01[0], z01[1], z23[0], z23[1]};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          double xk[P16], av[P16];
-#pragma unroll
-          for (int b = 0; b < P16; ++b) {
-            xk[b] = (double)xf[b][i];
-            av[b] = xk[b] * wr[i];
-            xz[b] += xk[b] * wzr[i];
-          }
-          gram_kstep<P16, T4>(acc, av, xk);
+          // (LMX = false: no X'1 sums here, so the x1 argument is never read -- nullptr stands in)
+          weighted_kstep<T4, false>(acc, xz, nullptr, [&](int b) { return (double)xf[b][i]; }, wr[i], wzr[i]);
         }
       }
     }

@@ -139,7 +139,7 @@ def test_rank_deficient_design_takes_the_host_path(kind):
 @pytest.mark.parametrize("p", [17, 18, 19, 20, 21])
 def test_last_column_block_on_4x4_mfma_matches_the_oracle(p):
     """p <= 20 runs the LM Gram (and the gaussian passes) with the second column block's two tiles on
-    v_mfma_f64_4x4x4f64 (narrow.hip gram_kstep T4); p = 21 is the first width back on 16x16x4."""
+    v_mfma_f64_4x4x4f64 (narrow_core.hpp gram_kstep T4); p = 21 is the first width back on 16x16x4."""
     rng = np.random.default_rng(100 + p)
     n = 200_003
     X = np.column_stack([np.ones(n), rng.uniform(-1, 1, (n, p - 1))])

@@ -8,7 +8,9 @@ the narrow kernel at p = 20, 40, 64, K1 at p = 128, K1r at p = 256, the wide pat
 binomial logit (both init modes; with m; with an offset and prior weights that include zeros) and probit,
 Poisson log on counts with fractional values and values >= 256 (the reference rows beside the fast path and
 the tables; offset, prior weights with zeros, both init modes) and sqrt, Gamma inverse and log, negative
-binomial log and sqrt at theta = 2.
+binomial log and sqrt at theta = 2.  The fp32-X narrow kernel (storage="f32") at p = 20, 40, 64: binomial logit
+plain and with m, the Poisson counts with offset and zero prior weights.  fit_lm at p = 20 and 40 (the LM Gram
+pass with X'1 and y'y, at p = 20 on the 4x4x4 tiles).
 Diagnostics and the steps over the cluster factor (p = 5 and 65, the two-way designs of tests/fe2_reference.py,
 every family): fit_glm_fe, fit_glm_fe2, fit_glm_gee (exchangeable, rho fixed at 0.2, independence), fe_pass and
 gee_pass at 0.8 beta and in the initial mode (the GEE fits stop after GEE_ITERS iterations at the latest), vcov_fe, vcov_fe2 and vcov_gee (with their meats), influence (every
@@ -113,6 +115,14 @@ def _fit_cases():
         out.append((f"poisson:sqrt:{p}:single", "poisson", "sqrt", "single", links("poisson", p)))
         out.append((f"gamma:log:{p}:multiple", "gamma", "log", "multiple", links("gamma", p)))
         out.append((f"negbin:sqrt:{p}:single", "negbin", "sqrt", "single", negbin("sqrt", p)))
+
+    def f32(make):  # the same data with the design stored as float32 (the fp32-X narrow kernel)
+        return lambda: dict(make(), storage="f32")
+
+    for p in (20, 40, 64):
+        out.append((f"f32:binomial:logit:{p}:single", "binomial", "logit", "single", f32(binomial(p))))
+        out.append((f"f32:binomial:logit:{p}:m", "binomial", "logit", "multiple", f32(binomial(p, with_m=True))))
+        out.append((f"f32:poisson:log:{p}:single", "poisson", "log", "single", f32(poisson_counts(p))))
     return out
 
 
@@ -185,12 +195,23 @@ def child(out_path):
             d = make()
             if "theta" in d:
                 e.set_theta(d["theta"])
-            e.set_data(d["X"], d["y"], m=d.get("m"), offset=d.get("offset"), prior=d.get("prior"))
+            e.set_data(d["X"], d["y"], m=d.get("m"), offset=d.get("offset"), prior=d.get("prior"),
+                       storage=d.get("storage", "f64"))
             t0 = time.perf_counter()
             _guard(res, name, lambda: {"fit": _fit_vec(e.fit_glm(fam, lnk, init=init))})
             st = e.stats()
             print(f"CASE {name:32s} {st.get('pass_kernel_kind', '?'):8s} variant {st.get('kernel_variant')} "
                   f"{time.perf_counter() - t0:.3f} s", flush=True)
+
+        for p in (20, 40):  # the LM Gram pass with X'1 and y'y (LMX), at p = 20 on the 4x4x4 tiles (T4)
+            X, y, _, _ = synth.generate(1, 0, N, p, 5)
+            e.set_data(X, y)
+
+            def lm():
+                f = e.fit_lm()
+                return {"fit": np.concatenate([f.coefs, f.stderr, np.ravel(f.xtxi), [f.sse, f.r2, f.fstat, f.sigma]])}
+            _guard(res, f"lm:{p}", lm)
+            print(f"CASE lm:{p}", flush=True)
 
         T = L.cluster_plan(np.zeros(0, dtype=np.int32), 1)[0]
         for p, layout in ((5, "sorted"), (65, "sorted"), (5, "interleaved"), (5, "shuffled")):

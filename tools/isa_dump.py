@@ -19,8 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-OBJECTS = ("kernels", "fused_odd", "narrow", "wide", "influence", "theta", "cluster", "fe_hip", "fe2_hip",
-           "gee_hip")
+OBJECTS = ("kernels", "fused_odd", "narrow", "narrow_f32", "wide", "influence", "theta", "cluster", "blockgram",
+           "fe_hip", "fe2_hip", "gee_hip", "multinom_hip")
 
 
 def _code_objects(run):
@@ -164,7 +164,7 @@ def diff(a: str, b: str) -> int:
             moved[txt] = moved.get(txt, 0) + 1
             karg += 1
             continue
-        print(f"differs: {f}")
+        print(f"differs ({len(la)} -> {len(lb)} instructions): {f}")
         bad += 1
     for txt, k in sorted(moved.items()):
         print(f"  offsets {txt}: {k} symbols")
